@@ -15,6 +15,10 @@ The top-level ``value`` / ``dtype`` / ``roofline`` are the FLOAT64 run: float64 
 arithmetic (metropolis_engine.py:41, :51), 288 B of state traffic per chain-step.  The float32 build of the same
 kernels (144 B per chain-step, the production dtype) is the sibling block ``f32``.  ``roofline_hbm`` is the same
 float64 kernel at 2^22 chains, where the state (604 MB) no longer fits the 256 MiB Infinity Cache.
+
+``--dump-outputs DIR`` writes the headline engine's state after the last timed step (parameters, energies and widths of a
+fixed sample of 2^16 chains, and the acceptance counters) as ``DIR/<name>.npy``, so that two builds can be compared
+output for output on identical inputs.
 """
 import argparse
 import json
@@ -290,6 +294,28 @@ def roofline_block(dtype, chains_log2, kernel_ms, bound):
                     % (per_step, "fp64" if dtype == "f64" else "fp32", chains_log2)}
 
 
+DUMP_CHAINS = 1 << 16                    # chains sampled by --dump-outputs (seeded, the same for every run)
+
+
+def dump_outputs(engine, out_dir, dtype):
+    """What a caller of the timed path receives after its last step -- the chain parameters, energies and proposal
+    widths, and the (accepted, proposed) counters -- as ``out_dir/<name>.npy``.  Above DUMP_CHAINS chains a fixed,
+    seeded sample of chains is written (``chain_index`` names them), which keeps the files at a few MB."""
+    import numpy as np
+    from metropolisengine_amd import _capi
+    os.makedirs(out_dir, exist_ok=True)
+    n = engine.n_chains
+    idx = np.arange(n) if n <= DUMP_CHAINS else np.sort(np.random.default_rng(2026).choice(n, DUMP_CHAINS, replace=False))
+    kind = np.float64 if dtype == "f64" else np.float32
+    arrays = {"chain_index": idx.astype(np.float64),
+              "real_params": engine._get(_capi.FIELD_PARAMS)[idx].astype(kind),
+              "energy": engine._get(_capi.FIELD_ENERGY)[idx].astype(kind),
+              "sampling_width": engine._get(_capi.FIELD_WIDTH)[idx].astype(kind),
+              "accept_stats": np.array(engine.accept_stats(), dtype=np.float64)}
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+
 def bound_label(state_bytes):
     return "hbm+infinity-cache" if state_bytes <= INFINITY_CACHE_BYTES else "hbm"
 
@@ -309,7 +335,12 @@ def main():
                     "BASELINE configs 3-5 through their protocols (a few seconds; at every --gpus N)")
     ap.add_argument("--pool-backend", default="native", choices=("native", "torch"),
                     help="all-reduce of the pooled moments: the engine's own RCCL communicator, or torch.distributed")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the headline engine's state (rank 0's shard, a fixed sample of "
+                         "chains) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # stdout carries exactly ONE line, the JSON record: RCCL prints a version banner to stdout when a communicator is
     # created, and child libraries may print too -- everything before the record goes to stderr instead
@@ -410,6 +441,8 @@ def main():
     kernel_ms = dev_ms / args.steps                        # average launch duration (events, same timed region)
     per_step = BYTES_PER_CHAIN_STEP_F64 if args.dtype == "f64" else BYTES_PER_CHAIN_STEP
     roofline = roofline_block(args.dtype, args.chains_log2, kernel_ms, bound_label(per_step // 2 * n_local))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(engine, args.dump_outputs, args.dtype)
 
     # observability of the multi-GPU layout: how many ranks the collective backend really joined, and who owns what
     ranks_seen, offsets = 1, [rank * n_local]

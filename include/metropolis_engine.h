@@ -2,7 +2,7 @@
  * metropolis_engine.h -- C ABI of libmetropolis_hip.so, the MI355X (gfx950) many-chain Metropolis engine.
  *
  * This is the drop-in boundary for the reference's hot path.  The reference has no FFI: its "plugin API" is
- * the Python class MetropolisEngine (/root/reference/metropolisengine/metropolis_engine.py:10-463).  Each
+ * the Python class MetropolisEngine (the reference's metropolisengine/metropolis_engine.py:10-463).  Each
  * entry point below replaces one piece of that class for N independent chains on one GPU; the Python class
  * metropolisengine_amd.MetropolisEngine binds them with ctypes (see INTEGRATION.md for the stub).
  *

@@ -1,6 +1,6 @@
 // C-ABI of libmetropolis_hip.so (declared in include/metropolis_engine.h): engine lifetime, launches, field
 // transfer.  Host logic here mirrors the constructor and counters of the reference class
-// (/root/reference/metropolisengine/metropolis_engine.py:17-133); the arithmetic lives in the kernels.
+// (the reference's metropolisengine/metropolis_engine.py:17-133); the arithmetic lives in the kernels.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>

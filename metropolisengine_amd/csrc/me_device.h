@@ -1,7 +1,7 @@
 // Device code of the many-chain Metropolis engine for gfx950 (MI355X): one lane owns one chain, one wavefront a
 // tile of 64 chains; the chain's state lives in registers for the whole launch.
 //
-// Reference semantics (file = /root/reference/metropolisengine/metropolis_engine.py):
+// Reference semantics (file = the reference's metropolisengine/metropolis_engine.py):
 //   k_step     step_all / step_real_group / step_complex_group :209-259, draw_*_group :261-302,
 //              metropolis_decision :319-338, update_*_sigma :429-456
 //   k_measure  measure* :342-383, update_*_mean :404-410, update_covariance_matrix_* :416-427,

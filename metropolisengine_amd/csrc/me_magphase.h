@@ -1,5 +1,5 @@
 // k_step_magphase: the reference's alternative complex sampler, step_complex_group under
-// complex_sample_method="magnitude-phase" (/root/reference/metropolisengine/metropolis_engine.py:168-207, :304-317).
+// complex_sample_method="magnitude-phase" (the reference's metropolisengine/metropolis_engine.py:168-207, :304-317).
 //
 // One step = two Metropolis decisions on the complex group (the real parameters rest):
 //   magnitude stage (:178-192, :304-310)  |z_j| -> |z_j| + (sigma_c^2 Re K_jj) g_j at fixed phase -- the reference

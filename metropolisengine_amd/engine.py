@@ -1,6 +1,6 @@
 """``MetropolisEngine``: the reference's class surface over N independent chains on one MI355X.
 
-Mirrors ``metropolisengine.MetropolisEngine`` (/root/reference/metropolisengine/metropolis_engine.py:10-463):
+Mirrors ``metropolisengine.MetropolisEngine`` (the reference's metropolisengine/metropolis_engine.py:10-463):
 same constructor arguments in the same order, ``step_all()`` / ``measure()``, the same attribute names.  All
 arithmetic happens in libmetropolis_hip.so (HIP kernels, C ABI in include/metropolis_engine.h); this class only
 marshals arguments and unpacks results.  Differences from the reference, all forced by the GPU setting:

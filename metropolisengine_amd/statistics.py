@@ -1,6 +1,6 @@
 """Post-hoc equilibration statistics -- host side, off the accelerated hot path.
 
-Mirrors ``/root/reference/metropolisengine/statistics.py:25-64`` (``get_equilibration_points``,
+Mirrors the reference's ``metropolisengine/statistics.py:25-64`` (``get_equilibration_points``,
 ``get_equilibrated_means``) and ``MetropolisEngine.save_equilibrium_stats`` (metropolis_engine.py:481-504).
 
 PARITY UNPINNED.  The arithmetic of the reference lives in ``pymbar.timeseries.detectEquilibration`` (statistics.py:4,

@@ -3,7 +3,7 @@
  * the strong CPU baseline; the product never links or loads it.
  *
  * Restates, for N independent chains, the reference's step_all with the identity proposal shape
- * (/root/reference/metropolisengine/metropolis_engine.py): draw_real_group :261-272 and draw_complex_group :274-302
+ * (the reference's metropolisengine/metropolis_engine.py): draw_real_group :261-272 and draw_complex_group :274-302
  * with covariance = identity, metropolis_decision :319-338, update_*_sigma :429-456, for the diagonal quadratic
  * energy sum a_i x_i^2 + sum b_j |z_j|^2 (README.md:26-27, BASELINE configs 1-3).  float64 throughout, like the
  * reference.  Random streams: the counter-based Philox4x32-10 layout specified in oracle/philox.py, so a chain here

@@ -1,7 +1,9 @@
 """Generate tests/golden/*.npz from the IMPORTED reference -- TEST INFRASTRUCTURE ONLY.
 
-Runs only in the build container (needs ``/root/reference``); the fixtures it
-writes are committed, the reference is not.  ``pymbar`` (imported by
+Needs a checkout of the reference, named by ``--reference DIR`` or the
+``METROPOLIS_REFERENCE`` environment variable (the directory that holds its
+``metropolisengine`` package); the fixtures it writes are committed, the
+reference is not.  ``pymbar`` (imported by
 ``metropolisengine/statistics.py:4``, used only off the hot path) is absent
 offline and is replaced by an empty stub module.
 
@@ -18,9 +20,11 @@ Everything else -- the proposal covariances it builds, the accept rule, width
 adaptation, running mean / covariance / observables -- is the reference's own
 code.  A second set of anchors uses the reference's legacy seeded RNG unpatched.
 
-Usage:  PYTHONHASHSEED=0 PYTHONDONTWRITEBYTECODE=1 python oracle/make_golden.py            # rewrite tests/golden/
-        PYTHONHASHSEED=0 PYTHONDONTWRITEBYTECODE=1 python oracle/make_golden.py --check    # regenerate into a temporary
-                                                   directory and compare every array with the committed fixtures
+Usage:  PYTHONHASHSEED=0 PYTHONDONTWRITEBYTECODE=1 python oracle/make_golden.py --reference DIR            # rewrite
+                                                   tests/golden/
+        PYTHONHASHSEED=0 PYTHONDONTWRITEBYTECODE=1 python oracle/make_golden.py --reference DIR --check    # regenerate
+                                                   into a temporary directory and compare every array with the
+                                                   committed fixtures
 
 PYTHONHASHSEED=0 is required: the reference iterates a ``set`` of energy-term names when it records the per-term energy
 series (metropolis_engine.py:112-114), so the ORDER of its ``<term>_energy`` DataFrame columns follows the hash seed; with
@@ -42,13 +46,14 @@ from oracle import scenarios                                   # noqa: E402
 from oracle.reference_chain import complex_proposal_factor     # noqa: E402
 
 GOLDEN_DIR = os.path.join(ROOT, "tests", "golden")
+REFERENCE_DIR = None        # set by main(): --reference DIR, else $METROPOLIS_REFERENCE
 
 
 def import_reference():
     for name in ("pymbar", "pymbar.timeseries"):
         sys.modules.setdefault(name, types.ModuleType(name))
     sys.modules["pymbar"].timeseries = sys.modules["pymbar.timeseries"]
-    sys.path.insert(0, "/root/reference")
+    sys.path.insert(0, REFERENCE_DIR)
     import metropolisengine                                     # noqa: E402
     return metropolisengine
 
@@ -225,10 +230,20 @@ def check():
 
 
 def main():
+    global REFERENCE_DIR
+    import argparse
+    ap = argparse.ArgumentParser(description="generate or check tests/golden/ from the reference")
+    ap.add_argument("--reference", default=os.environ.get("METROPOLIS_REFERENCE"),
+                    help="directory holding the reference's metropolisengine package (default: $METROPOLIS_REFERENCE)")
+    ap.add_argument("--check", action="store_true", help="regenerate into a temporary directory and compare")
+    args = ap.parse_args()
     if os.environ.get("PYTHONHASHSEED") != "0":
         sys.exit("run with PYTHONHASHSEED=0 (the reference's energy-term column order follows the hash seed; see the "
                  "module docstring)")
-    if "--check" in sys.argv[1:]:
+    if not args.reference or not os.path.isdir(os.path.join(args.reference, "metropolisengine")):
+        sys.exit("name the reference checkout with --reference DIR or METROPOLIS_REFERENCE (DIR/metropolisengine)")
+    REFERENCE_DIR = os.path.abspath(args.reference)
+    if args.check:
         sys.exit(1 if check() else 0)
     generate()
 
