@@ -15,6 +15,7 @@
  *                           README.md:49-51; also the only "checkpoint" the reference has (ctor warm start, :17)
  *   me_accept_stats      <- the bool returned by step_all (:259), accumulated
  *   me_pooled_moments*   <- no reference equivalent (ensemble estimate across chains)
+ *   me_set_temperature_ladder, me_replica_*  <- no reference equivalent (parallel tempering across the chains)
  *   me_comm_*, me_pooled_moments_allreduce*  <- no reference equivalent (the one collective: RCCL all-reduce of the moments)
  *   me_last_error        <- Python exceptions (:39 ValueError, :92/:438 AssertionError, numpy ValueError :270)
  *
@@ -271,6 +272,33 @@ int me_set_stream(me_engine *engine, void *hip_stream);
 /* Enqueue n_launches launches of n_sweeps sweeps bracketed by HIP events on the engine's stream and return the
  * elapsed milliseconds (device time of the whole span). */
 int me_time_steps(me_engine *engine, int32_t n_launches, int32_t n_sweeps, float *elapsed_ms);
+
+/* Temperature ladders and replica exchange (parallel tempering; no reference counterpart).
+ *   me_set_temperature_ladder  T_0 < T_1 < ... < T_{K-1}, all finite and > 0: the n_chains local chains become K rungs of
+ *                       M = n_chains / K consecutive chains (M a multiple of 64, ME_ERR_INVALID otherwise); chain c steps at
+ *                       T_{c / M} with exactly the scalar accept rule at that temperature.  Resets the swap round and the
+ *                       swap counters.  n_rungs = 0 returns the engine to its scalar temp.  ME_ERR_UNSUPPORTED (with the
+ *                       reason in me_last_error) on the runtime-dimension set (more than 96 real degrees of freedom), on
+ *                       the matrix-core dense 64-parameter kernels and with ME_FLAG_REFERENCE_ENERGY_LEDGERS.
+ *   me_temperature_ladder      the ladder (n_rungs = 0: none); temps must hold n_rungs doubles, or be NULL for the count.
+ *   me_replica_exchange        enqueue n_rounds swap rounds on the engine's stream (asynchronous, like me_step).  Round r
+ *                       pairs slot j of rung k with slot j of rung k+1 for every k = r (mod 2) and swaps the two chains'
+ *                       configurations (ME_FIELD_PARAMS and every ME_FIELD_ENERGY row) with probability
+ *                       min(1, exp((1/T_k - 1/T_{k+1}) (E_a - E_b))), E = the sum of the ledger rows; a non-finite energy
+ *                       never swaps.  Widths, running means, covariances, factors and counters stay with the slot.  The
+ *                       uniform is word 0 of Philox block 0xffff at (global chain id of the rung-k chain, round).
+ *   me_replica_stats           the round counter and, per adjacent pair (k, k+1), the attempted and accepted swaps
+ *                       (n_pairs = n_rungs - 1); me_set_replica_stats restores them from a checkpoint.
+ *   me_pooled_moments_range    me_pooled_moments over chains [chain_begin, chain_begin + n_chains), whole 64-chain tiles
+ *                       (e.g. one rung).  Same layout; the two trailing entries (accepted, proposed) are 0 for a range:
+ *                       acceptance is counted per wavefront of a launch, not per chain (me_accept_stats has the totals). */
+int me_set_temperature_ladder(me_engine *engine, const double *temps, int32_t n_rungs);
+int me_temperature_ladder(me_engine *engine, double *temps, int32_t capacity, int32_t *n_rungs);
+int me_replica_exchange(me_engine *engine, int32_t n_rounds);
+int me_replica_stats(me_engine *engine, uint64_t *round, uint64_t *attempted, uint64_t *accepted, int32_t n_pairs);
+int me_set_replica_stats(me_engine *engine, uint64_t round, const uint64_t *attempted, const uint64_t *accepted,
+                         int32_t n_pairs);
+int me_pooled_moments_range(me_engine *engine, int64_t chain_begin, int64_t n_chains, double *host_out, int64_t n_doubles);
 
 /* Text of the last error on this engine (or of the last failed me_create when engine is NULL). */
 int me_last_error(me_engine *engine, char *buf, size_t buf_bytes);

@@ -92,6 +92,14 @@ SYMBOLS = {
     "me_time_steps": (ctypes.c_int, [_H, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_float)]),
     "me_last_error": (ctypes.c_int, [_H, ctypes.c_char_p, ctypes.c_size_t]),
     "me_supported": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]),
+    "me_set_temperature_ladder": (ctypes.c_int, [_H, _dp, ctypes.c_int32]),
+    "me_temperature_ladder": (ctypes.c_int, [_H, _dp, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)]),
+    "me_replica_exchange": (ctypes.c_int, [_H, ctypes.c_int32]),
+    "me_replica_stats": (ctypes.c_int, [_H, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
+                                        ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32]),
+    "me_set_replica_stats": (ctypes.c_int, [_H, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64),
+                                            ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32]),
+    "me_pooled_moments_range": (ctypes.c_int, [_H, ctypes.c_int64, ctypes.c_int64, _dp, ctypes.c_int64]),
 }
 
 

@@ -179,6 +179,14 @@ struct me_engine {
   // time-series trace of a few chains (the reference's per-measure appends, :350-356)
   double *trace_dev = nullptr;
   long long trace_chains = 0, trace_stride = 1, trace_rows = 0, trace_capacity = 0;
+  // temperature ladder (me_set_temperature_ladder): n_rungs = 0 is the scalar temp
+  int n_rungs = 0;
+  std::vector<double> ladder_temps;
+  void *ladder = nullptr;                        // (inv_temp, inv_temp_log2e) per rung, device dtype
+  unsigned long long *pair_counts = nullptr;     // [2 k] attempted, [2 k + 1] accepted swaps of the rung pair (k, k+1)
+  unsigned long long replica_round = 0;
+  void *range_x = nullptr;                       // me_pooled_moments_range: the range's rows of a component-major x
+  size_t range_bytes = 0;
   std::string err;
 };
 
@@ -353,13 +361,16 @@ void fill_step_launch(me_engine *e, StepLaunch &l, int n_sweeps) {
   l.target_acceptance = e->target_acceptance;
   // step_number_factor = max(measure_step_counter / m, 200)   (metropolis_engine.py:430)
   l.damping = std::max((double)e->measure_count / (double)e->m, 200.0);
+  l.ladder = e->n_rungs ? e->ladder : nullptr;
+  l.tiles_per_rung = e->n_rungs ? (int)(e->n / (64ll * e->n_rungs)) : 0;
 }
 
 void release(me_engine *e) {
   if (!e) return;
   (void)hipSetDevice(e->device);
   void *bufs[] = {e->x, e->energy, e->width, e->mean, e->cov, e->obs_mean, e->factor, e->shared_factor, e->shared_full, e->shared_image, e->energy_image,
-                  e->coef_dev, e->row_dev, e->accept_slots, e->accept_total, e->status, e->pool_dev, e->pool_partials, e->trace_dev};
+                  e->coef_dev, e->row_dev, e->accept_slots, e->accept_total, e->status, e->pool_dev, e->pool_partials, e->trace_dev,
+                  e->ladder, e->pair_counts, e->range_x};
   for (void *b : bufs)
     if (b) (void)hipFree(b);
   if (e->comm && e->rccl) (void)e->rccl->comm_destroy(e->comm);
@@ -1453,6 +1464,165 @@ int me_detect_equilibration(int32_t device_id, const double *series, int64_t n_s
     for (int64_t i = 1; i < length && constant; ++i) constant = row[i] == row[0];
     if (constant) { t0[s] = 0; g[s] = 1.0; neff_max[s] = 1.0; }
   }
+  return ME_OK;
+}
+
+// ---- temperature ladders and replica exchange (me_replica.hip) --------------------------------------------------------
+namespace {
+// why this engine cannot carry a ladder ("" = it can)
+std::string ladder_refusal(const me_engine *e) {
+  if (e->ks->n_real < 0)
+    return "temperature ladders are not available on the runtime-dimension kernel set (beyond " + std::to_string(kMaxRegisterDof) +
+           " real degrees of freedom)";
+  if (e->energy_kind == ME_ENERGY_DENSE_QUAD && e->nr == 64 && e->nc == 0)
+    return "temperature ladders are not available on the matrix-core kernels of the dense 64-parameter form";
+  if (e->stale_total)
+    return "temperature ladders are not available with ME_FLAG_REFERENCE_ENERGY_LEDGERS: its two ledgers make the energy of a "
+           "chain ambiguous";
+  return "";
+}
+int free_ladder(me_engine *e) {
+  ME_HIP(e, hipStreamSynchronize(e->stream));     // launches in flight read the table
+  if (e->ladder) (void)hipFree(e->ladder);
+  if (e->pair_counts) (void)hipFree(e->pair_counts);
+  e->ladder = nullptr;
+  e->pair_counts = nullptr;
+  e->n_rungs = 0;
+  e->ladder_temps.clear();
+  e->replica_round = 0;
+  return ME_OK;
+}
+}  // namespace
+
+int me_set_temperature_ladder(me_engine *e, const double *temps, int32_t n_rungs) {
+  if (!e) return ME_ERR_INVALID;
+  if (n_rungs < 0 || (n_rungs > 0 && !temps)) return fail(e, ME_ERR_INVALID, "n_rungs must be >= 0 and temps given");
+  ME_HIP(e, hipSetDevice(e->device));
+  if (n_rungs == 0) return free_ladder(e);
+  const std::string why = ladder_refusal(e);
+  if (!why.empty()) return fail(e, ME_ERR_UNSUPPORTED, why);
+  for (int k = 0; k < n_rungs; ++k) {
+    if (!(std::isfinite(temps[k]) && temps[k] > 0))
+      return fail(e, ME_ERR_INVALID, "ladder temperatures must be finite and > 0");
+    if (k > 0 && !(temps[k] > temps[k - 1]))
+      return fail(e, ME_ERR_INVALID, "ladder temperatures must be strictly increasing");
+  }
+  if (e->n % (64ll * n_rungs) != 0)
+    return fail(e, ME_ERR_INVALID, "n_chains must be a multiple of 64 * n_rungs: every rung is a run of whole 64-chain tiles");
+  // the step kernels' scalar constants, per rung (me_kernels.hip: typed)
+  std::vector<double> table(2 * (size_t)n_rungs);
+  for (int k = 0; k < n_rungs; ++k) {
+    table[2 * k] = 1.0 / temps[k];
+    table[2 * k + 1] = 1.4426950408889634 / temps[k];
+  }
+  std::vector<unsigned char> bytes;
+  to_device_type(table.data(), table.size(), e->dtype, bytes);
+  int rc = free_ladder(e);
+  if (rc != ME_OK) return rc;
+  ME_HIP(e, hipMalloc(&e->ladder, bytes.size()));
+  ME_HIP(e, hipMemcpy(e->ladder, bytes.data(), bytes.size(), hipMemcpyHostToDevice));
+  const size_t counts = 2 * (size_t)std::max(n_rungs - 1, 1) * sizeof(unsigned long long);
+  ME_HIP(e, hipMalloc((void **)&e->pair_counts, counts));
+  ME_HIP(e, hipMemset(e->pair_counts, 0, counts));
+  e->ladder_temps.assign(temps, temps + n_rungs);
+  e->n_rungs = n_rungs;
+  return ME_OK;
+}
+
+int me_temperature_ladder(me_engine *e, double *temps, int32_t capacity, int32_t *n_rungs) {
+  if (!e || !n_rungs) return ME_ERR_INVALID;
+  *n_rungs = e->n_rungs;
+  if (e->n_rungs == 0 || !temps) return ME_OK;      // (temps = NULL: the count only)
+  if (capacity < e->n_rungs) return fail(e, ME_ERR_INVALID, "temps must hold n_rungs doubles");
+  std::copy(e->ladder_temps.begin(), e->ladder_temps.end(), temps);
+  return ME_OK;
+}
+
+int me_replica_exchange(me_engine *e, int32_t n_rounds) {
+  if (!e) return ME_ERR_INVALID;
+  if (n_rounds < 0) return fail(e, ME_ERR_INVALID, "n_rounds must be >= 0");
+  if (e->n_rungs == 0) return fail(e, ME_ERR_STATE, "no temperature ladder: call me_set_temperature_ladder first");
+  ME_HIP(e, hipSetDevice(e->device));
+  for (int i = 0; i < n_rounds; ++i) {
+    ME_HIP(e, launch_replica_swap(e->x, e->energy, e->n, e->d, e->n_terms, e->x_tiled, e->dtype, e->ladder, e->n_rungs,
+                                  e->replica_round, e->chain_offset, e->seed, e->pair_counts, e->stream));
+    e->replica_round += 1;
+  }
+  return ME_OK;
+}
+
+int me_replica_stats(me_engine *e, uint64_t *round, uint64_t *attempted, uint64_t *accepted, int32_t n_pairs) {
+  if (!e) return ME_ERR_INVALID;
+  if (e->n_rungs == 0) return fail(e, ME_ERR_STATE, "no temperature ladder");
+  if (n_pairs != e->n_rungs - 1) return fail(e, ME_ERR_INVALID, "n_pairs must be n_rungs - 1");
+  if (round) *round = e->replica_round;
+  if (n_pairs == 0) return ME_OK;
+  ME_HIP(e, hipSetDevice(e->device));
+  std::vector<unsigned long long> counts(2 * (size_t)n_pairs);
+  ME_HIP(e, hipMemcpyAsync(counts.data(), e->pair_counts, counts.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, e->stream));
+  ME_HIP(e, hipStreamSynchronize(e->stream));
+  for (int k = 0; k < n_pairs; ++k) {
+    if (attempted) attempted[k] = counts[2 * k];
+    if (accepted) accepted[k] = counts[2 * k + 1];
+  }
+  return ME_OK;
+}
+
+int me_set_replica_stats(me_engine *e, uint64_t round, const uint64_t *attempted, const uint64_t *accepted, int32_t n_pairs) {
+  if (!e) return ME_ERR_INVALID;
+  if (e->n_rungs == 0) return fail(e, ME_ERR_STATE, "no temperature ladder");
+  if (n_pairs != e->n_rungs - 1) return fail(e, ME_ERR_INVALID, "n_pairs must be n_rungs - 1");
+  if (n_pairs > 0 && (!attempted || !accepted)) return fail(e, ME_ERR_INVALID, "attempted / accepted missing");
+  std::vector<unsigned long long> counts(2 * (size_t)n_pairs);
+  for (int k = 0; k < n_pairs; ++k) {
+    if (accepted[k] > attempted[k]) return fail(e, ME_ERR_INVALID, "accepted swaps exceed attempted ones");
+    counts[2 * k] = attempted[k];
+    counts[2 * k + 1] = accepted[k];
+  }
+  ME_HIP(e, hipSetDevice(e->device));
+  if (n_pairs > 0) {
+    ME_HIP(e, hipMemcpyAsync(e->pair_counts, counts.data(), counts.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, e->stream));
+    ME_HIP(e, hipStreamSynchronize(e->stream));
+  }
+  e->replica_round = round;
+  return ME_OK;
+}
+
+int me_pooled_moments_range(me_engine *e, int64_t chain_begin, int64_t n_chains, double *host_out, int64_t n_doubles) {
+  if (!e || !host_out) return ME_ERR_INVALID;
+  if (chain_begin < 0 || n_chains <= 0 || chain_begin + n_chains > e->n || chain_begin % 64 != 0 || n_chains % 64 != 0)
+    return fail(e, ME_ERR_INVALID, "the chain range must be whole 64-chain tiles inside the engine");
+  if (n_doubles != moments_size(e->nr, e->nc)) return fail(e, ME_ERR_INVALID, "wrong pooled-moment buffer length");
+  if (e->pool_pending) return fail(e, ME_ERR_STATE, "a pooled-moment reduction is in flight (me_pooled_moments_end first)");
+  if (!e->pool_partials) return fail(e, ME_ERR_UNSUPPORTED, "pooled moments: dimension too large for the reduction kernel");
+  ME_HIP(e, hipSetDevice(e->device));
+  // the reduction kernels read x as a field of n chains: a tile-major range is one such field already; the rows of a
+  // component-major range are gathered into a field of their own first (one strided device copy)
+  const void *x = nullptr;
+  if (e->x_tiled) {
+    x = (const unsigned char *)e->x + (size_t)chain_begin * e->d * e->esize;
+  } else {
+    const size_t bytes = (size_t)n_chains * e->d * e->esize;
+    if (bytes > e->range_bytes) {
+      ME_HIP(e, hipStreamSynchronize(e->stream));
+      if (e->range_x) (void)hipFree(e->range_x);
+      e->range_x = nullptr;
+      e->range_bytes = 0;
+      ME_HIP(e, hipMalloc(&e->range_x, bytes));
+      e->range_bytes = bytes;
+    }
+    ME_HIP(e, hipMemcpy2DAsync(e->range_x, (size_t)n_chains * e->esize, (const unsigned char *)e->x + (size_t)chain_begin * e->esize,
+                               (size_t)e->n * e->esize, (size_t)n_chains * e->esize, (size_t)e->d, hipMemcpyDeviceToDevice, e->stream));
+    x = e->range_x;
+  }
+  // acceptance is counted per wavefront of a launch, not per chain: a range has no accept / proposal counts (both 0)
+  hipError_t err = launch_pool_reduce(x, n_chains, e->nr, e->nc, e->dtype, e->accept_slots, 0, 0.0, e->pool_partials,
+                                      e->pool_dev, e->stream, e->ks->pool_stage1, e->x_tiled);
+  if (err == hipErrorInvalidValue) return fail(e, ME_ERR_UNSUPPORTED, "pooled moments: dimension too large for the reduction kernel");
+  ME_HIP(e, err);
+  ME_HIP(e, hipMemcpyAsync(e->pool_host, e->pool_dev, sizeof(double) * (size_t)n_doubles, hipMemcpyDeviceToHost, e->stream));
+  ME_HIP(e, wait_polling(e->stream));
+  std::memcpy(host_out, e->pool_host, sizeof(double) * (size_t)n_doubles);
   return ME_OK;
 }
 

@@ -572,7 +572,28 @@ struct StepArgs {
   int split_widths;   // mixed engines: group widths (rows 1, 2) differ from the shared width (row 0)
   int stale_total;    // quirk Q5 mode: a mixed engine's step_all compares against / updates ledger row T only
   R reject_bound, temp, inv_temp, inv_temp_log2e, ratio, p, damping, up, down;
+  // temperature ladder (me_set_temperature_ladder): (inv_temp, inv_temp_log2e) per rung, rung k = chains
+  // [k M, (k+1) M) = tiles [k tiles_per_rung, (k+1) tiles_per_rung); nullptr: every chain at the scalar temp
+  const R *ladder;
+  int tiles_per_rung;
 };
+
+// The uphill test of chain c's accept rule (:329-335) at the chain's temperature.  LADDER = false: the scalar temp of the
+// kernel arguments, exactly as before ladders existed.  LADDER = true: the rung's constants from a.ladder.  A rung is a run
+// of whole 64-chain tiles, so the rung is wave-uniform: the tile index goes through readfirstlane and the two table words
+// are scalar loads (a table of a few rungs stays in the scalar cache); every rung of a ladder has T > 0.
+// (A template flag, not a runtime null check: the check alone, however placed, moved the register allocation of the scalar
+// kernels -- float32 16-parameter k_step 60 -> 73 VGPRs and occupancy 7 -> 6 with the selection once per grid-stride
+// iteration, float64 120 -> 123 VGPRs with the selection at the test.  The headline kernels have no SGPRs to spare.)
+template <bool LADDER, typename R>
+__device__ __forceinline__ bool uphill_at(const StepArgs<R> &a, long long c, R u, R diff) {
+  if constexpr (!LADDER) {
+    return a.temp > R(0) && Num<R>::uphill(u, diff, a.inv_temp, a.inv_temp_log2e);
+  } else {
+    const int rung = __builtin_amdgcn_readfirstlane((int)(c >> 6)) / a.tiles_per_rung;
+    return Num<R>::uphill(u, diff, a.ladder[2 * rung], a.ladder[2 * rung + 1]);
+  }
+}
 
 // packed index of element (i, j), j <= i, of a row-major lower triangle
 __host__ __device__ constexpr int tri(int i, int j) { return i * (i + 1) / 2 + j; }
@@ -700,8 +721,8 @@ __device__ __forceinline__ void propose_registers(const R (&x)[NR + 2 * NC], con
 
 }
 
-template <typename R, int NR, int NC, class Energy, int CK, int GROUP, class Ledger>
-__device__ __forceinline__ void decide_step(const StepArgs<R> &a, const Energy &en, bool stale_total, R u,
+template <typename R, int NR, int NC, class Energy, int CK, int GROUP, bool LADDER, class Ledger>
+__device__ __forceinline__ void decide_step(const StepArgs<R> &a, long long c, const Energy &en, bool stale_total, R u,
                                             const R (&g)[2 * ((NR + 2 * NC + 1) / 2)], R (&x)[NR + 2 * NC], const R (&xp)[NR + 2 * NC],
                                             Ledger &ledger, R &total_q5, R &w, R &w_r, R &w_c, unsigned int &wave_accepted,
                                             bool &bad_energy) {
@@ -717,7 +738,8 @@ __device__ __forceinline__ void decide_step(const StepArgs<R> &a, const Energy &
   const R e_new = ledger.propose(en, xp, terms_new);
   const R diff = e_new - (stale_total ? total_q5 : ledger.partial());
   bool accept = diff <= R(0);
-  if (a.temp > R(0)) accept = accept || N_::uphill(u, diff, a.inv_temp, a.inv_temp_log2e);
+  if constexpr (LADDER) accept = accept || uphill_at<true>(a, c, u, diff);
+  else if (a.temp > R(0)) accept = accept || N_::uphill(u, diff, a.inv_temp, a.inv_temp_log2e);
   accept = accept && !rejected;
   bad_energy |= (!rejected && !N_::finite(e_new));
   if constexpr (CK == CK_IDENTITY) {
@@ -750,7 +772,7 @@ __device__ __forceinline__ void decide_step(const StepArgs<R> &a, const Energy &
 }
 
 // n_sweeps sweeps with a register-resident proposal shape:  x, ledger / total_q5, w, w_r, w_c are updated in place
-template <typename R, int NR, int NC, class Energy, int CK, bool INJECT, int GROUP, class Ledger, class Fac>
+template <typename R, int NR, int NC, class Energy, int CK, bool INJECT, int GROUP, bool LADDER, class Ledger, class Fac>
 __device__ __forceinline__ void run_sweeps(const StepArgs<R> &a, const Energy &en, long long c, unsigned long long gid,
                                            bool stale_total, R (&x)[NR + 2 * NC], Ledger &ledger, R &total_q5, R &w, R &w_r,
                                            R &w_c, Fac &&fac, unsigned int &wave_accepted, bool &bad_energy) {
@@ -760,7 +782,7 @@ __device__ __forceinline__ void run_sweeps(const StepArgs<R> &a, const Energy &e
     R g[NW], u, xp[D];
     draw_step<R, NR, NC, INJECT>(a, c, gid, s, g, u);
     propose_registers<R, NR, NC, CK, GROUP>(x, g, w_r, w_c, fac, xp);
-    decide_step<R, NR, NC, Energy, CK, GROUP>(a, en, stale_total, u, g, x, xp, ledger, total_q5, w, w_r, w_c, wave_accepted, bad_energy);
+    decide_step<R, NR, NC, Energy, CK, GROUP, LADDER>(a, c, en, stale_total, u, g, x, xp, ledger, total_q5, w, w_r, w_c, wave_accepted, bad_energy);
   }
 }
 
@@ -800,7 +822,9 @@ __device__ __forceinline__ void stagger_priority() {
 #endif
 }
 
-template <typename R, int NR, int NC, class Energy, int CK, bool INJECT = false, int GROUP = GROUP_ALL, bool NTS = false>
+// LADDER: the chains step at the temperatures of a ladder (a.ladder, uphill_at) instead of the scalar temp.
+template <typename R, int NR, int NC, class Energy, int CK, bool INJECT = false, int GROUP = GROUP_ALL, bool NTS = false,
+          bool LADDER = false>
 __global__ void ME_STEP_BOUNDS k_step(StepArgs<R> a, Energy en) {
   constexpr int D = NR + 2 * NC;
   constexpr bool MIXED = NR > 0 && NC > 0;
@@ -979,7 +1003,8 @@ __global__ void ME_STEP_BOUNDS k_step(StepArgs<R> a, Energy en) {
         const R e_new = ledger.propose(en, xp, terms_new);
         const R diff = e_new - (stale_total ? total_q5 : ledger.partial());
         bool accept = diff <= R(0);
-        if (a.temp > R(0)) accept = accept || N_::uphill(u_accept, diff, a.inv_temp, a.inv_temp_log2e);
+        if constexpr (LADDER) accept = accept || uphill_at<true>(a, c, u_accept, diff);
+        else if (a.temp > R(0)) accept = accept || N_::uphill(u_accept, diff, a.inv_temp, a.inv_temp_log2e);
         accept = accept && !rejected;
         bad_energy |= (!rejected && !N_::finite(e_new));
 #pragma unroll
@@ -993,7 +1018,7 @@ __global__ void ME_STEP_BOUNDS k_step(StepArgs<R> a, Energy en) {
         wave_accepted += (unsigned int)__popcll(__ballot(accept));
       }
     } else {
-      run_sweeps<R, NR, NC, Energy, CK, INJECT, GROUP>(a, en, c, gid, stale_total, x, ledger, total_q5, w, w_r, w_c, fac, wave_accepted, bad_energy);
+      run_sweeps<R, NR, NC, Energy, CK, INJECT, GROUP, LADDER>(a, en, c, gid, stale_total, x, ledger, total_q5, w, w_r, w_c, fac, wave_accepted, bad_energy);
     }
     bad_width |= !(w > R(0));
 #pragma unroll
@@ -1363,7 +1388,7 @@ __global__ void __launch_bounds__(kStepThreads, ME_MEASURE_WAVES) k_measure(Meas
 #endif
 constexpr int cycle_prefetch_level(int, int, int, int) { return ME_CYCLE_PREFETCH; }
 
-template <typename R, int NR, int NC, class Energy, int CK, bool NT, bool NTM>
+template <typename R, int NR, int NC, class Energy, int CK, bool NT, bool NTM, bool LADDER = false>
 __global__ void ME_STEP_BOUNDS k_cycle(StepArgs<R> a, MeasureArgs<R> ma, Energy en) {
   constexpr int D = NR + 2 * NC;
   constexpr int P = NR * (NR + 1) / 2 + NC * NC;
@@ -1424,7 +1449,7 @@ __global__ void ME_STEP_BOUNDS k_cycle(StepArgs<R> a, MeasureArgs<R> ma, Energy 
         for (int k = 0; k < P; ++k) pre.cv[k] = packed_load<NT>(fcov, k, toff);
       }
     }
-    run_sweeps<R, NR, NC, Energy, CKX, false, GROUP_ALL>(a, en, c, gid, stale_total, x, ledger, total_q5, w, w_r, w_c, fac,
+    run_sweeps<R, NR, NC, Energy, CKX, false, GROUP_ALL, LADDER>(a, en, c, gid, stale_total, x, ledger, total_q5, w, w_r, w_c, fac,
                                                          wave_accepted, bad_energy);
     bad_width |= !(w > R(0));
     // the state goes out first: a block of stores in front of measure_chain's loads costs nothing, and x dies as soon as the

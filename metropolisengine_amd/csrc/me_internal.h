@@ -65,6 +65,8 @@ struct StepLaunch {
   int stale_total;    // ME_FLAG_REFERENCE_ENERGY_LEDGERS: step_all of a mixed engine uses the extra ledger row only
   const void *cov;    // per-chain covariance field (magnitude-phase sampler reads its diagonal)
   double reject_bound, temp, ratio, target_acceptance, damping;
+  const void *ladder; // temperature ladder: (inv_temp, inv_temp_log2e) per rung in the device dtype; nullptr: scalar temp
+  int tiles_per_rung; // 64-chain tiles per rung (ladder only)
 };
 
 struct MeasureLaunch {
@@ -161,6 +163,12 @@ hipError_t launch_trace(const void *x, const void *energy, const void *width, lo
 hipError_t launch_detect_equilibration(const double *series, long long n_series, long long length, int fast, int nskip,
                                        double *scratch, long long *t0_out, double *g_out, double *neff_out,
                                        hipStream_t stream);
+// One replica-exchange round (me_replica.hip): rung k pairs with rung k+1 for every k = round (mod 2); slot j of the two
+// rungs swaps x and its energy-ledger rows with the Metropolis probability of the two temperatures.  ladder: the step
+// kernels' (inv_temp, inv_temp_log2e) table; pair_counts[2 k], [2 k + 1]: attempted / accepted swaps of the pair (k, k+1), added to.
+hipError_t launch_replica_swap(void *x, void *energy, long long n, int d, int n_terms, bool tiled_state, int dtype,
+                               const void *ladder, int n_rungs, unsigned long long round, unsigned long long chain_offset,
+                               unsigned long long seed, unsigned long long *pair_counts, hipStream_t stream);
 hipError_t launch_sum_slots(const unsigned long long *slots, long long n_slots, unsigned long long *total,
                             hipStream_t stream);
 

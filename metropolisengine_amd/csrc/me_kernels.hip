@@ -154,10 +154,12 @@ StepArgs<R> typed(const StepLaunch &l) {
   a.damping = (R)l.damping;
   a.up = (R)(l.ratio * (1.0 - l.target_acceptance) / l.damping);
   a.down = (R)(-l.ratio * l.target_acceptance / l.damping);
+  a.ladder = (const R *)l.ladder;
+  a.tiles_per_rung = l.tiles_per_rung;
   return a;
 }
 
-template <typename R, class Energy, bool INJECT, int GROUP>
+template <typename R, class Energy, bool INJECT, int GROUP, bool LADDER>
 hipError_t launch_step_cov(const StepLaunch &l, const StepArgs<R> &a, const Energy &en, dim3 grid, dim3 block,
                            hipStream_t stream) {
   switch (l.cov_kind) {
@@ -166,22 +168,22 @@ hipError_t launch_step_cov(const StepLaunch &l, const StepArgs<R> &a, const Ener
       // budget: 16 parameters at 2^22 chains, float32 (302 MB: a good part still hits) 107 us default / 114 us nt;
       // float64 (604 MB) 236 us default / 225 us nt.
       constexpr long long state_bytes = (long long)sizeof(R) * (D + 2);
-      if constexpr (!INJECT && GROUP == GROUP_ALL) {
+      if constexpr (!INJECT && GROUP == GROUP_ALL && !LADDER) {   // (ladders: the default policy, one instantiation fewer)
         if (state_bytes * l.n > 2 * cache_budget_bytes()) {
           hipLaunchKernelGGL((k_step<R, NR, NC, Energy, CK_IDENTITY, INJECT, GROUP, true>), grid, block, 0, stream, a, en);
           break;
         }
       }
-      hipLaunchKernelGGL((k_step<R, NR, NC, Energy, CK_IDENTITY, INJECT, GROUP>), grid, block, 0, stream, a, en);
+      hipLaunchKernelGGL((k_step<R, NR, NC, Energy, CK_IDENTITY, INJECT, GROUP, false, LADDER>), grid, block, 0, stream, a, en);
       break;
     }
-    case CK_SHARED: hipLaunchKernelGGL((k_step<R, NR, NC, Energy, CK_SHARED, INJECT, GROUP>), grid, block, 0, stream, a, en); break;
+    case CK_SHARED: hipLaunchKernelGGL((k_step<R, NR, NC, Energy, CK_SHARED, INJECT, GROUP, false, LADDER>), grid, block, 0, stream, a, en); break;
 #if ME_PER_CHAIN == 2
     case CK_PER_CHAIN: {
       // streamed factors (8-37 KB per chain and step) never stay in any cache: one variant, read non-temporally.  (The
       // stream is thousands of lines of straight-line code per instantiation; the replay hook does not get one.)
       if constexpr (INJECT) return hipErrorInvalidValue;
-      else hipLaunchKernelGGL((k_step<R, NR, NC, Energy, CK_PER_CHAIN_NT, INJECT, GROUP>), grid, block, 0, stream, a, en);
+      else hipLaunchKernelGGL((k_step<R, NR, NC, Energy, CK_PER_CHAIN_NT, INJECT, GROUP, false, LADDER>), grid, block, 0, stream, a, en);
       break;
     }
 #elif ME_PER_CHAIN
@@ -193,11 +195,11 @@ hipError_t launch_step_cov(const StepLaunch &l, const StepArgs<R> &a, const Ener
       constexpr long long per_chain_bytes = (long long)sizeof(R) * (D + 2 + NR * (NR + 1) / 2 + NC * NC);
       if constexpr (!INJECT) {
         if (per_chain_bytes * l.n > cache_budget_bytes()) {
-          hipLaunchKernelGGL((k_step<R, NR, NC, Energy, CK_PER_CHAIN_NT, INJECT, GROUP>), grid, block, 0, stream, a, en);
+          hipLaunchKernelGGL((k_step<R, NR, NC, Energy, CK_PER_CHAIN_NT, INJECT, GROUP, false, LADDER>), grid, block, 0, stream, a, en);
           break;
         }
       }
-      hipLaunchKernelGGL((k_step<R, NR, NC, Energy, CK_PER_CHAIN, INJECT, GROUP>), grid, block, 0, stream, a, en);
+      hipLaunchKernelGGL((k_step<R, NR, NC, Energy, CK_PER_CHAIN, INJECT, GROUP, false, LADDER>), grid, block, 0, stream, a, en);
       break;
     }
 #endif
@@ -206,13 +208,13 @@ hipError_t launch_step_cov(const StepLaunch &l, const StepArgs<R> &a, const Ener
   return hipGetLastError();
 }
 
-template <typename R, class Energy, bool INJECT>
+template <typename R, class Energy, bool INJECT, bool LADDER = false>
 hipError_t launch_step_group(const StepLaunch &l, const StepArgs<R> &a, const Energy &en, dim3 grid, dim3 block,
                              hipStream_t stream) {
-  if (l.group == GROUP_ALL) return launch_step_cov<R, Energy, INJECT, GROUP_ALL>(l, a, en, grid, block, stream);
+  if (l.group == GROUP_ALL) return launch_step_cov<R, Energy, INJECT, GROUP_ALL, LADDER>(l, a, en, grid, block, stream);
   if constexpr (NR > 0 && NC > 0) {   // group-wise stepping exists for mixed engines (pure engines alias step_all)
-    if (l.group == GROUP_REAL) return launch_step_cov<R, Energy, INJECT, GROUP_REAL>(l, a, en, grid, block, stream);
-    if (l.group == GROUP_COMPLEX) return launch_step_cov<R, Energy, INJECT, GROUP_COMPLEX>(l, a, en, grid, block, stream);
+    if (l.group == GROUP_REAL) return launch_step_cov<R, Energy, INJECT, GROUP_REAL, LADDER>(l, a, en, grid, block, stream);
+    if (l.group == GROUP_COMPLEX) return launch_step_cov<R, Energy, INJECT, GROUP_COMPLEX, LADDER>(l, a, en, grid, block, stream);
   }
   return hipErrorInvalidValue;
 }
@@ -225,6 +227,15 @@ hipError_t step_with(const StepLaunch &l, const Energy &en, hipStream_t stream) 
   const bool per_chain = l.cov_kind == CK_PER_CHAIN;
   const int threads = (l.n_sweeps >= kFusedSweepsThreshold || (ME_PER_CHAIN == 2 && per_chain)) ? kFusedStepThreads : kStepThreads;
   const dim3 grid(grid_for(l.n, l.grid_blocks, threads)), block(threads);
+  if (l.ladder) {
+    // a temperature ladder (me_set_temperature_ladder): the LADDER kernels; no replay hook, no matrix-core dense-64 form
+    if (l.inj_normals) return hipErrorNotSupported;
+#if ME_DENSE && !defined(ME_USER_SOURCE)
+    if constexpr (NR == 64 && NC == 0 && std::is_same<Energy, EnergyDense<R, 64, 0>>::value) return hipErrorNotSupported;
+    else
+#endif
+      return launch_step_group<R, Energy, false, true>(l, a, en, grid, block, stream);
+  }
   if (l.inj_normals) {
     // injected-stream replay: float64 only (it exists to check trajectories against the float64 reference)
     if constexpr (std::is_same<R, double>::value) return launch_step_group<R, Energy, true>(l, a, en, grid, block, stream);
@@ -276,10 +287,13 @@ hipError_t magphase_with(const StepLaunch &l, const Energy &en, hipStream_t stre
     a.factor = (const R *)l.cov;
     const dim3 grid(grid_for(l.n, l.grid_blocks)), block(kStepThreads);
     if (l.inj_normals) {
+      if (l.ladder) return hipErrorNotSupported;
       if constexpr (std::is_same<R, double>::value)
         hipLaunchKernelGGL((k_step_magphase<R, NR, NC, Energy, true>), grid, block, 0, stream, a, en);
       else
         return hipErrorNotSupported;
+    } else if (l.ladder) {
+      hipLaunchKernelGGL((k_step_magphase<R, NR, NC, Energy, false, true>), grid, block, 0, stream, a, en);
     } else {
       hipLaunchKernelGGL((k_step_magphase<R, NR, NC, Energy, false>), grid, block, 0, stream, a, en);
     }
@@ -432,7 +446,10 @@ hipError_t cycle(const StepLaunch &l, const MeasureLaunch &ml, hipStream_t strea
       const dim3 grid(grid_for(l.n, l.grid_blocks, threads)), block(threads);
       auto launch = [&](auto ck) {
         constexpr int CK = decltype(ck)::value;
-        if (ntm) hipLaunchKernelGGL((k_cycle<R, NR, NC, Energy, CK, true, true>), grid, block, 0, stream, a, ma, en);
+        // (a ladder: one cache policy, the non-temporal one when the launch's working set passes the cache)
+        if (l.ladder && nt) hipLaunchKernelGGL((k_cycle<R, NR, NC, Energy, CK, true, true, true>), grid, block, 0, stream, a, ma, en);
+        else if (l.ladder) hipLaunchKernelGGL((k_cycle<R, NR, NC, Energy, CK, false, false, true>), grid, block, 0, stream, a, ma, en);
+        else if (ntm) hipLaunchKernelGGL((k_cycle<R, NR, NC, Energy, CK, true, true>), grid, block, 0, stream, a, ma, en);
         else if (nt) hipLaunchKernelGGL((k_cycle<R, NR, NC, Energy, CK, true, false>), grid, block, 0, stream, a, ma, en);
         else hipLaunchKernelGGL((k_cycle<R, NR, NC, Energy, CK, false, false>), grid, block, 0, stream, a, ma, en);
       };

@@ -36,7 +36,7 @@ struct Trig<double> {
 };
 
 // a.factor carries the per-chain covariance field (ME_FIELD_COV), not the proposal factors.
-template <typename R, int NR, int NC, class Energy, bool INJECT = false>
+template <typename R, int NR, int NC, class Energy, bool INJECT = false, bool LADDER = false>
 __global__ void __launch_bounds__(kStepThreads) k_step_magphase(StepArgs<R> a, Energy en) {
   static_assert(NC > 0, "the magnitude-phase sampler acts on complex parameters");
   constexpr int D = NR + 2 * NC;
@@ -80,7 +80,8 @@ __global__ void __launch_bounds__(kStepThreads) k_step_magphase(StepArgs<R> a, E
       const R e_new = ledger.propose(en, xp, terms_new);
       const R diff = e_new - ledger.partial();
       bool accept = diff <= R(0);
-      if (a.temp > R(0)) accept = accept || N_::uphill(u, diff, a.inv_temp, a.inv_temp_log2e);
+      if constexpr (LADDER) accept = accept || uphill_at<true>(a, c, u, diff);
+      else if (a.temp > R(0)) accept = accept || N_::uphill(u, diff, a.inv_temp, a.inv_temp_log2e);
       accept = accept && !rejected;
       bad_energy |= (!rejected && !N_::finite(e_new));
 #pragma unroll

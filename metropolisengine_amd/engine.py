@@ -14,6 +14,9 @@ marshals arguments and unpacks results.  Differences from the reference, all for
  * keyword-only extras: ``n_chains``, ``seed``, ``dtype``, ``device``, ``chain_offset``, ``cov_mode``, ``trace_chains``,
    ``trace_stride``, ``track_covariance``, ``reference_energy_ledgers`` (reproduce the reference's two energy ledgers,
    SURVEY.md quirk Q5: ``step_all`` of a mixed engine uses ``energy_total``, group steps ``energy[term]``).
+ * ``temperatures=[T_0, ..., T_{K-1}]`` (keyword-only, with ``temp=0``): a temperature ladder -- K rungs of
+   ``n_chains / K`` consecutive chains, rung k stepping at ``T_k`` -- and :meth:`replica_exchange` swaps between adjacent
+   rungs (parallel tempering; no reference counterpart).
  * with ``n_chains == 1`` attributes have the reference's shapes and ``step_all()`` returns a bool; with more
    chains they gain a leading chain axis and ``step_all()`` returns ``None`` (it stays asynchronous).
  * randomness is a seeded counter-based Philox stream per global chain id instead of numpy's global state.
@@ -70,6 +73,22 @@ def unpack_real_factor(packed, nr):
     return out
 
 
+def validate_ladder(temperatures, n_chains):
+    """A temperature ladder as a float64 array: ``T_0 < T_1 < ... < T_{K-1}``, finite and > 0, and ``n_chains`` a multiple
+    of ``64 K`` (every rung is a run of whole 64-chain tiles).  Raises ``ValueError``."""
+    temps = np.asarray(temperatures, dtype=np.float64)
+    if temps.ndim != 1 or temps.size < 1:
+        raise ValueError("temperatures must be a non-empty 1-D sequence")
+    if not np.all(np.isfinite(temps)) or not np.all(temps > 0):
+        raise ValueError("ladder temperatures must be finite and > 0")
+    if not np.all(np.diff(temps) > 0):
+        raise ValueError("ladder temperatures must be strictly increasing")
+    if int(n_chains) % (64 * temps.size) != 0:
+        raise ValueError("n_chains (%d) must be a multiple of 64 * %d rungs: every rung is a run of whole 64-chain tiles"
+                         % (int(n_chains), temps.size))
+    return temps
+
+
 def set_cache_budget(n_bytes):
     """Process-wide tuning knob (``me_set_cache_budget``): launches whose working set exceeds ``n_bytes`` stream their
     read-once / write-once fields with the non-temporal cache policy.  Default 224 MiB."""
@@ -82,10 +101,15 @@ class MetropolisEngine:
                  covariance_matrix_complex=None, params_names=None, target_acceptance=.3, temp=0,
                  complex_sample_method="multivariate-gaussian", *, n_chains=1, seed=0, dtype="f32", device=0,
                  chain_offset=0, cov_mode="reference", trace_chains=None, trace_stride=1, track_covariance=False,
-                 reference_energy_ledgers=False):
+                 reference_energy_ledgers=False, temperatures=None):
         if initial_real_params is None and initial_complex_params is None:
             print("must give list containing  at least one value for initial real or complex parameters")
             raise ValueError("no initial parameters")                                    # metropolis_engine.py:37-39
+        if temperatures is not None:
+            # checked before anything is built or traced: a ladder replaces the scalar temp
+            if temp is None or temp != 0:
+                raise ValueError("give either temp or temperatures: a ladder engine steps every rung at its own temperature")
+            temperatures = validate_ladder(temperatures, n_chains)
         if not isinstance(energy_functions, EnergySpec):
             # the reference's own form: a Python callable (real_params, complex_params) -> float, or its dictionary of
             # term callables (metropolis_engine.py:20, :111-116).  It is TRACED once on symbolic parameters, written out as
@@ -226,6 +250,8 @@ class MetropolisEngine:
         self.trace_stride = int(trace_stride)
         if self.trace_chains:
             _capi.check(self._lib.me_trace_enable(handle, self.trace_chains, self.trace_stride), handle)
+        if temperatures is not None:
+            self.set_temperatures(temperatures)
 
     # ------------------------------------------------------------------ lifetime
     def close(self):
@@ -504,6 +530,76 @@ class MetropolisEngine:
         self._check(self._lib.me_pooled_moments_end(self._handle, _as_double_ptr(out), size.value))
         return out
 
+    # ------------------------------------------------------------------ temperature ladders and replica exchange
+    @property
+    def temperatures(self):
+        """The ladder ``T_0 < ... < T_{K-1}`` as a ``(K,)`` array, or ``None`` (every chain at ``temp``)."""
+        k = ctypes.c_int32()
+        self._check(self._lib.me_temperature_ladder(self._handle, None, 0, ctypes.byref(k)))
+        if k.value == 0:
+            return None
+        out = np.empty(k.value, dtype=np.float64)
+        self._check(self._lib.me_temperature_ladder(self._handle, _as_double_ptr(out), k.value, ctypes.byref(k)))
+        return out
+
+    def set_temperatures(self, temperatures):
+        """Install a ladder (``me_set_temperature_ladder``): the chains become ``K`` rungs of ``n_chains / K`` consecutive
+        chains, rung ``k`` stepping at ``temperatures[k]``; the swap round and counters start over.  ``None`` returns the
+        engine to its scalar ``temp``.  ``NotImplementedError`` on engines that cannot carry a ladder (runtime dimensions,
+        the dense 64-parameter matrix-core form, ``reference_energy_ledgers=True``)."""
+        if temperatures is None:
+            self._check(self._lib.me_set_temperature_ladder(self._handle, None, 0))
+            return
+        if self.temp != 0:
+            raise ValueError("this engine has a scalar temp; a ladder engine is created with temp=0")
+        temps = np.ascontiguousarray(validate_ladder(temperatures, self.n_chains))
+        self._check(self._lib.me_set_temperature_ladder(self._handle, _as_double_ptr(temps), temps.size))
+
+    def replica_exchange(self, n_rounds=1):
+        """Enqueue ``n_rounds`` replica-exchange rounds (asynchronous, like :meth:`step_all`): round ``r`` offers slot ``j``
+        of rung ``k`` and slot ``j`` of rung ``k+1`` a swap of their configurations for every ``k = r (mod 2)``."""
+        self._check(self._lib.me_replica_exchange(self._handle, int(n_rounds)))
+
+    def swap_stats(self):
+        """``(round, attempted, accepted)``: the next round's number and the swaps per adjacent pair of rungs, ``(K-1,)``."""
+        temps = self.temperatures
+        if temps is None:
+            raise ValueError("this engine has no temperature ladder")
+        n_pairs = temps.size - 1
+        rnd = ctypes.c_uint64()
+        att = (ctypes.c_uint64 * max(n_pairs, 1))()
+        acc = (ctypes.c_uint64 * max(n_pairs, 1))()
+        self._check(self._lib.me_replica_stats(self._handle, ctypes.byref(rnd), att, acc, n_pairs))
+        return (rnd.value, np.array(att[:n_pairs], dtype=np.int64), np.array(acc[:n_pairs], dtype=np.int64))
+
+    def swap_acceptance(self):
+        """Accepted / attempted swaps per adjacent pair of rungs, ``(K-1,)`` (NaN before the pair's first attempt)."""
+        _, att, acc = self.swap_stats()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(att > 0, acc / np.maximum(att, 1), np.nan)
+
+    def chain_temperatures(self):
+        """The temperature each local chain steps at, ``(n_chains,)``."""
+        temps = self.temperatures
+        if temps is None:
+            return np.full(self.n_chains, float(self.temp))
+        return np.repeat(temps, self.n_chains // temps.size)
+
+    def pooled_moments_by_rung(self):
+        """:meth:`pooled_moments` of every rung, ``(K, moments_size)`` (``me_pooled_moments_range``); the two trailing
+        counters of a rung are 0 (acceptance is counted per launch wavefront, not per chain).  Without a ladder: one row,
+        the whole engine."""
+        temps = self.temperatures
+        if temps is None:
+            return self.pooled_moments()[None, :]
+        size = ctypes.c_int64()
+        self._check(self._lib.me_pooled_moments_size(self._handle, ctypes.byref(size)))
+        m = self.n_chains // temps.size
+        out = np.empty((temps.size, size.value), dtype=np.float64)
+        for k in range(temps.size):
+            self._check(self._lib.me_pooled_moments_range(self._handle, k * m, m, _as_double_ptr(out[k]), size.value))
+        return out
+
     # -- RCCL behind the C ABI (me_comm_*): the all-reduce of the moments runs on the engine's own streams, no PyTorch
     @staticmethod
     def comm_unique_id():
@@ -589,6 +685,10 @@ class MetropolisEngine:
         shared = self.shared_factor()
         if shared is not None:                       # cov_mode="pooled": the proposal shape every chain shares
             state["shared_factor"] = shared
+        temps = self.temperatures
+        if temps is not None:                        # a ladder engine: the ladder and the replica-exchange position
+            state["temperatures"] = temps
+            state["replica_round"], state["swap_attempted"], state["swap_accepted"] = self.swap_stats()
         return state
 
     def load_state_dict(self, state):
@@ -617,6 +717,21 @@ class MetropolisEngine:
                 raise ValueError("checkpoint shared_factor has the wrong length")
         if "accepted" in state and "proposed" in state and int(state["accepted"]) > int(state["proposed"]):
             raise ValueError("checkpoint accept counters are inconsistent")
+        ladder = None
+        if "temperatures" in state:
+            if self.temp != 0:
+                raise ValueError("the checkpoint carries a temperature ladder: this engine has a scalar temp")
+            ladder = validate_ladder(state["temperatures"], self.n_chains)
+            if "replica_round" not in state or "swap_attempted" not in state or "swap_accepted" not in state:
+                raise ValueError("checkpoint lacks the replica-exchange round / swap counters of its ladder")
+            att = np.asarray(state["swap_attempted"], dtype=np.int64)
+            acc = np.asarray(state["swap_accepted"], dtype=np.int64)
+            if att.shape != (ladder.size - 1,) or acc.shape != (ladder.size - 1,):
+                raise ValueError("checkpoint swap counters must have one entry per adjacent pair of rungs")
+            if np.any(acc < 0) or np.any(acc > att) or int(state["replica_round"]) < 0:
+                raise ValueError("checkpoint swap counters are inconsistent")
+            # (first, so that an engine that cannot carry a ladder refuses before anything else is written)
+            self.set_temperatures(ladder)
         for field, values in todo:
             self._set(field, values)
         self._check(self._lib.me_set_counters(self._handle, int(state["step_index"]),
@@ -625,6 +740,11 @@ class MetropolisEngine:
             self.set_shared_factor(state["shared_factor"])
         if "accepted" in state and "proposed" in state:
             self._check(self._lib.me_set_accept_stats(self._handle, int(state["accepted"]), int(state["proposed"])))
+        if ladder is not None:
+            n_pairs = ladder.size - 1
+            att = (ctypes.c_uint64 * max(n_pairs, 1))(*[int(v) for v in state["swap_attempted"]])
+            acc = (ctypes.c_uint64 * max(n_pairs, 1))(*[int(v) for v in state["swap_accepted"]])
+            self._check(self._lib.me_set_replica_stats(self._handle, int(state["replica_round"]), att, acc, n_pairs))
 
     # ------------------------------------------------------------------ time series (:31-35, :350-356, :466-479)
     def trace(self):
