@@ -16,6 +16,8 @@
  *   me_accept_stats      <- the bool returned by step_all (:259), accumulated
  *   me_pooled_moments*   <- no reference equivalent (ensemble estimate across chains)
  *   me_set_temperature_ladder, me_replica_*  <- no reference equivalent (parallel tempering across the chains)
+ *   me_set_temperature   <- the constructor's temp (:92), changed on a running engine (simulated annealing)
+ *   me_population_*      <- no reference equivalent (population annealing: Boltzmann resampling, free energies)
  *   me_comm_*, me_pooled_moments_allreduce*  <- no reference equivalent (the one collective: RCCL all-reduce of the moments)
  *   me_last_error        <- Python exceptions (:39 ValueError, :92/:438 AssertionError, numpy ValueError :270)
  *
@@ -299,6 +301,39 @@ int me_replica_stats(me_engine *engine, uint64_t *round, uint64_t *attempted, ui
 int me_set_replica_stats(me_engine *engine, uint64_t round, const uint64_t *attempted, const uint64_t *accepted,
                          int32_t n_pairs);
 int me_pooled_moments_range(me_engine *engine, int64_t chain_begin, int64_t n_chains, double *host_out, int64_t n_doubles);
+
+/* Scalar temperature and population annealing (no reference counterpart).
+ *   me_set_temperature         the scalar temp of a running engine, finite and >= 0; the next step uses it (plain simulated
+ *                       annealing).  ME_ERR_STATE on a ladder engine.
+ *   me_population_resample     enqueue one population-annealing stage from T_old = temp > 0 to new_temp (finite, > 0) on the
+ *                       engine's stream (asynchronous, like me_step).  E_i = the sum of chain i's ledger rows in row order in
+ *                       the device dtype, l_i = -(1/new_temp - 1/T_old) E_i in float64 (weight 0 when not finite), M = max l_i,
+ *                       w_i = exp(l_i - M), W = sum w_i, S2 = sum w_i^2 (fixed summation order: bitwise reproducible).  The
+ *                       stage records log_weight = M + ln(W / N), the estimate of ln Z(new_temp) / Z(T_old), neff_fraction =
+ *                       W^2 / (N S2) and n_finite, then resamples systematically with one uniform u = word 0 of Philox block
+ *                       0xfffe at counter (chain_offset, stage index): slot j takes chain a_j = min{ i : N C_i / W > j + u },
+ *                       C_i = w_0 + ... + w_i (slots left undefined by rounding take the last chain of positive weight).  Slot
+ *                       j receives chain a_j's configuration (ME_FIELD_PARAMS and every ME_FIELD_ENERGY row) and its family
+ *                       id; widths, running means, covariances, factors, traces and counters stay with the slot, exactly as
+ *                       in a replica-exchange swap.  Then temp = new_temp.  n_finite = 0 leaves the population unchanged and
+ *                       records log_weight = -inf, neff_fraction = 0; new_temp = temp is the identity (log_weight = 0).
+ *                       ME_ERR_STATE on a ladder engine or with temp = 0; ME_ERR_UNSUPPORTED with
+ *                       ME_FLAG_REFERENCE_ENERGY_LEDGERS.  Each engine (GPU shard) is an independent population: the shards'
+ *                       stages combine as ln mean_w = logsumexp_s(log_weight_s + ln N_s) - ln sum_s N_s.
+ *   me_population_stats        the stage count and, per stage, its new temperature, log_weight, neff_fraction and n_finite
+ *                       (waits for the stream).  Any pointer may be NULL; the arrays given must hold `stages` entries
+ *                       (capacity).  me_set_population_stats restores them from a checkpoint.
+ *   me_population_families     family ids of chains [chain_begin, chain_begin + n): int64, the global chain id of each
+ *                       slot's founder (chain_offset + j before the first stage; non-decreasing in j on every engine that
+ *                       was only resampled).  me_set_population_families restores them. */
+int me_set_temperature(me_engine *engine, double temp);
+int me_population_resample(me_engine *engine, double new_temp);
+int me_population_stats(me_engine *engine, uint64_t *stages, double *stage_temps, double *log_weight, double *neff_fraction,
+                        int64_t *n_finite, int64_t capacity);
+int me_set_population_stats(me_engine *engine, uint64_t stages, const double *stage_temps, const double *log_weight,
+                            const double *neff_fraction, const int64_t *n_finite);
+int me_population_families(me_engine *engine, int64_t chain_begin, int64_t n, int64_t *dst);
+int me_set_population_families(me_engine *engine, int64_t chain_begin, int64_t n, const int64_t *src);
 
 /* Text of the last error on this engine (or of the last failed me_create when engine is NULL). */
 int me_last_error(me_engine *engine, char *buf, size_t buf_bytes);

@@ -100,6 +100,13 @@ SYMBOLS = {
     "me_set_replica_stats": (ctypes.c_int, [_H, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64),
                                             ctypes.POINTER(ctypes.c_uint64), ctypes.c_int32]),
     "me_pooled_moments_range": (ctypes.c_int, [_H, ctypes.c_int64, ctypes.c_int64, _dp, ctypes.c_int64]),
+    "me_set_temperature": (ctypes.c_int, [_H, ctypes.c_double]),
+    "me_population_resample": (ctypes.c_int, [_H, ctypes.c_double]),
+    "me_population_stats": (ctypes.c_int, [_H, ctypes.POINTER(ctypes.c_uint64), _dp, _dp, _dp, ctypes.POINTER(ctypes.c_int64),
+                                           ctypes.c_int64]),
+    "me_set_population_stats": (ctypes.c_int, [_H, ctypes.c_uint64, _dp, _dp, _dp, ctypes.POINTER(ctypes.c_int64)]),
+    "me_population_families": (ctypes.c_int, [_H, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
+    "me_set_population_families": (ctypes.c_int, [_H, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
 }
 
 

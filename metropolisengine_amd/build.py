@@ -101,6 +101,9 @@ def build(force=False, jobs=None, verbose=True):
                            "-DME_ONLY_DTYPE=%d" % bits]))
     for name in ("me_generic", "me_statistics", "me_runtime_dims", "me_replica", "me_api"):
         units.append((os.path.join(OBJ_DIR, name + ".o"), os.path.join(CSRC, name + ".hip"), []))
+    # population annealing: the weights, sums and slot boundaries must round exactly as written (no fused multiply-adds),
+    # so that the scan pass reproduces the weight pass's sums bit for bit and tests/population_reference.py can restate them
+    units.append((os.path.join(OBJ_DIR, "me_population.o"), os.path.join(CSRC, "me_population.hip"), ["-ffp-contract=off"]))
 
     todo = []
     for obj, src, flags in units:

@@ -187,6 +187,15 @@ struct me_engine {
   unsigned long long replica_round = 0;
   void *range_x = nullptr;                       // me_pooled_moments_range: the range's rows of a component-major x
   size_t range_bytes = 0;
+  // population annealing (me_population_resample, me_population.hip); allocated at the first stage or family restore
+  long long *pop_fam = nullptr, *pop_fam_out = nullptr;   // family ids (start as the global chain ids), gather scratch
+  void *pop_x = nullptr, *pop_energy = nullptr;           // gather scratch of x and the ledger
+  size_t pop_x_bytes = 0, pop_energy_bytes = 0;
+  unsigned int *pop_anc = nullptr;                        // ancestor of every slot
+  double *pop_scratch = nullptr;                          // block partials, factors, offsets, stage parameters
+  double *pop_records = nullptr;                          // (log_weight, neff_fraction, n_finite) per stage
+  unsigned long long pop_stages = 0, pop_capacity = 0;
+  std::vector<double> pop_temps;                          // T_new of every stage
   std::string err;
 };
 
@@ -370,7 +379,8 @@ void release(me_engine *e) {
   (void)hipSetDevice(e->device);
   void *bufs[] = {e->x, e->energy, e->width, e->mean, e->cov, e->obs_mean, e->factor, e->shared_factor, e->shared_full, e->shared_image, e->energy_image,
                   e->coef_dev, e->row_dev, e->accept_slots, e->accept_total, e->status, e->pool_dev, e->pool_partials, e->trace_dev,
-                  e->ladder, e->pair_counts, e->range_x};
+                  e->ladder, e->pair_counts, e->range_x, e->pop_fam, e->pop_fam_out, e->pop_x, e->pop_energy, e->pop_anc,
+                  e->pop_scratch, e->pop_records};
   for (void *b : bufs)
     if (b) (void)hipFree(b);
   if (e->comm && e->rccl) (void)e->rccl->comm_destroy(e->comm);
@@ -1623,6 +1633,179 @@ int me_pooled_moments_range(me_engine *e, int64_t chain_begin, int64_t n_chains,
   ME_HIP(e, hipMemcpyAsync(e->pool_host, e->pool_dev, sizeof(double) * (size_t)n_doubles, hipMemcpyDeviceToHost, e->stream));
   ME_HIP(e, wait_polling(e->stream));
   std::memcpy(host_out, e->pool_host, sizeof(double) * (size_t)n_doubles);
+  return ME_OK;
+}
+
+// ---- scalar temperature and population annealing (me_population.hip) --------------------------------------------------
+namespace {
+int ensure_families(me_engine *e) {
+  if (e->pop_fam) return ME_OK;
+  ME_HIP(e, hipMalloc((void **)&e->pop_fam, (size_t)e->n * sizeof(long long)));
+  ME_HIP(e, launch_population_init_families(e->pop_fam, e->n, e->chain_offset, e->stream));
+  return ME_OK;
+}
+// everything a stage writes besides x, the ledger and the families; the ledger scratch follows me_set_energy's row count
+int ensure_population_scratch(me_engine *e) {
+  const size_t energy_bytes = (size_t)e->n * (size_t)e->n_terms * e->esize;
+  if (e->pop_energy && e->pop_energy_bytes < energy_bytes) {
+    ME_HIP(e, hipStreamSynchronize(e->stream));
+    (void)hipFree(e->pop_energy);
+    e->pop_energy = nullptr;
+  }
+  if (!e->pop_energy) {
+    ME_HIP(e, hipMalloc(&e->pop_energy, energy_bytes));
+    e->pop_energy_bytes = energy_bytes;
+  }
+  if (!e->pop_x) {
+    // same extent as x (tile-major: whole 64-chain tiles); it starts as a copy so that the padding lanes of a partial tile,
+    // which no gather writes, never carry uninitialised memory back into x
+    e->pop_x_bytes = (size_t)(e->x_tiled ? (e->n + 63) / 64 * 64 : e->n) * (size_t)e->d * e->esize;
+    ME_HIP(e, hipMalloc(&e->pop_x, e->pop_x_bytes));
+    ME_HIP(e, hipMemcpyAsync(e->pop_x, e->x, e->pop_x_bytes, hipMemcpyDeviceToDevice, e->stream));
+  }
+  if (!e->pop_fam_out) ME_HIP(e, hipMalloc((void **)&e->pop_fam_out, (size_t)e->n * sizeof(long long)));
+  if (!e->pop_anc) ME_HIP(e, hipMalloc((void **)&e->pop_anc, (size_t)e->n * sizeof(unsigned int)));
+  if (!e->pop_scratch) ME_HIP(e, hipMalloc((void **)&e->pop_scratch, population_scratch_doubles(e->n) * sizeof(double)));
+  return ME_OK;
+}
+// room for `stages` stage records on the device (grown by doubling; a growth waits for the stream once)
+int ensure_records(me_engine *e, unsigned long long stages) {
+  if (stages <= e->pop_capacity) return ME_OK;
+  unsigned long long cap = std::max<unsigned long long>(256, e->pop_capacity);
+  while (cap < stages) cap *= 2;
+  double *grown = nullptr;
+  ME_HIP(e, hipMalloc((void **)&grown, (size_t)cap * 3 * sizeof(double)));
+  if (e->pop_records) {
+    ME_HIP(e, hipMemcpyAsync(grown, e->pop_records, (size_t)e->pop_stages * 3 * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+    ME_HIP(e, hipStreamSynchronize(e->stream));
+    (void)hipFree(e->pop_records);
+  }
+  e->pop_records = grown;
+  e->pop_capacity = cap;
+  return ME_OK;
+}
+int check_family_range(me_engine *e, int64_t chain_begin, int64_t n) {
+  if (chain_begin < 0 || n < 0 || chain_begin + n > e->n) return fail(e, ME_ERR_INVALID, "family range outside the engine's chains");
+  return ME_OK;
+}
+}  // namespace
+
+int me_set_temperature(me_engine *e, double temp) {
+  if (!e) return ME_ERR_INVALID;
+  if (!(std::isfinite(temp) && temp >= 0)) return fail(e, ME_ERR_INVALID, "temp must be finite and >= 0");
+  if (e->n_rungs) return fail(e, ME_ERR_STATE, "this engine has a temperature ladder: its rungs carry the temperatures");
+  e->temp = temp;          // the next launch reads it (fill_step_launch)
+  return ME_OK;
+}
+
+int me_population_resample(me_engine *e, double new_temp) {
+  if (!e) return ME_ERR_INVALID;
+  if (!(std::isfinite(new_temp) && new_temp > 0)) return fail(e, ME_ERR_INVALID, "the new temperature must be finite and > 0");
+  if (e->stale_total)
+    return fail(e, ME_ERR_UNSUPPORTED, "population annealing is not available with ME_FLAG_REFERENCE_ENERGY_LEDGERS: its two "
+                                       "ledgers make the energy of a chain ambiguous");
+  if (e->n_rungs) return fail(e, ME_ERR_STATE, "population annealing needs the scalar temp: this engine has a temperature ladder");
+  if (!(e->temp > 0)) return fail(e, ME_ERR_STATE, "population annealing cannot reweight from temp = 0: set a temperature first");
+  ME_HIP(e, hipSetDevice(e->device));
+  int rc;
+  if ((rc = ensure_families(e)) || (rc = ensure_population_scratch(e)) || (rc = ensure_records(e, e->pop_stages + 1))) return rc;
+  PopulationLaunch L;
+  L.x = e->x;
+  L.energy = e->energy;
+  L.x_out = e->pop_x;
+  L.energy_out = e->pop_energy;
+  L.families = e->pop_fam;
+  L.families_out = e->pop_fam_out;
+  L.ancestors = e->pop_anc;
+  L.scratch = e->pop_scratch;
+  L.record = e->pop_records + 3 * (size_t)e->pop_stages;
+  L.n = e->n;
+  L.d = e->d;
+  L.n_terms = e->n_terms;
+  L.tiled = e->x_tiled;
+  L.neg_dbeta = -(1.0 / new_temp - 1.0 / e->temp);
+  L.chain_offset = e->chain_offset;
+  L.stage = e->pop_stages;
+  L.seed = e->seed;
+  ME_HIP(e, launch_population_resample(L, e->dtype, e->stream));
+  // the scratch goes back into the engine's own buffers: their addresses stay what a captured graph recorded
+  ME_HIP(e, hipMemcpyAsync(e->x, e->pop_x, e->pop_x_bytes, hipMemcpyDeviceToDevice, e->stream));
+  ME_HIP(e, hipMemcpyAsync(e->energy, e->pop_energy, (size_t)e->n * (size_t)e->n_terms * e->esize, hipMemcpyDeviceToDevice, e->stream));
+  ME_HIP(e, hipMemcpyAsync(e->pop_fam, e->pop_fam_out, (size_t)e->n * sizeof(long long), hipMemcpyDeviceToDevice, e->stream));
+  e->temp = new_temp;
+  e->pop_temps.push_back(new_temp);
+  e->pop_stages += 1;
+  return ME_OK;
+}
+
+int me_population_stats(me_engine *e, uint64_t *stages, double *stage_temps, double *log_weight, double *neff_fraction,
+                        int64_t *n_finite, int64_t capacity) {
+  if (!e) return ME_ERR_INVALID;
+  if (stages) *stages = e->pop_stages;
+  if (!stage_temps && !log_weight && !neff_fraction && !n_finite) return ME_OK;
+  if (capacity < 0 || (unsigned long long)capacity < e->pop_stages)
+    return fail(e, ME_ERR_INVALID, "the arrays must hold one entry per stage");
+  if (e->pop_stages == 0) return ME_OK;
+  ME_HIP(e, hipSetDevice(e->device));
+  std::vector<double> rec(3 * (size_t)e->pop_stages);
+  ME_HIP(e, hipMemcpyAsync(rec.data(), e->pop_records, rec.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+  ME_HIP(e, hipStreamSynchronize(e->stream));
+  for (size_t k = 0; k < e->pop_stages; ++k) {
+    if (stage_temps) stage_temps[k] = e->pop_temps[k];
+    if (log_weight) log_weight[k] = rec[3 * k];
+    if (neff_fraction) neff_fraction[k] = rec[3 * k + 1];
+    if (n_finite) n_finite[k] = (int64_t)rec[3 * k + 2];
+  }
+  return ME_OK;
+}
+
+int me_set_population_stats(me_engine *e, uint64_t stages, const double *stage_temps, const double *log_weight,
+                            const double *neff_fraction, const int64_t *n_finite) {
+  if (!e) return ME_ERR_INVALID;
+  if (stages > 0 && (!stage_temps || !log_weight || !neff_fraction || !n_finite))
+    return fail(e, ME_ERR_INVALID, "stage_temps / log_weight / neff_fraction / n_finite missing");
+  std::vector<double> rec(3 * (size_t)stages);
+  for (uint64_t k = 0; k < stages; ++k) {
+    if (!(std::isfinite(stage_temps[k]) && stage_temps[k] > 0)) return fail(e, ME_ERR_INVALID, "stage temperatures must be finite and > 0");
+    if (n_finite[k] < 0 || n_finite[k] > e->n) return fail(e, ME_ERR_INVALID, "n_finite must lie in [0, n_chains]");
+    rec[3 * k] = log_weight[k];
+    rec[3 * k + 1] = neff_fraction[k];
+    rec[3 * k + 2] = (double)n_finite[k];
+  }
+  ME_HIP(e, hipSetDevice(e->device));
+  int rc = ensure_records(e, std::max<uint64_t>(stages, 1));
+  if (rc) return rc;
+  if (stages > 0) {
+    ME_HIP(e, hipMemcpyAsync(e->pop_records, rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    ME_HIP(e, hipStreamSynchronize(e->stream));
+  }
+  e->pop_temps.assign(stage_temps, stage_temps + stages);
+  e->pop_stages = stages;
+  return ME_OK;
+}
+
+int me_population_families(me_engine *e, int64_t chain_begin, int64_t n, int64_t *dst) {
+  if (!e || (!dst && n > 0)) return ME_ERR_INVALID;
+  int rc = check_family_range(e, chain_begin, n);
+  if (rc || n == 0) return rc;
+  if (!e->pop_fam) {                  // never resampled: every chain is its own family, the global chain id
+    for (int64_t k = 0; k < n; ++k) dst[k] = (int64_t)(e->chain_offset + (unsigned long long)(chain_begin + k));
+    return ME_OK;
+  }
+  ME_HIP(e, hipSetDevice(e->device));
+  ME_HIP(e, hipMemcpyAsync(dst, e->pop_fam + chain_begin, (size_t)n * sizeof(long long), hipMemcpyDeviceToHost, e->stream));
+  ME_HIP(e, hipStreamSynchronize(e->stream));
+  return ME_OK;
+}
+
+int me_set_population_families(me_engine *e, int64_t chain_begin, int64_t n, const int64_t *src) {
+  if (!e || (!src && n > 0)) return ME_ERR_INVALID;
+  int rc = check_family_range(e, chain_begin, n);
+  if (rc || n == 0) return rc;
+  ME_HIP(e, hipSetDevice(e->device));
+  if ((rc = ensure_families(e))) return rc;
+  ME_HIP(e, hipMemcpyAsync(e->pop_fam + chain_begin, src, (size_t)n * sizeof(long long), hipMemcpyHostToDevice, e->stream));
+  ME_HIP(e, hipStreamSynchronize(e->stream));
   return ME_OK;
 }
 

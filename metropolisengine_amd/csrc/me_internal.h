@@ -171,6 +171,26 @@ hipError_t launch_replica_swap(void *x, void *energy, long long n, int d, int n_
                                unsigned long long seed, unsigned long long *pair_counts, hipStream_t stream);
 hipError_t launch_sum_slots(const unsigned long long *slots, long long n_slots, unsigned long long *total,
                             hipStream_t stream);
+// One population-annealing stage (me_population.hip): weights, scan, ancestors, and the gather of x, the ledger rows and
+// the family ids of the ancestors into x_out / energy_out / families_out (the caller copies them back).
+struct PopulationLaunch {
+  const void *x, *energy;
+  void *x_out, *energy_out;
+  const long long *families;
+  long long *families_out;
+  unsigned int *ancestors;          // n entries
+  double *scratch;                  // population_scratch_doubles(n)
+  double *record;                   // this stage's (log_weight, neff_fraction, n_finite)
+  long long n;
+  int d, n_terms;
+  bool tiled;                       // tile-major x (KernelSet::tiled_state)
+  double neg_dbeta;                 // -(1/T_new - 1/T_old)
+  unsigned long long chain_offset, stage, seed;
+};
+size_t population_scratch_doubles(long long n);
+hipError_t launch_population_resample(const PopulationLaunch &launch, int dtype, hipStream_t stream);
+hipError_t launch_population_init_families(long long *families, long long n, unsigned long long chain_offset,
+                                           hipStream_t stream);
 
 // blocks launched for n chains (one lane per chain, grid-stride beyond `requested` blocks when requested > 0)
 inline int grid_for(long long n, int requested, int threads = kStepThreads) {

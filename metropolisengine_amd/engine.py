@@ -17,6 +17,9 @@ marshals arguments and unpacks results.  Differences from the reference, all for
  * ``temperatures=[T_0, ..., T_{K-1}]`` (keyword-only, with ``temp=0``): a temperature ladder -- K rungs of
    ``n_chains / K`` consecutive chains, rung k stepping at ``T_k`` -- and :meth:`replica_exchange` swaps between adjacent
    rungs (parallel tempering; no reference counterpart).
+ * :meth:`set_temp` changes the scalar temperature of a running engine (simulated annealing); :meth:`resample` /
+   :meth:`anneal` run population annealing -- Boltzmann resampling of the chains between temperatures, with the free-energy
+   estimate ``ln Z(T_new) / Z(T_old)`` of every stage in :meth:`population_stats` (no reference counterpart).
  * with ``n_chains == 1`` attributes have the reference's shapes and ``step_all()`` returns a bool; with more
    chains they gain a leading chain axis and ``step_all()`` returns ``None`` (it stays asynchronous).
  * randomness is a seeded counter-based Philox stream per global chain id instead of numpy's global state.
@@ -154,6 +157,8 @@ class MetropolisEngine:
         self.seed = int(seed)
         self.chain_offset = int(chain_offset)
         self.temp = temp
+        self._population_used = False    # set_temp / resample were used: checkpoints then carry temp, stages and families
+        self._initial_temp = temp        # what a checkpoint without "temp" describes
         self.target_acceptance = target_acceptance
         self._initial_widths = initial_widths     # what the width of an absent group stays at
         # "magnitude-phase" swaps step_complex_group only; step_all keeps the Gaussian sampler (:129-130, quirk Q9)
@@ -600,6 +605,91 @@ class MetropolisEngine:
             self._check(self._lib.me_pooled_moments_range(self._handle, k * m, m, _as_double_ptr(out[k]), size.value))
         return out
 
+    # ------------------------------------------------------------------ scalar temperature and population annealing
+    def set_temp(self, temp):
+        """Change the scalar temperature of the running engine (``me_set_temperature``); the next step uses it, so a schedule
+        of ``set_temp`` + :meth:`step_all` is plain simulated annealing.  ``temp`` finite and ``>= 0`` (``ValueError``
+        otherwise, and on a ladder engine, whose rungs carry the temperatures)."""
+        temp = float(temp)
+        if not (np.isfinite(temp) and temp >= 0):
+            raise ValueError("temp must be finite and >= 0")
+        if self.temperatures is not None:
+            raise ValueError("this engine has a temperature ladder: set_temperatures changes it")
+        self._check(self._lib.me_set_temperature(self._handle, temp))
+        self.temp = temp
+        self._population_used = True
+
+    def resample(self, temp):
+        """One population-annealing stage (``me_population_resample``, asynchronous): reweight every chain by
+        ``exp(-(1/temp - 1/self.temp) E)``, record the stage's estimate of ``ln Z(temp) / Z(self.temp)``, resample the
+        population systematically in proportion to the weights and continue at ``temp``.  A slot receives its ancestor's
+        configuration (parameters, energy ledger) and family id; everything adapted or measured (widths, running means,
+        covariances, factors, traces, counters) stays with the slot.  ``ValueError`` for a ``temp`` that is not finite and
+        > 0, on a ladder engine and from ``temp == 0``; ``NotImplementedError`` with ``reference_energy_ledgers=True``."""
+        temp = float(temp)
+        if not (np.isfinite(temp) and temp > 0):
+            raise ValueError("the new temperature must be finite and > 0")
+        if self.temperatures is not None:
+            raise ValueError("population annealing needs the scalar temp: this engine has a temperature ladder")
+        if not self.temp > 0:
+            raise ValueError("population annealing cannot reweight from temp = 0: set_temp first")
+        self._check(self._lib.me_population_resample(self._handle, temp))
+        self.temp = temp
+        self._population_used = True
+
+    def _reset_population(self):
+        """Back to the state before any set_temp / resample: the constructor's temp, no stages, families = global ids."""
+        self._check(self._lib.me_set_temperature(self._handle, float(self._initial_temp)))
+        self.temp = self._initial_temp
+        self._check(self._lib.me_set_population_stats(self._handle, 0, None, None, None, None))
+        ids = np.arange(self.n_chains, dtype=np.int64) + np.int64(self.chain_offset)
+        self._check(self._lib.me_set_population_families(self._handle, 0, self.n_chains,
+                                                         ids.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        self._population_used = False
+
+    def anneal(self, temps, n_sweeps=1):
+        """For each ``T`` of ``temps`` in turn: :meth:`resample` to ``T``, then ``step_all(n_sweeps)``.
+
+        The proposal widths are not touched: they stay with the slots and adapt only as :meth:`step_all` adapts them, by
+        about 1/200 per step.  Over a large cooling that is too slow for a many-dimensional space -- proposals far wider
+        than the cold Boltzmann width are almost all rejected, the population stops moving between stages and ``log_z``
+        comes out biased low (a 16-dimensional quadratic cooled a hundredfold in 40 stages of 10 sweeps: 1-2 too low).
+        Start from a population equilibrated at the first temperature, and where the energy is close to quadratic scale
+        the widths by ``sqrt(T_new / T_old)`` at each stage (``tests/test_gpu_population.py``, ``_anneal_quadratic``) or
+        give each stage enough sweeps for the adaptation to follow."""
+        for t in np.asarray(temps, dtype=np.float64).ravel():
+            self.resample(t)
+            self.step_all(n_sweeps)
+
+    def population_stats(self):
+        """The stages so far: ``{"stages": int, "temps", "log_weight", "neff_fraction", "n_finite", "log_z"}`` -- per stage its
+        new temperature, the estimate of ``ln Z(T_k) / Z(T_{k-1})``, ``W^2 / (N S2)``, the chains of finite weight, and
+        ``log_z`` = the running sum of ``log_weight`` (``ln Z(T_k) / Z(T_start)``)."""
+        stages = ctypes.c_uint64()
+        self._check(self._lib.me_population_stats(self._handle, ctypes.byref(stages), None, None, None, None, 0))
+        k = stages.value
+        temps, lw, neff = (np.empty(k, dtype=np.float64) for _ in range(3))
+        nfin = np.empty(k, dtype=np.int64)
+        if k:
+            self._check(self._lib.me_population_stats(self._handle, ctypes.byref(stages), _as_double_ptr(temps),
+                                                      _as_double_ptr(lw), _as_double_ptr(neff),
+                                                      nfin.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), k))
+        return {"stages": k, "temps": temps, "log_weight": lw, "neff_fraction": neff, "n_finite": nfin,
+                "log_z": np.cumsum(lw)}
+
+    def families(self):
+        """The family id of every local chain, ``(n_chains,)`` int64: the global chain id of its founder (``chain_offset + j``
+        before the first stage).  Resampling keeps the array non-decreasing."""
+        out = np.empty(self.n_chains, dtype=np.int64)
+        self._check(self._lib.me_population_families(self._handle, 0, self.n_chains,
+                                                     out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        return out
+
+    def n_families(self):
+        """The number of surviving families, ``1 + #{j : fam[j] != fam[j-1]}``."""
+        fam = self.families()
+        return int(1 + np.count_nonzero(fam[1:] != fam[:-1]))
+
     # -- RCCL behind the C ABI (me_comm_*): the all-reduce of the moments runs on the engine's own streams, no PyTorch
     @staticmethod
     def comm_unique_id():
@@ -689,6 +779,12 @@ class MetropolisEngine:
         if temps is not None:                        # a ladder engine: the ladder and the replica-exchange position
             state["temperatures"] = temps
             state["replica_round"], state["swap_attempted"], state["swap_accepted"] = self.swap_stats()
+        if self._population_used:                    # set_temp / resample: the temperature, the stages and the families
+            stats = self.population_stats()
+            state["temp"] = float(self.temp)
+            for key in ("temps", "log_weight", "neff_fraction", "n_finite"):
+                state["population_" + key] = stats[key]
+            state["families"] = self.families()
         return state
 
     def load_state_dict(self, state):
@@ -717,9 +813,32 @@ class MetropolisEngine:
                 raise ValueError("checkpoint shared_factor has the wrong length")
         if "accepted" in state and "proposed" in state and int(state["accepted"]) > int(state["proposed"]):
             raise ValueError("checkpoint accept counters are inconsistent")
+        population = None
+        if "temp" in state:
+            temp = float(state["temp"])
+            if not (np.isfinite(temp) and temp >= 0):
+                raise ValueError("checkpoint temp must be finite and >= 0")
+            if "temperatures" in state:
+                raise ValueError("the checkpoint carries both a scalar temp and a temperature ladder")
+            keys = ("population_temps", "population_log_weight", "population_neff_fraction", "population_n_finite")
+            if any(key not in state for key in keys) or "families" not in state:
+                raise ValueError("checkpoint lacks the population stages / families of its temp")
+            temps, lw, neff = (np.ascontiguousarray(state[key], dtype=np.float64) for key in keys[:3])
+            nfin = np.ascontiguousarray(state[keys[3]], dtype=np.int64)
+            if not (temps.ndim == 1 and lw.shape == neff.shape == nfin.shape == temps.shape):
+                raise ValueError("checkpoint population stages must be 1-D arrays of one length")
+            if not np.all(np.isfinite(temps) & (temps > 0)) or np.any(nfin < 0) or np.any(nfin > self.n_chains):
+                raise ValueError("checkpoint population stages are inconsistent")
+            fam = np.ascontiguousarray(state["families"], dtype=np.int64)
+            if fam.shape != (self.n_chains,):
+                raise ValueError("checkpoint families must hold one id per chain")
+            population = (temp, temps, lw, neff, nfin, fam)
+        # a checkpoint without "temp" was taken before set_temp / resample were used: the engine returns to its constructor's
+        # temp, no stages and every chain its own family, so that its history and the checkpoint's do not mix
+        reset_population = population is None and self._population_used
         ladder = None
         if "temperatures" in state:
-            if self.temp != 0:
+            if (self._initial_temp if reset_population else self.temp) != 0:
                 raise ValueError("the checkpoint carries a temperature ladder: this engine has a scalar temp")
             ladder = validate_ladder(state["temperatures"], self.n_chains)
             if "replica_round" not in state or "swap_attempted" not in state or "swap_accepted" not in state:
@@ -730,6 +849,9 @@ class MetropolisEngine:
                 raise ValueError("checkpoint swap counters must have one entry per adjacent pair of rungs")
             if np.any(acc < 0) or np.any(acc > att) or int(state["replica_round"]) < 0:
                 raise ValueError("checkpoint swap counters are inconsistent")
+        if reset_population:
+            self._reset_population()
+        if ladder is not None:
             # (first, so that an engine that cannot carry a ladder refuses before anything else is written)
             self.set_temperatures(ladder)
         for field, values in todo:
@@ -745,6 +867,16 @@ class MetropolisEngine:
             att = (ctypes.c_uint64 * max(n_pairs, 1))(*[int(v) for v in state["swap_attempted"]])
             acc = (ctypes.c_uint64 * max(n_pairs, 1))(*[int(v) for v in state["swap_accepted"]])
             self._check(self._lib.me_set_replica_stats(self._handle, int(state["replica_round"]), att, acc, n_pairs))
+        if population is not None:
+            temp, temps, lw, neff, nfin, fam = population
+            if self.temperatures is not None:          # a scalar-temperature checkpoint replaces a ladder
+                self.set_temperatures(None)
+            self.set_temp(temp)
+            self._check(self._lib.me_set_population_stats(self._handle, temps.size, _as_double_ptr(temps), _as_double_ptr(lw),
+                                                          _as_double_ptr(neff),
+                                                          nfin.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+            self._check(self._lib.me_set_population_families(self._handle, 0, self.n_chains,
+                                                             fam.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
 
     # ------------------------------------------------------------------ time series (:31-35, :350-356, :466-479)
     def trace(self):

@@ -9,6 +9,9 @@ mkdir -p tools/variants/obj_$name
 for u in me_api me_generic me_statistics me_runtime_dims me_replica; do
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -I include "$@" -c metropolisengine_amd/csrc/$u.hip -o tools/variants/obj_$name/$u.o &
 done
+# population annealing: built with the flag build.py gives it (its scan relies on unfused products, me_population.hip)
+hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -I include -ffp-contract=off "$@" -c metropolisengine_amd/csrc/me_population.hip \
+  -o tools/variants/obj_$name/me_population.o &
 hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -I include -DME_NR=${NR:-16} -DME_NC=${NC:-0} -DME_DENSE=${DENSE:-0} -DME_PER_CHAIN=${PER_CHAIN:-1} "$@" \
   -c metropolisengine_amd/csrc/me_kernels.hip -o tools/variants/obj_$name/k.o &
 wait
