@@ -43,6 +43,17 @@ def _as_double_ptr(arr):
     return arr.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
 
 
+def _initial_state(initial_real_params, initial_complex_params):
+    """[real | Re z | Im z] of the initial parameters (one more state for the traced energy's self-check), or None if
+    they do not convert; the constructor validates them itself."""
+    try:
+        r = np.asarray([] if initial_real_params is None else initial_real_params, dtype=np.float64).reshape(-1)
+        c = np.asarray([] if initial_complex_params is None else initial_complex_params, dtype=np.complex128).reshape(-1)
+    except (TypeError, ValueError):
+        return None
+    return np.concatenate([r, c.real, c.imag])
+
+
 def unpack_real_block(packed, nr):
     """[n, P] packed lower triangles -> [n, nr, nr] symmetric matrices (real block of ME_FIELD_COV)."""
     n = packed.shape[0]
@@ -125,7 +136,8 @@ class MetropolisEngine:
             traced_reject = reject_condition if (reject_condition is not None and not isinstance(reject_condition, RejectSpec)) else None
             if traced_reject is not None and not callable(traced_reject):
                 raise TypeError("reject_condition must be a RejectSpec, a callable (real_params, complex_params) -> bool, or None")
-            energy_functions = PythonEnergy(energy_functions, reject=traced_reject)
+            energy_functions = PythonEnergy(energy_functions, reject=traced_reject,
+                                            initial=_initial_state(initial_real_params, initial_complex_params))
             if traced_reject is not None:
                 reject_condition = PythonReject()
         if reject_condition is not None and not isinstance(reject_condition, RejectSpec):

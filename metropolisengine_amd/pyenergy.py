@@ -4,17 +4,32 @@ dictionaries, and ``reject_condition``) TRACED into a HIP device function and co
 The reference couples sampler and physics through a Python callable that it invokes once per proposal
 (metropolis_engine.py:20, :111-120, :250).  A HIP kernel cannot call Python, and this engine has no CPU fallback -- so the
 callable is executed ONCE, at construction, on symbolic stand-ins for the parameters: ``real_params`` / ``complex_params`` are
-numpy object arrays of :class:`Sym` / :class:`SymComplex` nodes that overload arithmetic and record what the function
-computes.  Whatever Python the function is written in -- lambdas, methods of a ``System`` object holding constants,
+numpy object arrays (:class:`SymArray`) of :class:`Sym` / :class:`SymComplex` nodes that overload arithmetic and record what
+the function computes.  Whatever Python the function is written in -- lambdas, methods of a ``System`` object holding constants,
 ``*real_params`` unpacking, closures, helper functions, ``numpy`` ufuncs and reductions (the forms of README.md:26-33,
 demo/toymodel_xypotentialwell.py:13-32 and demo/toymodel_complex_and_real.py:17-33) -- runs as ordinary Python; only
 arithmetic on the parameters is recorded.  The recorded expression graph is written out as ``me_user_energy`` (straight-line
 code, common subexpressions shared, sums of two products as explicit fused multiply-adds), compiled by hipcc
 (``build.build_user_energy``) and loaded like any hand-written plugin (include/metropolis_user_energy.h).
 
-What cannot be traced raises :class:`TraceError` at construction: control flow that depends on parameter VALUES
-(``if x > 0``, ``max(x, y)``, ``math.exp(x)`` -- use ``np.exp`` --, ``float(x)``), because the trace sees one symbolic
-evaluation, not one per chain.
+What traces: ``+ - * /``, unary minus, ``abs``; integer powers (square and multiply), ``x ** 0.5`` (sqrt), real powers
+and ``2 ** x`` (pow); ``np.sqrt``, ``np.exp``, ``np.log``, ``np.sin``, ``np.cos``, ``np.tan``, ``np.tanh``, ``np.sinh``,
+``np.cosh``, ``np.arctan``, ``np.arctan2``, ``np.abs``, ``np.square`` on real values; complex ``+ - * /``, integer powers and
+``abs``; element-wise ``.real``, ``.imag``, ``.conj()``, ``.conjugate()``, ``np.real``, ``np.imag``, ``np.conj`` and
+``np.angle`` (``arctan2(im, re)``) on parameter arrays and on arrays computed from them; reductions and products that
+numpy builds from these (``np.sum``, ``np.mean``, ``np.var``, ``np.prod``, ``np.dot``, ``np.vdot``, ``@``, ``np.einsum``,
+Python ``sum``), slicing and broadcasting against constant arrays.  A ``reject_condition`` may compare traced values and
+combine the comparisons with ``& | ~``.
+
+What cannot be traced raises :class:`TraceError` at construction -- every exception raised while tracing is re-raised as
+one, naming the original: control flow that depends on parameter VALUES (``if x > 0``, chained comparisons, ``max(x, y)``,
+``np.max``, ``np.where``, ``np.clip``, ``np.sign``, ``np.any`` / ``np.all``, ``math.exp(x)`` -- use ``np.exp`` --,
+``float(x)``), because the trace sees one symbolic evaluation, not one per chain; and numpy functions without a device
+counterpart here (``np.log1p``, ``np.expm1``, ``np.hypot``, complex ``np.exp`` / ``np.log`` / ``np.sqrt``,
+``np.linalg.norm`` of a complex array).  After tracing, the recorded graph is evaluated at 8 fixed-seed standard-normal
+states (and the initial state, when the engine knows it) and compared with the callable on numbers -- for a term
+dictionary, with every group's callable under each name: a difference beyond rounding is a :class:`TraceError` too, so an
+idiom that records something other than what numpy computes cannot reach the GPU silently.
 """
 import hashlib
 import math
@@ -271,6 +286,59 @@ class SymComplex:
     __float__ = __complex__
 
 
+def _real_part(v):
+    if isinstance(v, SymComplex):
+        return v.re
+    if isinstance(v, (Sym, int, float, complex, np.number)) and not isinstance(v, (bool, np.bool_)):
+        return v.real
+    raise TraceError("cannot take the real part of %r in a traced energy" % (v,))
+
+
+def _imag_part(v):
+    if isinstance(v, SymComplex):
+        return v.im
+    if isinstance(v, (Sym, int, float, complex, np.number)) and not isinstance(v, (bool, np.bool_)):
+        return v.imag
+    raise TraceError("cannot take the imaginary part of %r in a traced energy" % (v,))
+
+
+def _angle(v):
+    return Sym.lift(_imag_part(v)).arctan2(_real_part(v))
+
+
+class SymArray(np.ndarray):
+    """The object arrays handed to a traced callable.  A plain object array answers ``.real`` with itself and ``.imag``
+    with zeros, whatever its elements; here both act on each element (``SymComplex.re`` / ``.im``; a real :class:`Sym` is
+    its own real part and has imaginary part 0), as on the reference's ``complex128`` arrays.  numpy keeps the subclass
+    through ufuncs, so arrays computed from the parameters (``(c * c.conj()).real``, ``(c ** 2).imag``) behave the same;
+    ``np.real`` / ``np.imag`` read these properties, ``np.conj`` calls each element's ``conjugate``, and ``np.angle``
+    becomes ``arctan2(im, re)`` element by element.  Its priority is above the nodes', so that ``array * node`` is
+    numpy's element-wise product rather than a deferral to the node."""
+    __array_priority__ = 2000.0
+
+    def _map(self, fn):
+        out = np.empty(self.shape, dtype=object)
+        for i, v in enumerate(self.flat):
+            out.flat[i] = fn(v)
+        return out.view(SymArray)
+
+    real = property(lambda self: self._map(_real_part))
+    imag = property(lambda self: self._map(_imag_part))
+
+    def __array_wrap__(self, array, context=None, return_scalar=False):
+        if array.ndim == 0:                           # a reduction (np.prod, ...): the node, as for a plain object array
+            return array[()]
+        return super().__array_wrap__(array, context, return_scalar)
+
+    def __array_function__(self, func, types, args, kwargs):
+        if func is np.angle:
+            z = args[0] if args else kwargs["z"]
+            deg = args[1] if len(args) > 1 else kwargs.get("deg", False)
+            out = np.asanyarray(z).view(SymArray)._map(_angle)
+            return out * (180.0 / math.pi) if deg else out
+        return super().__array_function__(func, types, args, kwargs)
+
+
 # --------------------------------------------------------------------------------------------------- tracing
 def _inputs(n_real, n_complex):
     real = np.empty(n_real, dtype=object)
@@ -279,7 +347,7 @@ def _inputs(n_real, n_complex):
     cplx = np.empty(n_complex, dtype=object)
     for j in range(n_complex):
         cplx[j] = SymComplex(Sym("x", value=n_real + j), Sym("x", value=n_real + n_complex + j))
-    return real, cplx
+    return real.view(SymArray), cplx.view(SymArray)
 
 
 def _scalar(v):
@@ -290,19 +358,141 @@ def _scalar(v):
     return v
 
 
+def _call(fn, n_real, n_complex, what):
+    """``fn`` on symbolic parameters; any failure is a :class:`TraceError` that names the original exception."""
+    real, cplx = _inputs(n_real, n_complex)
+    try:
+        return _scalar(fn(real, cplx))
+    except TraceError:
+        raise
+    except Exception as exc:
+        raise TraceError("the %s cannot be traced: %s: %s" % (what, type(exc).__name__, exc)) from exc
+
+
 def trace_energy(fn, n_real, n_complex):
     """Run ``fn(real_params, complex_params)`` on symbolic parameters; returns the real :class:`Sym` it computes (the real
     part of a complex-typed result, SURVEY.md quirk Q11: the Landau toy returns ``complex128`` with zero imaginary part)."""
-    real, cplx = _inputs(n_real, n_complex)
-    out = _scalar(fn(real, cplx))
+    out = _call(fn, n_real, n_complex, "energy")
     if isinstance(out, SymComplex):
         out = out.re
     return Sym.lift(out)
 
 
 def trace_reject(fn, n_real, n_complex):
-    real, cplx = _inputs(n_real, n_complex)
-    return SymBool.lift(_scalar(fn(real, cplx)))
+    return SymBool.lift(_call(fn, n_real, n_complex, "reject condition"))
+
+
+# --------------------------------------------------------------------------------------------------- numeric self-check
+# d/da of the unary ops, for the rounding scale below
+_DERIV = {"neg": lambda a, v: 1.0, "abs": lambda a, v: 1.0, "sqrt": lambda a, v: 0.5 / v, "exp": lambda a, v: v,
+          "log": lambda a, v: 1.0 / a, "sin": lambda a, v: np.cos(a), "cos": lambda a, v: np.sin(a),
+          "tan": lambda a, v: 1.0 + v * v, "tanh": lambda a, v: 1.0 - v * v, "sinh": lambda a, v: np.cosh(a),
+          "cosh": lambda a, v: np.sinh(a), "arctan": lambda a, v: 1.0 / (1.0 + a * a)}
+_FLOAT_OPS = {"add": np.add, "sub": np.subtract, "mul": np.multiply, "div": np.divide, "pow": np.power, "neg": np.negative,
+              "abs": np.abs, "sqrt": np.sqrt, "exp": np.exp, "log": np.log, "sin": np.sin, "cos": np.cos, "tan": np.tan,
+              "tanh": np.tanh, "sinh": np.sinh, "cosh": np.cosh, "arctan": np.arctan, "arctan2": np.arctan2}
+_FLOAT_CMP = {"lt": np.less, "le": np.less_equal, "gt": np.greater, "ge": np.greater_equal, "eq": np.equal, "ne": np.not_equal}
+
+
+def _evaluate(root, x):
+    """``(value, scale)`` of a recorded graph at the float64 state ``x``: the value, and a first-order bound on how far
+    rounding can move it (in units of the unit roundoff: sums add the operands' scales, every other op weights them by its
+    partial derivatives and adds its own result).  Comparisons evaluate to booleans with scale 0."""
+    memo = {}
+    stack = [(root, False)]
+    while stack:
+        node, ready = stack.pop()
+        if id(node) in memo:
+            continue
+        if not ready and node.args:
+            stack.append((node, True))
+            stack.extend((a, False) for a in node.args)
+            continue
+        args = [memo[id(a)] for a in node.args]
+        if isinstance(node, SymBool):
+            if node.op == "cmp":
+                v = bool(_FLOAT_CMP[node.cmp](args[0][0], args[1][0]))
+            elif node.op == "const":
+                v = bool(node.cmp)
+            elif node.op == "not":
+                v = not args[0][0]
+            else:
+                v = (args[0][0] and args[1][0]) if node.op == "and" else (args[0][0] or args[1][0])
+            memo[id(node)] = (v, 0.0)
+            continue
+        if node.op == "x":
+            v = np.float64(x[node.value])
+            memo[id(node)] = (v, abs(v))
+            continue
+        if node.op == "const":
+            memo[id(node)] = (np.float64(node.value), abs(node.value))
+            continue
+        v = _FLOAT_OPS[node.op](*[a[0] for a in args])
+        if node.op in ("add", "sub"):
+            s = args[0][1] + args[1][1]
+        elif node.op == "mul":
+            (a, sa), (b, sb) = args
+            s = sa * abs(b) + abs(a) * sb
+        elif node.op == "div":
+            (a, sa), (b, sb) = args
+            s = sa / abs(b) + abs(a) * sb / (b * b) + abs(v)
+        elif node.op == "pow":
+            (a, sa), (b, sb) = args
+            s = abs(b * a ** (b - 1.0)) * sa + (abs(v * np.log(abs(a))) * sb if sb and v else 0.0) + abs(v)
+        elif node.op == "arctan2":
+            (a, sa), (b, sb) = args
+            s = (abs(b) * sa + abs(a) * sb) / (a * a + b * b) + abs(v)
+        else:
+            a, sa = args[0]
+            s = (abs(_DERIV[node.op](a, v)) * sa if sa else 0.0) + abs(v)
+        memo[id(node)] = (v, s)
+    return memo[id(root)]
+
+
+def _numeric(fn, x, n_real, n_complex):
+    out = _scalar(fn(x[:n_real].copy(), x[n_real:n_real + n_complex] + 1j * x[n_real + n_complex:]))
+    return out if isinstance(out, (bool, np.bool_)) else complex(out).real
+
+
+def _agree(got, want, scale):
+    if isinstance(want, (bool, np.bool_)):
+        return bool(got) == bool(want)
+    if math.isnan(want):
+        return True                                    # out of the callable's domain
+    if math.isnan(got):
+        return False
+    if not math.isfinite(scale):
+        return True                                    # no usable bound
+    if math.isinf(want) or math.isinf(got):
+        return got == want
+    return abs(got - want) <= 1e-8 * scale             # rounding is ~1e-16 * scale: a traced idiom gone wrong is not
+
+
+def _self_check(node, fns, n_real, n_complex, states, what):
+    """Compare the recorded graph with every callable in ``fns`` at ``states``; a disagreement is a TraceError."""
+    with np.errstate(all="ignore"):
+        for x in states:
+            got, scale = _evaluate(node, x)
+            for group, fn in fns:
+                try:
+                    want = _numeric(fn, x, n_real, n_complex)
+                except Exception as exc:
+                    raise TraceError("the %s fails on numbers: %s: %s" % (what, type(exc).__name__, exc)) from exc
+                if not _agree(got, want, float(scale)):
+                    raise TraceError(
+                        "the traced %s%s computes %r where the function gives %r at real_params=%s, complex_params=%s: it "
+                        "uses an operation that the trace records differently from numpy" % (
+                            what, " (group %r)" % group if group else "", got, want, x[:n_real].tolist(),
+                            (x[n_real:n_real + n_complex] + 1j * x[n_real + n_complex:]).tolist()))
+
+
+def check_states(n_real, n_complex, initial=None):
+    """The states of the self-check: 8 fixed-seed standard-normal states, then ``initial`` ([real | Re z | Im z]) if
+    given."""
+    states = list(np.random.default_rng(20261016).standard_normal((8, n_real + 2 * n_complex)))
+    if initial is not None:
+        states.append(np.asarray(initial, dtype=np.float64).reshape(-1))
+    return states
 
 
 # --------------------------------------------------------------------------------------------------- code generation
@@ -426,19 +616,23 @@ def _function(header, roots, ret):
     return "%s {\n%s%s}\n" % (header, body, ret(names))
 
 
-def generate_source(energy, n_real, n_complex, reject=None):
+def generate_source(energy, n_real, n_complex, reject=None, initial=None):
     """HIP source of the plugin for ``energy`` (a callable, or the reference's dictionary ``{"complex": {term: fn},
-    "real": {...}, "all": {...}}``, metropolis_engine.py:111-116) and an optional ``reject`` callable.  Returns
-    ``(source_text, term_names)``."""
+    "real": {...}, "all": {...}}``, metropolis_engine.py:111-116) and an optional ``reject`` callable.  Every traced graph
+    is checked against its callable(s) at :func:`check_states` (``initial``: the engine's initial state, if known).
+    Returns ``(source_text, term_names)``."""
+    states = check_states(n_real, n_complex, initial)
     parts = [_PRELUDE]
     if isinstance(energy, dict):
         names = sorted(set().union(*[set(group) for group in energy.values()]))
         roots, groups = [], []
         for name in names:
-            fn = None
-            for group in ("all", "real", "complex"):
-                fn = fn or energy.get(group, {}).get(name)
-            roots.append(trace_energy(fn, n_real, n_complex))
+            fns = [(group, energy[group][name]) for group in ("all", "real", "complex") if name in energy.get(group, {})]
+            # one graph per name, traced from the first group that has it; every group's callable must compute it
+            roots.append(trace_energy(fns[0][1], n_real, n_complex))
+            distinct = list({id(fn): (group, fn) for group, fn in reversed(fns)}.values())
+            _self_check(roots[-1], distinct if len(distinct) > 1 else [(None, fns[0][1])], n_real, n_complex, states,
+                        "energy term %r" % name)
             groups.append((1 if name in energy.get("real", {}) else 0) | (2 if name in energy.get("complex", {}) else 0))
         parts.append("#define ME_USER_N_TERMS %d\n" % len(names))
         parts.append("constexpr unsigned me_user_term_groups(int term) { return %s; }\n" % " : ".join(
@@ -451,11 +645,13 @@ def generate_source(energy, n_real, n_complex, reject=None):
         term_names = tuple(names)
     else:
         root = trace_energy(energy, n_real, n_complex)
+        _self_check(root, [(None, energy)], n_real, n_complex, states, "energy")
         parts.append(_function("template <typename R>\n__device__ R me_user_energy(const R *x, const R *coef)", [root],
                                lambda n: "  return %s;\n" % n[0]))
         term_names = ("total",)
     if reject is not None:
         cond = trace_reject(reject, n_real, n_complex)
+        _self_check(cond, [(None, reject)], n_real, n_complex, states, "reject condition")
         parts.append("#define ME_USER_HAS_REJECT\n")
         parts.append(_function("template <typename R>\n__device__ bool me_user_reject(const R *x, const R *coef)", [cond],
                                lambda n: "  return %s;\n" % n[0]))
@@ -466,13 +662,13 @@ class PythonEnergy(EnergySpec):
     """``energy_functions`` given as the reference gives it -- a Python callable ``(real_params, complex_params) -> float`` or
     its term dictionary -- traced at construction and compiled as a user plugin (see the module docstring).  ``reject`` is
     the reference's ``reject_condition`` callable (honoured when passed to the constructor; the reference drops it there,
-    quirk Q6)."""
+    quirk Q6).  ``initial`` ([real | Re z | Im z]), if given, is one more state of the numeric self-check."""
     kind = _capi.ENERGY_USER
 
-    def __init__(self, energy, reject=None):
+    def __init__(self, energy, reject=None, initial=None):
         if not (callable(energy) or isinstance(energy, dict)):
             raise TypeError("energy must be a callable or a dictionary of term callables")
-        self.energy, self.reject = energy, reject
+        self.energy, self.reject, self.initial = energy, reject, initial
         self.term_names = tuple(sorted(set().union(*[set(g) for g in energy.values()]))) if isinstance(energy, dict) else ("total",)
         self.name = None
         self._loaded = set()
@@ -484,7 +680,8 @@ class PythonEnergy(EnergySpec):
         """Trace, write the generated source to ``_build/pyenergy/py<digest>.h`` and compile it (hipcc, once per distinct
         energy and dimensions; up to date plugins are reused).  Returns the plugin path; sets ``self.name``."""
         from . import build
-        source, _ = generate_source(self.energy, n_real, n_complex, self.reject)
+        initial = self.initial if self.initial is not None and np.size(self.initial) == n_real + 2 * n_complex else None
+        source, _ = generate_source(self.energy, n_real, n_complex, self.reject, initial)
         digest = hashlib.sha256(("%d,%d\n" % (n_real, n_complex) + source).encode()).hexdigest()[:16]
         self.name = "py" + digest
         directory = os.path.join(build.OBJ_DIR, "pyenergy")

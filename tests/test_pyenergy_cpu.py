@@ -10,32 +10,9 @@ import pytest
 
 from metropolisengine_amd import pyenergy as pe
 
+from pyenergy_eval import evaluate                                                                # noqa: E402
 from reference_style_energies import (landau_dictionary, landau_total, numpy_style, readme_energy, wall,   # noqa: E402
                                       well_energy)
-
-# ---- a numpy interpreter of the recorded graph (test infrastructure only) ----------------------------------------
-_OPS = {"add": np.add, "sub": np.subtract, "mul": np.multiply, "div": np.divide, "pow": np.power, "neg": np.negative,
-        "abs": np.abs, "sqrt": np.sqrt, "exp": np.exp, "log": np.log, "sin": np.sin, "cos": np.cos, "tan": np.tan,
-        "tanh": np.tanh, "sinh": np.sinh, "cosh": np.cosh, "arctan": np.arctan, "arctan2": np.arctan2}
-_CMP = {"lt": np.less, "le": np.less_equal, "gt": np.greater, "ge": np.greater_equal, "eq": np.equal, "ne": np.not_equal}
-
-
-def evaluate(node, x):
-    if isinstance(node, pe.SymBool):
-        if node.op == "cmp":
-            return _CMP[node.cmp](evaluate(node.args[0], x), evaluate(node.args[1], x))
-        if node.op == "const":
-            return node.cmp
-        if node.op == "not":
-            return not evaluate(node.args[0], x)
-        a, b = evaluate(node.args[0], x), evaluate(node.args[1], x)
-        return (a and b) if node.op == "and" else (a or b)
-    if node.op == "x":
-        return x[node.value]
-    if node.op == "const":
-        return node.value
-    return _OPS[node.op](*[evaluate(a, x) for a in node.args])
-
 
 @pytest.mark.parametrize("fn,nr,nc", [(readme_energy, 1, 0), (well_energy, 2, 0), (landau_total, 2, 1), (numpy_style, 3, 2)],
                          ids=["readme", "xy_well", "landau", "numpy_style"])
