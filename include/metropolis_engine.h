@@ -335,6 +335,49 @@ int me_set_population_stats(me_engine *engine, uint64_t stages, const double *st
 int me_population_families(me_engine *engine, int64_t chain_begin, int64_t n, int64_t *dst);
 int me_set_population_families(me_engine *engine, int64_t chain_begin, int64_t n, const int64_t *src);
 
+/* Energy samples, MBAR free energies and temperature reweighting of a ladder (no reference counterpart; csrc/me_mbar.hip
+ * has the definition).
+ *   me_energy_samples_enable   allocate a float64 device field [capacity_records][n_chains] and set the record count to 0;
+ *                       capacity_records = 0 frees it.  Any engine with one coherent ledger (ladder or scalar temp, every
+ *                       kernel set); ME_ERR_UNSUPPORTED with ME_FLAG_REFERENCE_ENERGY_LEDGERS.
+ *   me_energy_samples_record   enqueue one kernel on the engine's stream (asynchronous, like me_step): the next row gets E_i for
+ *                       every chain, E_i = the sum of chain i's ledger rows in row order in the device dtype, widened to
+ *                       float64 (the quantity of me_replica_exchange and me_population_resample).  ME_ERR_STATE when the
+ *                       store is not enabled or full.
+ *   me_energy_samples_count    rows recorded and the capacity (0, 0 when not enabled).
+ *   me_energy_samples_get      rows [record_begin, record_begin + n_records) as [record][chain] doubles (waits for the stream).
+ *   me_energy_samples_set      replace the content by n_records host rows (<= capacity): resumes a run; a checkpoint
+ *                       (me_get / me_set of the fields) does NOT carry the samples.
+ *   A sample is indexed by its slot; slot c belongs to rung c / M whatever was swapped into it.  me_set_temperature_ladder
+ *   therefore sets the record count to 0: samples taken under another ladder would be attributed to the wrong temperatures.
+ *   me_mbar_solve              the multistate Bennett acceptance ratio over the recorded samples and the engine's ladder
+ *                       (K rungs): f_k = -ln Z(T_k) / Z(T_0) by self-consistent iteration from f = 0 until the largest
+ *                       change of an f_k is <= tolerance (> 0) or max_iterations (>= 1) are done; *residual is that last
+ *                       change, *iterations the count, n_used[k] the finite samples of rung k (non-finite energies are
+ *                       skipped).  All sums have a fixed order: a solve is bitwise reproducible.  ME_ERR_STATE without a
+ *                       ladder, without records, or when a rung has no finite sample; ME_ERR_UNSUPPORTED beyond 64 rungs.
+ *   me_mbar_reweight           for each of the n target temperatures (finite, > 0), from f of me_mbar_solve: ln_z =
+ *                       ln Z(T) / Z(T_0), the mean and variance of the energy at T and neff_fraction = (sum w)^2 / (N sum w^2)
+ *                       of the reweighting weights w (N = all finite samples).  Any output pointer may be NULL.
+ *   me_mbar_solve_samples / me_mbar_reweight_samples   the same kernels on host arrays (engine-independent, like
+ *                       me_detect_equilibration): energies[n_samples], rungs[n_samples] in [0, n_rungs), ladder_temps[n_rungs]
+ *                       finite and > 0 (any order).  For samples gathered from several shards, and for subsets of a run. */
+int me_energy_samples_enable(me_engine *engine, int64_t capacity_records);
+int me_energy_samples_record(me_engine *engine);
+int me_energy_samples_count(me_engine *engine, int64_t *records, int64_t *capacity);
+int me_energy_samples_get(me_engine *engine, int64_t record_begin, int64_t n_records, double *dst);
+int me_energy_samples_set(me_engine *engine, int64_t n_records, const double *src);
+int me_mbar_solve(me_engine *engine, double tolerance, int32_t max_iterations, double *f_out, int32_t *iterations,
+                  double *residual, int64_t *n_used_out);
+int me_mbar_reweight(me_engine *engine, const double *f, const double *temps, int32_t n, double *ln_z, double *mean_e,
+                     double *var_e, double *neff_fraction);
+int me_mbar_solve_samples(int32_t device_id, const double *energies, const int32_t *rungs, int64_t n_samples,
+                          const double *ladder_temps, int32_t n_rungs, double tolerance, int32_t max_iterations, double *f_out,
+                          int32_t *iterations, double *residual, int64_t *n_used_out);
+int me_mbar_reweight_samples(int32_t device_id, const double *energies, const int32_t *rungs, int64_t n_samples,
+                             const double *ladder_temps, int32_t n_rungs, const double *f, const double *temps, int32_t n,
+                             double *ln_z, double *mean_e, double *var_e, double *neff_fraction);
+
 /* Text of the last error on this engine (or of the last failed me_create when engine is NULL). */
 int me_last_error(me_engine *engine, char *buf, size_t buf_bytes);
 

@@ -107,6 +107,19 @@ SYMBOLS = {
     "me_set_population_stats": (ctypes.c_int, [_H, ctypes.c_uint64, _dp, _dp, _dp, ctypes.POINTER(ctypes.c_int64)]),
     "me_population_families": (ctypes.c_int, [_H, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
     "me_set_population_families": (ctypes.c_int, [_H, ctypes.c_int64, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
+    "me_energy_samples_enable": (ctypes.c_int, [_H, ctypes.c_int64]),
+    "me_energy_samples_record": (ctypes.c_int, [_H]),
+    "me_energy_samples_count": (ctypes.c_int, [_H, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)]),
+    "me_energy_samples_get": (ctypes.c_int, [_H, ctypes.c_int64, ctypes.c_int64, _dp]),
+    "me_energy_samples_set": (ctypes.c_int, [_H, ctypes.c_int64, _dp]),
+    "me_mbar_solve": (ctypes.c_int, [_H, ctypes.c_double, ctypes.c_int32, _dp, ctypes.POINTER(ctypes.c_int32), _dp,
+                                     ctypes.POINTER(ctypes.c_int64)]),
+    "me_mbar_reweight": (ctypes.c_int, [_H, _dp, _dp, ctypes.c_int32, _dp, _dp, _dp, _dp]),
+    "me_mbar_solve_samples": (ctypes.c_int, [ctypes.c_int32, _dp, ctypes.POINTER(ctypes.c_int32), ctypes.c_int64, _dp,
+                                             ctypes.c_int32, ctypes.c_double, ctypes.c_int32, _dp,
+                                             ctypes.POINTER(ctypes.c_int32), _dp, ctypes.POINTER(ctypes.c_int64)]),
+    "me_mbar_reweight_samples": (ctypes.c_int, [ctypes.c_int32, _dp, ctypes.POINTER(ctypes.c_int32), ctypes.c_int64, _dp,
+                                                ctypes.c_int32, _dp, _dp, ctypes.c_int32, _dp, _dp, _dp, _dp]),
 }
 
 

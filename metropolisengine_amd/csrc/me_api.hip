@@ -196,6 +196,9 @@ struct me_engine {
   double *pop_records = nullptr;                          // (log_weight, neff_fraction, n_finite) per stage
   unsigned long long pop_stages = 0, pop_capacity = 0;
   std::vector<double> pop_temps;                          // T_new of every stage
+  // recorded energy samples (me_energy_samples_*, me_mbar.hip): float64 [esamp_capacity][n], esamp_rows of them filled
+  double *esamp = nullptr;
+  long long esamp_capacity = 0, esamp_rows = 0;
   std::string err;
 };
 
@@ -380,7 +383,7 @@ void release(me_engine *e) {
   void *bufs[] = {e->x, e->energy, e->width, e->mean, e->cov, e->obs_mean, e->factor, e->shared_factor, e->shared_full, e->shared_image, e->energy_image,
                   e->coef_dev, e->row_dev, e->accept_slots, e->accept_total, e->status, e->pool_dev, e->pool_partials, e->trace_dev,
                   e->ladder, e->pair_counts, e->range_x, e->pop_fam, e->pop_fam_out, e->pop_x, e->pop_energy, e->pop_anc,
-                  e->pop_scratch, e->pop_records};
+                  e->pop_scratch, e->pop_records, e->esamp};
   for (void *b : bufs)
     if (b) (void)hipFree(b);
   if (e->comm && e->rccl) (void)e->rccl->comm_destroy(e->comm);
@@ -1500,6 +1503,7 @@ int free_ladder(me_engine *e) {
   e->n_rungs = 0;
   e->ladder_temps.clear();
   e->replica_round = 0;
+  e->esamp_rows = 0;          // recorded energies belong to the rungs of the ladder they were taken under
   return ME_OK;
 }
 }  // namespace
@@ -1807,6 +1811,196 @@ int me_set_population_families(me_engine *e, int64_t chain_begin, int64_t n, con
   ME_HIP(e, hipMemcpyAsync(e->pop_fam + chain_begin, src, (size_t)n * sizeof(long long), hipMemcpyHostToDevice, e->stream));
   ME_HIP(e, hipStreamSynchronize(e->stream));
   return ME_OK;
+}
+
+// ---- energy samples, MBAR free energies and reweighting (me_mbar.hip) --------------------------------------------------
+namespace {
+int mbar_check_common(me_engine *e, int n_rungs, int empty_rung, hipError_t err) {
+  if (err == hipErrorInvalidValue)
+    return fail(e, ME_ERR_UNSUPPORTED, "MBAR supports 1 to " + std::to_string(kMbarMaxRungs) + " rungs and at least one sample");
+  ME_HIP(e, err);
+  if (empty_rung >= 0)
+    return fail(e, ME_ERR_STATE, "rung " + std::to_string(empty_rung) + " of " + std::to_string(n_rungs) +
+                                     " has no sample with a finite energy: MBAR needs every rung sampled");
+  return ME_OK;
+}
+int mbar_check_temps(me_engine *e, const double *temps, int n, const char *what) {
+  for (int k = 0; k < n; ++k)
+    if (!(std::isfinite(temps[k]) && temps[k] > 0)) return fail(e, ME_ERR_INVALID, std::string(what) + " must be finite and > 0");
+  return ME_OK;
+}
+// the engine's store as an MBAR problem (ME_ERR_STATE when there is nothing to solve)
+int engine_samples(me_engine *e, MbarSamples &sm) {
+  if (e->n_rungs == 0) return fail(e, ME_ERR_STATE, "no temperature ladder: MBAR combines the rungs of me_set_temperature_ladder");
+  if (!e->esamp || e->esamp_rows == 0)
+    return fail(e, ME_ERR_STATE, "no recorded energy samples: me_energy_samples_enable, then me_energy_samples_record");
+  sm.energies = e->esamp;
+  sm.rungs = nullptr;
+  sm.n_samples = e->esamp_rows * e->n;
+  sm.n_chains = e->n;
+  sm.rung_chains = e->n / e->n_rungs;
+  return ME_OK;
+}
+// host samples of the engine-less forms on the device
+struct DeviceSamples {
+  double *energies = nullptr;
+  int *rungs = nullptr;
+  ~DeviceSamples() {
+    if (energies) (void)hipFree(energies);
+    if (rungs) (void)hipFree(rungs);
+  }
+};
+int upload_samples(int device_id, const double *energies, const int32_t *rungs, int64_t n_samples, const double *ladder_temps,
+                   int n_rungs, DeviceSamples &dev, MbarSamples &sm) {
+  if (!energies || !rungs || !ladder_temps) return fail(nullptr, ME_ERR_INVALID, "null pointer");
+  if (n_samples < 1 || n_rungs < 1) return fail(nullptr, ME_ERR_INVALID, "need n_samples >= 1 and n_rungs >= 1");
+  int rc = mbar_check_temps(nullptr, ladder_temps, n_rungs, "ladder temperatures");
+  if (rc) return rc;
+  for (int64_t i = 0; i < n_samples; ++i)
+    if (rungs[i] < 0 || rungs[i] >= n_rungs) return fail(nullptr, ME_ERR_INVALID, "rungs must lie in [0, n_rungs)");
+  ME_HIP(nullptr, hipSetDevice(device_id));
+  ME_HIP(nullptr, hipMalloc((void **)&dev.energies, sizeof(double) * (size_t)n_samples));
+  ME_HIP(nullptr, hipMalloc((void **)&dev.rungs, sizeof(int) * (size_t)n_samples));
+  ME_HIP(nullptr, hipMemcpy(dev.energies, energies, sizeof(double) * (size_t)n_samples, hipMemcpyHostToDevice));
+  ME_HIP(nullptr, hipMemcpy(dev.rungs, rungs, sizeof(int) * (size_t)n_samples, hipMemcpyHostToDevice));
+  sm.energies = dev.energies;
+  sm.rungs = dev.rungs;
+  sm.n_samples = n_samples;
+  sm.n_chains = sm.rung_chains = 1;
+  return ME_OK;
+}
+int solve_common(me_engine *e, const MbarSamples &sm, const double *ladder_temps, int n_rungs, double tolerance, int max_iterations,
+                 double *f_out, int32_t *iterations, double *residual, int64_t *n_used_out, hipStream_t stream) {
+  if (!f_out) return fail(e, ME_ERR_INVALID, "f_out missing");
+  if (!(tolerance > 0) || max_iterations < 1) return fail(e, ME_ERR_INVALID, "need tolerance > 0 and max_iterations >= 1");
+  std::vector<long long> used((size_t)std::max(n_rungs, 1));
+  int its = 0, empty = -1;
+  double res = 0.0;
+  const hipError_t err = mbar_solve(sm, ladder_temps, n_rungs, tolerance, max_iterations, f_out, &its, &res, used.data(), &empty, stream);
+  if (err == hipSuccess && n_used_out)
+    for (int k = 0; k < n_rungs; ++k) n_used_out[k] = used[k];
+  const int rc = mbar_check_common(e, n_rungs, empty, err);
+  if (rc) return rc;
+  if (iterations) *iterations = its;
+  if (residual) *residual = res;
+  return ME_OK;
+}
+int reweight_common(me_engine *e, const MbarSamples &sm, const double *ladder_temps, int n_rungs, const double *f, const double *temps,
+                    int n, double *ln_z, double *mean_e, double *var_e, double *neff_fraction, hipStream_t stream) {
+  if (!f || !temps || n < 1) return fail(e, ME_ERR_INVALID, "f and at least one target temperature are needed");
+  int rc = mbar_check_temps(e, temps, n, "target temperatures");
+  if (rc) return rc;
+  for (int k = 0; k < n_rungs; ++k)
+    if (!std::isfinite(f[k])) return fail(e, ME_ERR_INVALID, "f must be finite");
+  int empty = -1;
+  const hipError_t err = mbar_reweight(sm, ladder_temps, n_rungs, f, temps, n, ln_z, mean_e, var_e, neff_fraction, &empty, stream);
+  return mbar_check_common(e, n_rungs, empty, err);
+}
+}  // namespace
+
+int me_energy_samples_enable(me_engine *e, int64_t capacity_records) {
+  if (!e) return ME_ERR_INVALID;
+  if (capacity_records < 0) return fail(e, ME_ERR_INVALID, "capacity_records must be >= 0");
+  if (e->stale_total)
+    return fail(e, ME_ERR_UNSUPPORTED, "energy samples are not available with ME_FLAG_REFERENCE_ENERGY_LEDGERS: its two ledgers "
+                                       "make the energy of a chain ambiguous");
+  ME_HIP(e, hipSetDevice(e->device));
+  ME_HIP(e, hipStreamSynchronize(e->stream));       // a record in flight writes the field
+  if (e->esamp) (void)hipFree(e->esamp);
+  e->esamp = nullptr;
+  e->esamp_capacity = e->esamp_rows = 0;
+  if (capacity_records == 0) return ME_OK;
+  ME_HIP(e, hipMalloc((void **)&e->esamp, (size_t)capacity_records * (size_t)e->n * sizeof(double)));
+  e->esamp_capacity = capacity_records;
+  return ME_OK;
+}
+
+int me_energy_samples_record(me_engine *e) {
+  if (!e) return ME_ERR_INVALID;
+  if (!e->esamp) return fail(e, ME_ERR_STATE, "energy samples are not enabled: call me_energy_samples_enable first");
+  if (e->esamp_rows >= e->esamp_capacity)
+    return fail(e, ME_ERR_STATE, "the energy sample store is full (" + std::to_string(e->esamp_capacity) + " records)");
+  ME_HIP(e, hipSetDevice(e->device));
+  ME_HIP(e, launch_energy_record(e->energy, e->n, e->n_terms, e->dtype, e->esamp + (size_t)e->esamp_rows * (size_t)e->n, e->stream));
+  e->esamp_rows += 1;
+  return ME_OK;
+}
+
+int me_energy_samples_count(me_engine *e, int64_t *records, int64_t *capacity) {
+  if (!e) return ME_ERR_INVALID;
+  if (records) *records = e->esamp_rows;
+  if (capacity) *capacity = e->esamp_capacity;
+  return ME_OK;
+}
+
+int me_energy_samples_get(me_engine *e, int64_t record_begin, int64_t n_records, double *dst) {
+  if (!e || (!dst && n_records > 0)) return ME_ERR_INVALID;
+  if (record_begin < 0 || n_records < 0 || record_begin + n_records > e->esamp_rows)
+    return fail(e, ME_ERR_INVALID, "record range outside the recorded samples");
+  if (n_records == 0) return ME_OK;
+  ME_HIP(e, hipSetDevice(e->device));
+  ME_HIP(e, hipMemcpyAsync(dst, e->esamp + (size_t)record_begin * (size_t)e->n, (size_t)n_records * (size_t)e->n * sizeof(double),
+                           hipMemcpyDeviceToHost, e->stream));
+  ME_HIP(e, hipStreamSynchronize(e->stream));
+  return ME_OK;
+}
+
+int me_energy_samples_set(me_engine *e, int64_t n_records, const double *src) {
+  if (!e || (!src && n_records > 0)) return ME_ERR_INVALID;
+  if (!e->esamp) return fail(e, ME_ERR_STATE, "energy samples are not enabled: call me_energy_samples_enable first");
+  if (n_records < 0 || n_records > e->esamp_capacity) return fail(e, ME_ERR_INVALID, "n_records must lie in [0, capacity]");
+  ME_HIP(e, hipSetDevice(e->device));
+  if (n_records > 0) {
+    ME_HIP(e, hipMemcpyAsync(e->esamp, src, (size_t)n_records * (size_t)e->n * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    ME_HIP(e, hipStreamSynchronize(e->stream));
+  }
+  e->esamp_rows = n_records;
+  return ME_OK;
+}
+
+int me_mbar_solve(me_engine *e, double tolerance, int32_t max_iterations, double *f_out, int32_t *iterations, double *residual,
+                  int64_t *n_used_out) {
+  if (!e) return ME_ERR_INVALID;
+  MbarSamples sm;
+  int rc = engine_samples(e, sm);
+  if (rc) return rc;
+  ME_HIP(e, hipSetDevice(e->device));
+  return solve_common(e, sm, e->ladder_temps.data(), e->n_rungs, tolerance, max_iterations, f_out, iterations, residual, n_used_out,
+                      e->stream);
+}
+
+int me_mbar_reweight(me_engine *e, const double *f, const double *temps, int32_t n, double *ln_z, double *mean_e, double *var_e,
+                     double *neff_fraction) {
+  if (!e) return ME_ERR_INVALID;
+  MbarSamples sm;
+  int rc = engine_samples(e, sm);
+  if (rc) return rc;
+  ME_HIP(e, hipSetDevice(e->device));
+  return reweight_common(e, sm, e->ladder_temps.data(), e->n_rungs, f, temps, n, ln_z, mean_e, var_e, neff_fraction, e->stream);
+}
+
+int me_mbar_solve_samples(int32_t device_id, const double *energies, const int32_t *rungs, int64_t n_samples,
+                          const double *ladder_temps, int32_t n_rungs, double tolerance, int32_t max_iterations, double *f_out,
+                          int32_t *iterations, double *residual, int64_t *n_used_out) {
+  DeviceSamples dev;
+  MbarSamples sm;
+  int rc = upload_samples(device_id, energies, rungs, n_samples, ladder_temps, n_rungs, dev, sm);
+  if (rc) return rc;
+  rc = solve_common(nullptr, sm, ladder_temps, n_rungs, tolerance, max_iterations, f_out, iterations, residual, n_used_out, nullptr);
+  (void)hipDeviceSynchronize();
+  return rc;
+}
+
+int me_mbar_reweight_samples(int32_t device_id, const double *energies, const int32_t *rungs, int64_t n_samples,
+                             const double *ladder_temps, int32_t n_rungs, const double *f, const double *temps, int32_t n,
+                             double *ln_z, double *mean_e, double *var_e, double *neff_fraction) {
+  DeviceSamples dev;
+  MbarSamples sm;
+  int rc = upload_samples(device_id, energies, rungs, n_samples, ladder_temps, n_rungs, dev, sm);
+  if (rc) return rc;
+  rc = reweight_common(nullptr, sm, ladder_temps, n_rungs, f, temps, n, ln_z, mean_e, var_e, neff_fraction, nullptr);
+  (void)hipDeviceSynchronize();
+  return rc;
 }
 
 int me_last_error(me_engine *e, char *buf, size_t buf_bytes) {

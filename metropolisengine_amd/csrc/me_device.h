@@ -192,6 +192,15 @@ struct Field {
   }
 };
 
+// The energy of one chain: its ledger rows added in row order in the device dtype (chain_off = chain index * sizeof(R)).
+// The one definition behind replica swaps, population weights and recorded energy samples.
+template <typename R>
+__device__ __forceinline__ R chain_energy(const Field<R> &fe, unsigned int chain_off, int n_terms) {
+  R e = fe.load(0, chain_off);
+  for (int t = 1; t < n_terms; ++t) e = e + fe.load(t, chain_off);
+  return e;
+}
+
 // The packed per-chain covariance / factor fields are TILE-major: [tile of 64 chains][P entries][64 lanes], i.e. entry k of
 // chain c sits at ((c >> 6) * P + k) * 64 + (c & 63).  A wavefront's whole matrix is then ONE contiguous run of P x 256
 // bytes (34 KiB at 16 real parameters in float32) instead of P rows that lie a whole field row (4 MiB at 2^20 chains)

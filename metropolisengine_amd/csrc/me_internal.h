@@ -192,6 +192,25 @@ hipError_t launch_population_resample(const PopulationLaunch &launch, int dtype,
 hipError_t launch_population_init_families(long long *families, long long n, unsigned long long chain_offset,
                                            hipStream_t stream);
 
+// Energy samples and MBAR (me_mbar.hip).
+// dst[c] = (double)(sum of chain c's ledger rows in row order in the device dtype), c < n
+hipError_t launch_energy_record(const void *energy, long long n, int n_terms, int dtype, double *dst, hipStream_t stream);
+constexpr int kMbarMaxRungs = 64;
+// The samples of one MBAR problem, all in device memory.  rungs != nullptr: the rung of sample i is rungs[i]; otherwise
+// sample i is slot i % n_chains of an engine and its rung is (i % n_chains) / rung_chains.
+struct MbarSamples {
+  const double *energies;
+  const int *rungs;
+  long long n_samples, n_chains, rung_chains;
+};
+// Both wait for the stream and write host arrays.  *empty_rung = the first rung without a finite sample (nothing else is
+// computed then), or -1.  mbar_solve: f[K], n_used[K].  mbar_reweight: any of the four outputs may be nullptr.
+hipError_t mbar_solve(const MbarSamples &samples, const double *ladder_temps, int n_rungs, double tolerance, int max_iterations,
+                      double *f, int *iterations, double *residual, long long *n_used, int *empty_rung, hipStream_t stream);
+hipError_t mbar_reweight(const MbarSamples &samples, const double *ladder_temps, int n_rungs, const double *f, const double *temps,
+                         int n_temps, double *ln_z, double *mean_e, double *var_e, double *neff_fraction, int *empty_rung,
+                         hipStream_t stream);
+
 // blocks launched for n chains (one lane per chain, grid-stride beyond `requested` blocks when requested > 0)
 inline int grid_for(long long n, int requested, int threads = kStepThreads) {
   long long blocks = (n + threads - 1) / threads;

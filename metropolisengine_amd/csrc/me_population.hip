@@ -60,8 +60,7 @@ __device__ __forceinline__ double chain_log_weight(const Field<R> &fe, long long
   valid = false;
   if (c >= n) return 0.0;
   const unsigned int off = (unsigned int)c * (unsigned int)sizeof(R);
-  R e = fe.load(0, off);
-  for (int t = 1; t < n_terms; ++t) e = e + fe.load(t, off);
+  const R e = chain_energy(fe, off, n_terms);
   const double l = neg_dbeta * (double)e;
   valid = isfinite(l);
   return l;

@@ -63,11 +63,7 @@ __device__ __forceinline__ bool swap_pair(const SwapArgs<R> &s, const Field<R> &
   using N_ = Num<R>;
   const long long a = (long long)k * s.rung_chains + j, b = a + s.rung_chains;
   const unsigned int ea_off = (unsigned int)a * (unsigned int)sizeof(R), eb_off = (unsigned int)b * (unsigned int)sizeof(R);
-  R ea = fe.load(0, ea_off), eb = fe.load(0, eb_off);
-  for (int t = 1; t < s.n_terms; ++t) {
-    ea = ea + fe.load(t, ea_off);
-    eb = eb + fe.load(t, eb_off);
-  }
+  const R ea = chain_energy(fe, ea_off, s.n_terms), eb = chain_energy(fe, eb_off, s.n_terms);
   const unsigned long long gid = s.chain_offset + (unsigned long long)a;
   U4 ctr;
   ctr.x = (uint32_t)gid;

@@ -617,6 +617,86 @@ class MetropolisEngine:
             self._check(self._lib.me_pooled_moments_range(self._handle, k * m, m, _as_double_ptr(out[k]), size.value))
         return out
 
+    # ------------------------------------------------------------------ energy samples, MBAR free energies, reweighting
+    def record_energies(self, capacity):
+        """Allocate a device store for ``capacity`` records of every chain's energy (``me_energy_samples_enable``; float64,
+        ``capacity * n_chains * 8`` bytes) and forget the records so far; ``0`` frees it.  ``ValueError`` for a negative
+        capacity, ``NotImplementedError`` with ``reference_energy_ledgers=True``.
+
+        The samples are NOT part of :meth:`state_dict` (they can be hundreds of megabytes): a run is resumed with
+        :meth:`energy_samples` / :meth:`set_energy_samples`.  :meth:`set_temperatures` empties the store, because a sample's
+        temperature is the rung of its slot."""
+        capacity = int(capacity)
+        if capacity < 0:
+            raise ValueError("capacity must be >= 0")
+        self._check(self._lib.me_energy_samples_enable(self._handle, capacity))
+
+    def record_energy(self):
+        """Append one record: the energy of every chain now, the ledger rows summed in row order in the device dtype
+        (``me_energy_samples_record``; one kernel, asynchronous like :meth:`step_all`).  Raises when the store was never
+        enabled or is full."""
+        self._check(self._lib.me_energy_samples_record(self._handle))
+
+    def _energy_records(self):
+        rows, cap = ctypes.c_int64(), ctypes.c_int64()
+        self._check(self._lib.me_energy_samples_count(self._handle, ctypes.byref(rows), ctypes.byref(cap)))
+        return rows.value, cap.value
+
+    @property
+    def n_energy_records(self):
+        return self._energy_records()[0]
+
+    def energy_samples(self):
+        """The recorded energies, ``(records, n_chains)`` float64; column ``c`` is slot ``c``, i.e. rung ``c // M``."""
+        rows = self.n_energy_records
+        out = np.empty((rows, self.n_chains), dtype=np.float64)
+        if rows:
+            self._check(self._lib.me_energy_samples_get(self._handle, 0, rows, _as_double_ptr(out)))
+        return out
+
+    def set_energy_samples(self, samples):
+        """Replace the records by ``samples`` (``(records, n_chains)``, at most the capacity of :meth:`record_energies`)."""
+        a = np.ascontiguousarray(samples, dtype=np.float64)
+        if a.ndim != 2 or a.shape[1] != self.n_chains:
+            raise ValueError("samples must be (records, n_chains = %d)" % self.n_chains)
+        self._check(self._lib.me_energy_samples_set(self._handle, a.shape[0], _as_double_ptr(a)))
+
+    def ladder_free_energies(self, tol=1e-10, max_iter=10000):
+        """MBAR over the recorded energies of a ladder engine (``me_mbar_solve``, on the device): ``{"f", "ln_z",
+        "iterations", "residual", "converged", "n_samples"}`` with ``f[k] = -ln Z(T_k) / Z(T_0)``, ``ln_z = -f``, the
+        iterations taken, the last largest change of an ``f[k]``, whether it met ``tol``, and the finite samples of every
+        rung (non-finite energies are skipped).  Bitwise reproducible.  ``ValueError`` unless ``tol > 0`` and ``max_iter >=
+        1``; raises without a ladder, without records, or when a rung has no finite sample."""
+        from .statistics import validate_mbar_solve, _solve_result
+        tol, max_iter = validate_mbar_solve(tol, max_iter)
+        k = ctypes.c_int32()
+        self._check(self._lib.me_temperature_ladder(self._handle, None, 0, ctypes.byref(k)))
+        f = np.zeros(max(k.value, 1))
+        n_used = np.zeros(max(k.value, 1), dtype=np.int64)
+        its, res = ctypes.c_int32(), ctypes.c_double()
+        self._check(self._lib.me_mbar_solve(self._handle, tol, max_iter, _as_double_ptr(f), ctypes.byref(its), ctypes.byref(res),
+                                            n_used.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        return _solve_result(f, its.value, res.value, n_used, tol)
+
+    def reweight(self, temps, f=None):
+        """The ladder's samples reweighted to each temperature of ``temps`` (``me_mbar_reweight``): ``{"temps", "ln_z",
+        "energy_mean", "energy_var", "heat_capacity", "neff_fraction"}`` -- ``ln Z(T) / Z(T_0)``, the mean and variance of
+        the energy at ``T``, ``energy_var / T^2`` and the effective fraction of the samples behind the estimate.  ``f``: the
+        free energies of :meth:`ladder_free_energies` (solved with the defaults when ``None``).  ``ValueError`` for empty,
+        non-finite or non-positive ``temps``."""
+        from .statistics import validate_mbar_temps, _reweight_result
+        temps = validate_mbar_temps(temps)
+        if f is None:
+            f = self.ladder_free_energies()["f"]
+        f = np.ascontiguousarray(f, dtype=np.float64)
+        ladder = self.temperatures
+        if ladder is not None and f.shape != ladder.shape:
+            raise ValueError("f must hold one free energy per rung")
+        out = [np.zeros(temps.size) for _ in range(4)]
+        self._check(self._lib.me_mbar_reweight(self._handle, _as_double_ptr(f), _as_double_ptr(temps), temps.size,
+                                               *[_as_double_ptr(o) for o in out]))
+        return _reweight_result(temps, *out)
+
     # ------------------------------------------------------------------ scalar temperature and population annealing
     def set_temp(self, temp):
         """Change the scalar temperature of the running engine (``me_set_temperature``); the next step uses it, so a schedule

@@ -76,6 +76,98 @@ def detect_equilibration_batch(series, fast=True, nskip=1, device=0):
     return t0, g, neff
 
 
+# ---------------------------------------------------------------------------------------------- MBAR over a ladder
+# (no reference counterpart; the reference reaches for the same library family, pymbar, in its post-processing)
+MBAR_MAX_RUNGS = 64
+
+
+def validate_mbar_solve(tol, max_iter):
+    """``(tol, max_iter)`` of an MBAR solve as ``(float, int)``; ``ValueError`` unless ``tol > 0`` (and finite) and
+    ``max_iter >= 1``.  Runs before the library is touched."""
+    tol = float(tol)
+    if not (np.isfinite(tol) and tol > 0):
+        raise ValueError("tol must be finite and > 0")
+    if int(max_iter) < 1:
+        raise ValueError("max_iter must be >= 1")
+    return tol, int(max_iter)
+
+
+def validate_mbar_temps(temps, what="temps"):
+    """Temperatures as a contiguous 1-D float64 array: non-empty, finite and > 0 (``ValueError`` otherwise)."""
+    t = np.ascontiguousarray(np.atleast_1d(np.asarray(temps, dtype=np.float64)))
+    if t.ndim != 1 or t.size < 1:
+        raise ValueError("%s must be a non-empty 1-D sequence" % what)
+    if not np.all(np.isfinite(t)) or not np.all(t > 0):
+        raise ValueError("%s must be finite and > 0" % what)
+    return t
+
+
+def validate_mbar_samples(energies, rungs, temps):
+    """``(energies float64, rungs int32, temps float64)`` of the engine-less MBAR forms, flattened and checked: equal
+    lengths, at least one sample, ``0 <= rung < len(temps) <= 64``.  Energies may be non-finite (they are skipped)."""
+    t = validate_mbar_temps(temps, "temps")
+    if t.size > MBAR_MAX_RUNGS:
+        raise ValueError("MBAR supports at most %d rungs" % MBAR_MAX_RUNGS)
+    e = np.ascontiguousarray(np.asarray(energies, dtype=np.float64).ravel())
+    r = np.asarray(rungs).ravel()
+    if e.size < 1 or r.size != e.size:
+        raise ValueError("energies and rungs must have the same, non-zero, number of entries")
+    if r.dtype.kind not in "iu":
+        raise ValueError("rungs must be integers")
+    if r.min() < 0 or r.max() >= t.size:
+        raise ValueError("rungs must lie in [0, %d)" % t.size)
+    return e, np.ascontiguousarray(r, dtype=np.int32), t
+
+
+def _solve_result(f, iterations, residual, n_used, tol):
+    return {"f": f, "ln_z": -f, "iterations": int(iterations), "residual": float(residual),
+            "converged": bool(residual <= tol), "n_samples": n_used}
+
+
+def _reweight_result(temps, ln_z, mean, var, neff):
+    return {"temps": temps, "ln_z": ln_z, "energy_mean": mean, "energy_var": var, "heat_capacity": var / (temps * temps),
+            "neff_fraction": neff}
+
+
+def mbar_free_energies(energies, rungs, temps, tol=1e-10, max_iter=10000, device=0):
+    """MBAR free energies of a temperature ladder from samples on the host (``me_mbar_solve_samples``; the engine form is
+    ``MetropolisEngine.ladder_free_energies``).  ``energies[i]`` was sampled at ``temps[rungs[i]]``.  Returns
+    ``{"f", "ln_z", "iterations", "residual", "converged", "n_samples"}``: ``f[k] = -ln Z(T_k) / Z(T_0)``, ``ln_z = -f``,
+    ``n_samples[k]`` the finite energies of rung ``k`` (the others are skipped).  For samples gathered from several GPU
+    shards and for subsets of a run; a rung without a finite sample raises."""
+    import ctypes
+    from . import _capi
+    tol, max_iter = validate_mbar_solve(tol, max_iter)
+    e, r, t = validate_mbar_samples(energies, rungs, temps)
+    f = np.zeros(t.size)
+    n_used = np.zeros(t.size, dtype=np.int64)
+    its, res = ctypes.c_int32(), ctypes.c_double()
+    dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)
+    _capi.check(_capi.load().me_mbar_solve_samples(
+        int(device), e.ctypes.data_as(dp), r.ctypes.data_as(ip), e.size, t.ctypes.data_as(dp), t.size, tol, max_iter,
+        f.ctypes.data_as(dp), ctypes.byref(its), ctypes.byref(res), n_used.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+    return _solve_result(f, its.value, res.value, n_used, tol)
+
+
+def mbar_reweight(energies, rungs, temps, f, targets, device=0):
+    """Reweight the samples of a ladder (``temps``, free energies ``f`` of :func:`mbar_free_energies`) to the temperatures
+    ``targets`` (``me_mbar_reweight_samples``).  Returns ``{"temps", "ln_z", "energy_mean", "energy_var", "heat_capacity",
+    "neff_fraction"}``: ``ln_z = ln Z(T) / Z(T_0)``, ``heat_capacity = energy_var / T^2``."""
+    import ctypes
+    from . import _capi
+    e, r, t = validate_mbar_samples(energies, rungs, temps)
+    targets = validate_mbar_temps(targets, "targets")
+    f = np.ascontiguousarray(f, dtype=np.float64)
+    if f.shape != t.shape or not np.all(np.isfinite(f)):
+        raise ValueError("f must hold one finite free energy per rung")
+    out = [np.zeros(targets.size) for _ in range(4)]
+    dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)
+    _capi.check(_capi.load().me_mbar_reweight_samples(
+        int(device), e.ctypes.data_as(dp), r.ctypes.data_as(ip), e.size, t.ctypes.data_as(dp), t.size, f.ctypes.data_as(dp),
+        targets.ctypes.data_as(dp), targets.size, *[o.ctypes.data_as(dp) for o in out]))
+    return _reweight_result(targets, *out)
+
+
 def get_equilibration_points(df, device=None):
     """Per column ``[t0, g, Neff_max]``; constant columns are skipped and complex columns split into ``_real`` /
     ``_imag`` (statistics.py:25-48).  With ``device`` set, all columns go to the GPU in one batch."""

@@ -1,0 +1,108 @@
+"""Timings of the MBAR solver and of the energy-sample record kernel (profiles/mbar_solve.txt).
+
+    python tools/bench_mbar.py [--log2-chains 15] [--records 1024] [--rungs 8 16 32] [--reference-log2 20]
+    python tools/bench_mbar.py --one-solve 16       (a single solve, for a kernel trace around it)
+
+Per ladder size K: synthetic energies of a 16-dimensional quadratic form (E / T Gamma(8) distributed) on T_k = 0.5 r^k with
+r chosen so that the ladder spans the same range for every K, injected with set_energy_samples; one warm-up solve, then a
+timed solve to tol = 1e-10.  Milliseconds per iteration = wall time of the solve / iterations (the solve includes its
+counting pass and one 16-byte read per batch of 16 iterations).  Beside it the numpy restatement's time per iteration.
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import metropolisengine_amd as me  # noqa: E402
+import mbar_reference as ref  # noqa: E402
+
+DIM = 16
+
+
+def ladder(k):
+    return 0.5 * (1.3 ** 7) ** (np.arange(k) / (k - 1.0))
+
+
+def loaded_engine(k, log2_chains, records, seed=1):
+    n = 1 << log2_chains
+    temps = ladder(k)
+    eng = me.MetropolisEngine(me.IsoQuadratic(1.0), None, [0.1], None, n_chains=n, seed=3, dtype="f64", temperatures=temps)
+    eng.record_energies(records)
+    rng = np.random.default_rng(seed)
+    scale = np.repeat(temps, n // k)
+    eng.set_energy_samples(rng.gamma(DIM / 2.0, 1.0, size=(records, n)) * scale[None, :])
+    return eng, temps
+
+
+def time_solve(k, log2_chains, records):
+    eng, _ = loaded_engine(k, log2_chains, records)
+    eng.ladder_free_energies(tol=1e-10, max_iter=16)            # warm-up: allocations, code objects
+    t0 = time.perf_counter()
+    out = eng.ladder_free_energies(tol=1e-10)
+    wall = time.perf_counter() - t0
+    n = records << log2_chains
+    ms = 1e3 * wall / out["iterations"]
+    exps = n * k * (1 if k <= 16 else 2)
+    print("K = %2d: %d samples, %d iterations to residual %.2e (converged %s), %.3f ms per iteration, %.1f GB/s of samples, "
+          "%.3e exponentials/s (%d per sample and rung)"
+          % (k, n, out["iterations"], out["residual"], out["converged"], ms, 8e-9 * n / (1e-3 * ms), exps / (1e-3 * ms),
+             1 if k <= 16 else 2), flush=True)
+    t0 = time.perf_counter()
+    eng.reweight(np.geomspace(0.5, 3.0, 8), out["f"])
+    print("        reweighting to 8 temperatures: %.3f ms" % (1e3 * (time.perf_counter() - t0)), flush=True)
+
+
+def time_reference(k, log2_samples):
+    n = 1 << log2_samples
+    temps = ladder(k)
+    rng = np.random.default_rng(2)
+    rungs = np.repeat(np.arange(k), n // k)
+    e = rng.gamma(DIM / 2.0, 1.0, size=n) * temps[rungs]
+    f = np.zeros(k)
+    ref.iterate(e, rungs, temps, f)
+    t0 = time.perf_counter()
+    for _ in range(3):
+        f, _ = ref.iterate(e, rungs, temps, f)
+    ms = 1e3 * (time.perf_counter() - t0) / 3
+    print("K = %2d: numpy reference, %d samples: %.1f ms per iteration; scaled to 2^25 samples: %.0f ms"
+          % (k, n, ms, ms * (1 << 25) / n), flush=True)
+
+
+def time_record(log2_chains=20, dtype="f32", calls=50):
+    n = 1 << log2_chains
+    eng = me.MetropolisEngine(me.IsoQuadratic(1.0), None, [0.0] * DIM, None, temp=1.0, n_chains=n, seed=1, dtype=dtype)
+    eng.record_energies(calls + 1)
+    eng.record_energy()
+    eng.sync()
+    t0 = time.perf_counter()
+    for _ in range(calls):
+        eng.record_energy()
+    eng.sync()
+    us = 1e6 * (time.perf_counter() - t0) / calls
+    traffic = n * (8 + (4 if dtype == "f32" else 8))
+    print("me_energy_samples_record, %d chains, %s, one ledger row: %.1f us per call back to back, %d bytes of traffic: %.0f GB/s"
+          % (n, dtype, us, traffic, 1e-9 * traffic / (1e-6 * us)), flush=True)
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--log2-chains", type=int, default=15)
+    ap.add_argument("--records", type=int, default=1024)
+    ap.add_argument("--rungs", type=int, nargs="*", default=[8, 16, 32])
+    ap.add_argument("--reference-log2", type=int, default=20)
+    ap.add_argument("--one-solve", type=int, default=0)
+    cli = ap.parse_args()
+    if cli.one_solve:
+        time_solve(cli.one_solve, cli.log2_chains, cli.records)
+        sys.exit(0)
+    for k in cli.rungs:
+        time_solve(k, cli.log2_chains, cli.records)
+    for k in cli.rungs:
+        time_reference(k, cli.reference_log2)
+    for dtype in ("f32", "f64"):
+        time_record(dtype=dtype)
