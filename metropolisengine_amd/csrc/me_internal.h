@@ -1,5 +1,5 @@
-// Internal interface between the C-ABI layer (me_api.hip) and the per-dimension kernel sets
-// (me_kernels.hip compiled once per (n_real, n_complex)).  Not installed; the public ABI is
+// Internal interface between the host units (me_api.hip and the features' entry points, me_engine.h) and the
+// per-dimension kernel sets (me_kernels.hip compiled once per (n_real, n_complex)).  Not installed; the public ABI is
 // include/metropolis_engine.h.
 #pragma once
 
@@ -159,57 +159,8 @@ hipError_t launch_trace(const void *x, const void *energy, const void *width, lo
                         int width_rows, int dtype, long long n_traced, long long stride, double *out, hipStream_t stream,
                         bool tiled_state = false);
 // total[0] = sum of slots[0 .. n_slots)
-// Batched equilibration detection (me_statistics.hip; me_detect_equilibration in the public header).
-hipError_t launch_detect_equilibration(const double *series, long long n_series, long long length, int fast, int nskip,
-                                       double *scratch, long long *t0_out, double *g_out, double *neff_out,
-                                       hipStream_t stream);
-// One replica-exchange round (me_replica.hip): rung k pairs with rung k+1 for every k = round (mod 2); slot j of the two
-// rungs swaps x and its energy-ledger rows with the Metropolis probability of the two temperatures.  ladder: the step
-// kernels' (inv_temp, inv_temp_log2e) table; pair_counts[2 k], [2 k + 1]: attempted / accepted swaps of the pair (k, k+1), added to.
-hipError_t launch_replica_swap(void *x, void *energy, long long n, int d, int n_terms, bool tiled_state, int dtype,
-                               const void *ladder, int n_rungs, unsigned long long round, unsigned long long chain_offset,
-                               unsigned long long seed, unsigned long long *pair_counts, hipStream_t stream);
 hipError_t launch_sum_slots(const unsigned long long *slots, long long n_slots, unsigned long long *total,
                             hipStream_t stream);
-// One population-annealing stage (me_population.hip): weights, scan, ancestors, and the gather of x, the ledger rows and
-// the family ids of the ancestors into x_out / energy_out / families_out (the caller copies them back).
-struct PopulationLaunch {
-  const void *x, *energy;
-  void *x_out, *energy_out;
-  const long long *families;
-  long long *families_out;
-  unsigned int *ancestors;          // n entries
-  double *scratch;                  // population_scratch_doubles(n)
-  double *record;                   // this stage's (log_weight, neff_fraction, n_finite)
-  long long n;
-  int d, n_terms;
-  bool tiled;                       // tile-major x (KernelSet::tiled_state)
-  double neg_dbeta;                 // -(1/T_new - 1/T_old)
-  unsigned long long chain_offset, stage, seed;
-};
-size_t population_scratch_doubles(long long n);
-hipError_t launch_population_resample(const PopulationLaunch &launch, int dtype, hipStream_t stream);
-hipError_t launch_population_init_families(long long *families, long long n, unsigned long long chain_offset,
-                                           hipStream_t stream);
-
-// Energy samples and MBAR (me_mbar.hip).
-// dst[c] = (double)(sum of chain c's ledger rows in row order in the device dtype), c < n
-hipError_t launch_energy_record(const void *energy, long long n, int n_terms, int dtype, double *dst, hipStream_t stream);
-constexpr int kMbarMaxRungs = 64;
-// The samples of one MBAR problem, all in device memory.  rungs != nullptr: the rung of sample i is rungs[i]; otherwise
-// sample i is slot i % n_chains of an engine and its rung is (i % n_chains) / rung_chains.
-struct MbarSamples {
-  const double *energies;
-  const int *rungs;
-  long long n_samples, n_chains, rung_chains;
-};
-// Both wait for the stream and write host arrays.  *empty_rung = the first rung without a finite sample (nothing else is
-// computed then), or -1.  mbar_solve: f[K], n_used[K].  mbar_reweight: any of the four outputs may be nullptr.
-hipError_t mbar_solve(const MbarSamples &samples, const double *ladder_temps, int n_rungs, double tolerance, int max_iterations,
-                      double *f, int *iterations, double *residual, long long *n_used, int *empty_rung, hipStream_t stream);
-hipError_t mbar_reweight(const MbarSamples &samples, const double *ladder_temps, int n_rungs, const double *f, const double *temps,
-                         int n_temps, double *ln_z, double *mean_e, double *var_e, double *neff_fraction, int *empty_rung,
-                         hipStream_t stream);
 
 // blocks launched for n chains (one lane per chain, grid-stride beyond `requested` blocks when requested > 0)
 inline int grid_for(long long n, int requested, int threads = kStepThreads) {

@@ -39,6 +39,7 @@
 #include <vector>
 
 #include "me_device.h"
+#include "me_engine.h"
 #include "me_math64.h"
 
 namespace me {
@@ -53,7 +54,7 @@ constexpr int kMaxBlocks = 2048;                // about 8 blocks per CU; the gr
 constexpr int kUpdateThreads = 1024;
 constexpr int kBatch = 16;                      // iterations enqueued between two looks at the residual
 constexpr int kTargets = 8;                     // reweighting temperatures per pass over the samples
-constexpr int kK = kMbarMaxRungs;
+constexpr int kK = 64;                          // most rungs of one problem
 
 // device-side state of a solve: doubles [beta | c = ln N + f | ln N | N | f], then the control words
 constexpr int kBeta = 0, kC = kK, kLnN = 2 * kK, kN = 3 * kK, kF = 4 * kK, kTableDoubles = 5 * kK;
@@ -340,15 +341,20 @@ __global__ void __launch_bounds__(kThreads) k_mbar_reweight_finish(const Moments
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------
+// The samples of one MBAR problem, all in device memory.  rungs != nullptr: the rung of sample i is rungs[i]; otherwise
+// sample i is slot i % n_chains of an engine and its rung is (i % n_chains) / rung_chains.
+struct MbarSamples {
+  const double *energies;
+  const int *rungs;
+  long long n_samples, n_chains, rung_chains;
+};
+
+// device scratch of one solve / reweighting
 struct Work {
-  double *table = nullptr, *partials = nullptr, *inv_temps = nullptr, *out = nullptr;
-  Moments *moments = nullptr;
-  unsigned long long *counts = nullptr;
-  MbarControl *control = nullptr;
-  ~Work() {
-    for (void *p : {(void *)table, (void *)partials, (void *)inv_temps, (void *)out, (void *)moments, (void *)counts, (void *)control})
-      if (p) (void)hipFree(p);
-  }
+  DeviceBuffer table, partials, inv_temps, out;   // double
+  DeviceBuffer moments;                           // Moments
+  DeviceBuffer counts;                            // unsigned long long
+  DeviceBuffer control;                           // MbarControl
 };
 
 #define ME_MBAR_HIP(call)                 \
@@ -363,13 +369,13 @@ int blocks_of(long long n) { return (int)std::min<long long>(tiles_of(n), kMaxBl
 // N_k into host `counts`; *empty_rung = the first rung without a finite sample or -1
 hipError_t count_used(const MbarSamples &sm, int n_rungs, Work &w, std::vector<unsigned long long> &counts, int *empty_rung,
                       hipStream_t stream) {
-  ME_MBAR_HIP(hipMalloc((void **)&w.counts, kK * sizeof(unsigned long long)));
-  ME_MBAR_HIP(hipMemsetAsync(w.counts, 0, kK * sizeof(unsigned long long), stream));
+  ME_MBAR_HIP(w.counts.resize(kK * sizeof(unsigned long long)));
+  ME_MBAR_HIP(hipMemsetAsync(w.counts.get(), 0, w.counts.bytes(), stream));
   hipLaunchKernelGGL(k_mbar_count, dim3(blocks_of(sm.n_samples)), dim3(kThreads), 0, stream, sm.energies, sm.rungs, sm.n_samples,
-                     sm.n_chains, sm.rung_chains, n_rungs, w.counts);
+                     sm.n_chains, sm.rung_chains, n_rungs, w.counts.get<unsigned long long>());
   ME_MBAR_HIP(hipGetLastError());
   counts.assign(kK, 0);
-  ME_MBAR_HIP(hipMemcpyAsync(counts.data(), w.counts, kK * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+  ME_MBAR_HIP(hipMemcpyAsync(counts.data(), w.counts.get(), kK * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
   ME_MBAR_HIP(hipStreamSynchronize(stream));
   *empty_rung = -1;
   for (int k = n_rungs - 1; k >= 0; --k)
@@ -388,21 +394,14 @@ hipError_t upload_table(Work &w, const double *ladder_temps, int n_rungs, const 
     table[kF + k] = f ? f[k] : 0.0;
     table[kC + k] = table[kLnN + k] + table[kF + k];
   }
-  ME_MBAR_HIP(hipMalloc((void **)&w.table, kTableDoubles * sizeof(double)));
-  ME_MBAR_HIP(hipMemcpyAsync(w.table, table.data(), kTableDoubles * sizeof(double), hipMemcpyHostToDevice, stream));
+  ME_MBAR_HIP(w.table.resize(kTableDoubles * sizeof(double)));
+  ME_MBAR_HIP(hipMemcpyAsync(w.table.get(), table.data(), kTableDoubles * sizeof(double), hipMemcpyHostToDevice, stream));
   ME_MBAR_HIP(hipStreamSynchronize(stream));      // `table` leaves scope
   return hipSuccess;
 }
 
-}  // namespace
-
-hipError_t launch_energy_record(const void *energy, long long n, int n_terms, int dtype, double *dst, hipStream_t stream) {
-  const dim3 grid((unsigned)((n + kThreads - 1) / kThreads));
-  if (dtype == ME_F32) hipLaunchKernelGGL(k_energy_record<float>, grid, dim3(kThreads), 0, stream, (const float *)energy, n, n_terms, dst);
-  else hipLaunchKernelGGL(k_energy_record<double>, grid, dim3(kThreads), 0, stream, (const double *)energy, n, n_terms, dst);
-  return hipGetLastError();
-}
-
+// Both wait for the stream and write host arrays.  *empty_rung = the first rung without a finite sample (nothing else is
+// computed then), or -1.  mbar_solve: f[K], n_used[K].  mbar_reweight: any of the four outputs may be nullptr.
 hipError_t mbar_solve(const MbarSamples &sm, const double *ladder_temps, int n_rungs, double tolerance, int max_iterations,
                       double *f, int *iterations, double *residual, long long *n_used, int *empty_rung, hipStream_t stream) {
   if (n_rungs < 1 || n_rungs > kK || sm.n_samples < 1) return hipErrorInvalidValue;
@@ -414,23 +413,23 @@ hipError_t mbar_solve(const MbarSamples &sm, const double *ladder_temps, int n_r
   ME_MBAR_HIP(upload_table(w, ladder_temps, n_rungs, counts, nullptr, stream));
   const int n_blocks = blocks_of(sm.n_samples);
   const long long n_tiles = tiles_of(sm.n_samples);
-  ME_MBAR_HIP(hipMalloc((void **)&w.partials, (size_t)n_blocks * n_rungs * sizeof(double)));
-  ME_MBAR_HIP(hipMalloc((void **)&w.control, sizeof(MbarControl)));
-  ME_MBAR_HIP(hipMemsetAsync(w.control, 0, sizeof(MbarControl), stream));
+  ME_MBAR_HIP(w.partials.resize((size_t)n_blocks * n_rungs * sizeof(double)));
+  ME_MBAR_HIP(w.control.resize(sizeof(MbarControl)));
+  ME_MBAR_HIP(hipMemsetAsync(w.control.get(), 0, sizeof(MbarControl), stream));
   MbarControl c{0.0, 0, 0};
   while (c.iterations < max_iterations && !c.done) {
     const int batch = std::min(kBatch, max_iterations - c.iterations);
     for (int it = 0; it < batch; ++it) {
       hipLaunchKernelGGL(k_mbar_weights, dim3(n_blocks), dim3(kThreads), 0, stream, sm.energies, sm.n_samples, n_rungs,
-                         (const double *)w.table, (const MbarControl *)w.control, n_tiles, w.partials);
-      hipLaunchKernelGGL(k_mbar_update, dim3(1), dim3(kUpdateThreads), 0, stream, (const double *)w.partials, n_blocks, n_rungs,
-                         tolerance, w.table, w.control);
+                         w.table.get<const double>(), w.control.get<const MbarControl>(), n_tiles, w.partials.get<double>());
+      hipLaunchKernelGGL(k_mbar_update, dim3(1), dim3(kUpdateThreads), 0, stream, w.partials.get<const double>(), n_blocks, n_rungs,
+                         tolerance, w.table.get<double>(), w.control.get<MbarControl>());
     }
     ME_MBAR_HIP(hipGetLastError());
-    ME_MBAR_HIP(hipMemcpyAsync(&c, w.control, sizeof(MbarControl), hipMemcpyDeviceToHost, stream));
+    ME_MBAR_HIP(hipMemcpyAsync(&c, w.control.get(), sizeof(MbarControl), hipMemcpyDeviceToHost, stream));
     ME_MBAR_HIP(hipStreamSynchronize(stream));
   }
-  ME_MBAR_HIP(hipMemcpyAsync(f, w.table + kF, (size_t)n_rungs * sizeof(double), hipMemcpyDeviceToHost, stream));
+  ME_MBAR_HIP(hipMemcpyAsync(f, w.table.get<double>() + kF, (size_t)n_rungs * sizeof(double), hipMemcpyDeviceToHost, stream));
   ME_MBAR_HIP(hipStreamSynchronize(stream));
   *iterations = c.iterations;
   *residual = c.residual;
@@ -452,19 +451,19 @@ hipError_t mbar_reweight(const MbarSamples &sm, const double *ladder_temps, int 
   const long long n_tiles = tiles_of(sm.n_samples);
   std::vector<double> inv((size_t)n_temps), out(4 * (size_t)n_temps);
   for (int t = 0; t < n_temps; ++t) inv[t] = 1.0 / temps[t];
-  ME_MBAR_HIP(hipMalloc((void **)&w.inv_temps, inv.size() * sizeof(double)));
-  ME_MBAR_HIP(hipMalloc((void **)&w.out, out.size() * sizeof(double)));
-  ME_MBAR_HIP(hipMalloc((void **)&w.moments, (size_t)n_blocks * kTargets * sizeof(Moments)));
-  ME_MBAR_HIP(hipMemcpyAsync(w.inv_temps, inv.data(), inv.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+  ME_MBAR_HIP(w.inv_temps.resize(inv.size() * sizeof(double)));
+  ME_MBAR_HIP(w.out.resize(out.size() * sizeof(double)));
+  ME_MBAR_HIP(w.moments.resize((size_t)n_blocks * kTargets * sizeof(Moments)));
+  ME_MBAR_HIP(hipMemcpyAsync(w.inv_temps.get(), inv.data(), inv.size() * sizeof(double), hipMemcpyHostToDevice, stream));
   for (int t0 = 0; t0 < n_temps; t0 += kTargets) {
     const int nt = std::min(kTargets, n_temps - t0);
     hipLaunchKernelGGL(k_mbar_reweight, dim3(n_blocks), dim3(kThreads), 0, stream, sm.energies, sm.n_samples, n_rungs,
-                       (const double *)w.table, (const double *)(w.inv_temps + t0), nt, n_tiles, w.moments);
-    hipLaunchKernelGGL(k_mbar_reweight_finish, dim3(nt), dim3(kThreads), 0, stream, (const Moments *)w.moments, n_blocks, n_used,
-                       w.out + 4 * (size_t)t0);
+                       w.table.get<const double>(), w.inv_temps.get<const double>() + t0, nt, n_tiles, w.moments.get<Moments>());
+    hipLaunchKernelGGL(k_mbar_reweight_finish, dim3(nt), dim3(kThreads), 0, stream, w.moments.get<const Moments>(), n_blocks, n_used,
+                       w.out.get<double>() + 4 * (size_t)t0);
   }
   ME_MBAR_HIP(hipGetLastError());
-  ME_MBAR_HIP(hipMemcpyAsync(out.data(), w.out, out.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+  ME_MBAR_HIP(hipMemcpyAsync(out.data(), w.out.get(), out.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
   ME_MBAR_HIP(hipStreamSynchronize(stream));
   for (int t = 0; t < n_temps; ++t) {
     if (ln_z) ln_z[t] = out[4 * (size_t)t];
@@ -475,4 +474,192 @@ hipError_t mbar_reweight(const MbarSamples &sm, const double *ladder_temps, int 
   return hipSuccess;
 }
 
+// ---- entry points: energy samples, MBAR free energies and reweighting --------------------------------------------------
+int mbar_check_common(me_engine *e, int n_rungs, int empty_rung, hipError_t err) {
+  if (err == hipErrorInvalidValue)
+    return fail(e, ME_ERR_UNSUPPORTED, "MBAR supports 1 to " + std::to_string(kK) + " rungs and at least one sample");
+  ME_HIP(e, err);
+  if (empty_rung >= 0)
+    return fail(e, ME_ERR_STATE, "rung " + std::to_string(empty_rung) + " of " + std::to_string(n_rungs) +
+                                     " has no sample with a finite energy: MBAR needs every rung sampled");
+  return ME_OK;
+}
+int mbar_check_temps(me_engine *e, const double *temps, int n, const char *what) {
+  for (int k = 0; k < n; ++k)
+    if (!(std::isfinite(temps[k]) && temps[k] > 0)) return fail(e, ME_ERR_INVALID, std::string(what) + " must be finite and > 0");
+  return ME_OK;
+}
+// the engine's store as an MBAR problem (ME_ERR_STATE when there is nothing to solve)
+int engine_samples(me_engine *e, MbarSamples &sm) {
+  if (e->ladder.n_rungs == 0) return fail(e, ME_ERR_STATE, "no temperature ladder: MBAR combines the rungs of me_set_temperature_ladder");
+  if (!e->samples.data || e->samples.rows == 0)
+    return fail(e, ME_ERR_STATE, "no recorded energy samples: me_energy_samples_enable, then me_energy_samples_record");
+  sm.energies = e->samples.data.get<double>();
+  sm.rungs = nullptr;
+  sm.n_samples = e->samples.rows * e->n;
+  sm.n_chains = e->n;
+  sm.rung_chains = e->n / e->ladder.n_rungs;
+  return ME_OK;
+}
+// host samples of the engine-less forms on the device (`energies_dev`, `rungs_dev`: theirs for the length of the call)
+int upload_samples(int device_id, const double *energies, const int32_t *rungs, int64_t n_samples, const double *ladder_temps,
+                   int n_rungs, DeviceBuffer &energies_dev, DeviceBuffer &rungs_dev, MbarSamples &sm) {
+  if (!energies || !rungs || !ladder_temps) return fail(nullptr, ME_ERR_INVALID, "null pointer");
+  if (n_samples < 1 || n_rungs < 1) return fail(nullptr, ME_ERR_INVALID, "need n_samples >= 1 and n_rungs >= 1");
+  int rc = mbar_check_temps(nullptr, ladder_temps, n_rungs, "ladder temperatures");
+  if (rc) return rc;
+  for (int64_t i = 0; i < n_samples; ++i)
+    if (rungs[i] < 0 || rungs[i] >= n_rungs) return fail(nullptr, ME_ERR_INVALID, "rungs must lie in [0, n_rungs)");
+  ME_HIP(nullptr, hipSetDevice(device_id));
+  ME_HIP(nullptr, energies_dev.resize(sizeof(double) * (size_t)n_samples));
+  ME_HIP(nullptr, rungs_dev.resize(sizeof(int) * (size_t)n_samples));
+  ME_HIP(nullptr, hipMemcpy(energies_dev.get(), energies, energies_dev.bytes(), hipMemcpyHostToDevice));
+  ME_HIP(nullptr, hipMemcpy(rungs_dev.get(), rungs, rungs_dev.bytes(), hipMemcpyHostToDevice));
+  sm.energies = energies_dev.get<double>();
+  sm.rungs = rungs_dev.get<int>();
+  sm.n_samples = n_samples;
+  sm.n_chains = sm.rung_chains = 1;
+  return ME_OK;
+}
+int solve_common(me_engine *e, const MbarSamples &sm, const double *ladder_temps, int n_rungs, double tolerance, int max_iterations,
+                 double *f_out, int32_t *iterations, double *residual, int64_t *n_used_out, hipStream_t stream) {
+  if (!f_out) return fail(e, ME_ERR_INVALID, "f_out missing");
+  if (!(tolerance > 0) || max_iterations < 1) return fail(e, ME_ERR_INVALID, "need tolerance > 0 and max_iterations >= 1");
+  std::vector<long long> used((size_t)std::max(n_rungs, 1));
+  int its = 0, empty = -1;
+  double res = 0.0;
+  const hipError_t err = mbar_solve(sm, ladder_temps, n_rungs, tolerance, max_iterations, f_out, &its, &res, used.data(), &empty, stream);
+  if (err == hipSuccess && n_used_out)
+    for (int k = 0; k < n_rungs; ++k) n_used_out[k] = used[k];
+  const int rc = mbar_check_common(e, n_rungs, empty, err);
+  if (rc) return rc;
+  if (iterations) *iterations = its;
+  if (residual) *residual = res;
+  return ME_OK;
+}
+int reweight_common(me_engine *e, const MbarSamples &sm, const double *ladder_temps, int n_rungs, const double *f, const double *temps,
+                    int n, double *ln_z, double *mean_e, double *var_e, double *neff_fraction, hipStream_t stream) {
+  if (!f || !temps || n < 1) return fail(e, ME_ERR_INVALID, "f and at least one target temperature are needed");
+  int rc = mbar_check_temps(e, temps, n, "target temperatures");
+  if (rc) return rc;
+  for (int k = 0; k < n_rungs; ++k)
+    if (!std::isfinite(f[k])) return fail(e, ME_ERR_INVALID, "f must be finite");
+  int empty = -1;
+  const hipError_t err = mbar_reweight(sm, ladder_temps, n_rungs, f, temps, n, ln_z, mean_e, var_e, neff_fraction, &empty, stream);
+  return mbar_check_common(e, n_rungs, empty, err);
+}
+}  // namespace
 }  // namespace me
+
+using namespace me;
+
+extern "C" {
+
+int me_energy_samples_enable(me_engine *e, int64_t capacity_records) {
+  if (!e) return ME_ERR_INVALID;
+  if (capacity_records < 0) return fail(e, ME_ERR_INVALID, "capacity_records must be >= 0");
+  const int rc = refuse_stale_total(e, "energy samples are");
+  if (rc != ME_OK) return rc;
+  ME_HIP(e, hipSetDevice(e->device));
+  ME_HIP(e, hipStreamSynchronize(e->stream));       // a record in flight writes the field
+  e->samples = me_engine::Samples();
+  ME_HIP(e, e->samples.data.resize((size_t)capacity_records * (size_t)e->n * sizeof(double)));
+  e->samples.capacity = capacity_records;
+  return ME_OK;
+}
+
+int me_energy_samples_record(me_engine *e) {
+  if (!e) return ME_ERR_INVALID;
+  if (!e->samples.data) return fail(e, ME_ERR_STATE, "energy samples are not enabled: call me_energy_samples_enable first");
+  if (e->samples.rows >= e->samples.capacity)
+    return fail(e, ME_ERR_STATE, "the energy sample store is full (" + std::to_string(e->samples.capacity) + " records)");
+  ME_HIP(e, hipSetDevice(e->device));
+  // dst[c] = (double)(sum of chain c's ledger rows in row order in the device dtype), c < n
+  double *dst = e->samples.data.get<double>() + (size_t)e->samples.rows * (size_t)e->n;
+  const dim3 grid((unsigned)((e->n + kThreads - 1) / kThreads));
+  if (e->dtype == ME_F32)
+    hipLaunchKernelGGL(k_energy_record<float>, grid, dim3(kThreads), 0, e->stream, e->energy.get<const float>(), e->n, e->n_terms, dst);
+  else hipLaunchKernelGGL(k_energy_record<double>, grid, dim3(kThreads), 0, e->stream, e->energy.get<const double>(), e->n, e->n_terms, dst);
+  ME_HIP(e, hipGetLastError());
+  e->samples.rows += 1;
+  return ME_OK;
+}
+
+int me_energy_samples_count(me_engine *e, int64_t *records, int64_t *capacity) {
+  if (!e) return ME_ERR_INVALID;
+  if (records) *records = e->samples.rows;
+  if (capacity) *capacity = e->samples.capacity;
+  return ME_OK;
+}
+
+int me_energy_samples_get(me_engine *e, int64_t record_begin, int64_t n_records, double *dst) {
+  if (!e || (!dst && n_records > 0)) return ME_ERR_INVALID;
+  if (record_begin < 0 || n_records < 0 || record_begin + n_records > e->samples.rows)
+    return fail(e, ME_ERR_INVALID, "record range outside the recorded samples");
+  if (n_records == 0) return ME_OK;
+  ME_HIP(e, hipSetDevice(e->device));
+  ME_HIP(e, hipMemcpyAsync(dst, e->samples.data.get<double>() + (size_t)record_begin * (size_t)e->n, (size_t)n_records * (size_t)e->n * sizeof(double),
+                           hipMemcpyDeviceToHost, e->stream));
+  ME_HIP(e, hipStreamSynchronize(e->stream));
+  return ME_OK;
+}
+
+int me_energy_samples_set(me_engine *e, int64_t n_records, const double *src) {
+  if (!e || (!src && n_records > 0)) return ME_ERR_INVALID;
+  if (!e->samples.data) return fail(e, ME_ERR_STATE, "energy samples are not enabled: call me_energy_samples_enable first");
+  if (n_records < 0 || n_records > e->samples.capacity) return fail(e, ME_ERR_INVALID, "n_records must lie in [0, capacity]");
+  ME_HIP(e, hipSetDevice(e->device));
+  if (n_records > 0) {
+    ME_HIP(e, hipMemcpyAsync(e->samples.data.get(), src, (size_t)n_records * (size_t)e->n * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    ME_HIP(e, hipStreamSynchronize(e->stream));
+  }
+  e->samples.rows = n_records;
+  return ME_OK;
+}
+
+int me_mbar_solve(me_engine *e, double tolerance, int32_t max_iterations, double *f_out, int32_t *iterations, double *residual,
+                  int64_t *n_used_out) {
+  if (!e) return ME_ERR_INVALID;
+  MbarSamples sm;
+  int rc = engine_samples(e, sm);
+  if (rc) return rc;
+  ME_HIP(e, hipSetDevice(e->device));
+  return solve_common(e, sm, e->ladder.temps.data(), e->ladder.n_rungs, tolerance, max_iterations, f_out, iterations, residual, n_used_out,
+                      e->stream);
+}
+
+int me_mbar_reweight(me_engine *e, const double *f, const double *temps, int32_t n, double *ln_z, double *mean_e, double *var_e,
+                     double *neff_fraction) {
+  if (!e) return ME_ERR_INVALID;
+  MbarSamples sm;
+  int rc = engine_samples(e, sm);
+  if (rc) return rc;
+  ME_HIP(e, hipSetDevice(e->device));
+  return reweight_common(e, sm, e->ladder.temps.data(), e->ladder.n_rungs, f, temps, n, ln_z, mean_e, var_e, neff_fraction, e->stream);
+}
+
+int me_mbar_solve_samples(int32_t device_id, const double *energies, const int32_t *rungs, int64_t n_samples,
+                          const double *ladder_temps, int32_t n_rungs, double tolerance, int32_t max_iterations, double *f_out,
+                          int32_t *iterations, double *residual, int64_t *n_used_out) {
+  DeviceBuffer energies_dev, rungs_dev;
+  MbarSamples sm;
+  int rc = upload_samples(device_id, energies, rungs, n_samples, ladder_temps, n_rungs, energies_dev, rungs_dev, sm);
+  if (rc) return rc;
+  rc = solve_common(nullptr, sm, ladder_temps, n_rungs, tolerance, max_iterations, f_out, iterations, residual, n_used_out, nullptr);
+  (void)hipDeviceSynchronize();
+  return rc;
+}
+
+int me_mbar_reweight_samples(int32_t device_id, const double *energies, const int32_t *rungs, int64_t n_samples,
+                             const double *ladder_temps, int32_t n_rungs, const double *f, const double *temps, int32_t n,
+                             double *ln_z, double *mean_e, double *var_e, double *neff_fraction) {
+  DeviceBuffer energies_dev, rungs_dev;
+  MbarSamples sm;
+  int rc = upload_samples(device_id, energies, rungs, n_samples, ladder_temps, n_rungs, energies_dev, rungs_dev, sm);
+  if (rc) return rc;
+  rc = reweight_common(nullptr, sm, ladder_temps, n_rungs, f, temps, n, ln_z, mean_e, var_e, neff_fraction, nullptr);
+  (void)hipDeviceSynchronize();
+  return rc;
+}
+
+}  // extern "C"

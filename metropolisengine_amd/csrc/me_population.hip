@@ -30,11 +30,14 @@
 // kPopItems energies per thread stay in registers between the max and the sum), k_pop_finalize (one block), k_pop_scan_
 // ancestors (scatters a_j into the engine-owned ancestor array; a chain's run of more than kSerialSlots slots is written by
 // its whole wavefront), k_pop_gather (one lane per slot: x, the ledger rows and
-// the family id of a_j into engine-owned scratch, eight rows in flight).  me_api.hip then copies the scratch back into x,
+// the family id of a_j into engine-owned scratch, eight rows in flight).  me_population_resample then copies the scratch back into x,
 // the ledger and the family array: the x / energy pointers themselves never change (a captured graph holds them).
 #include <algorithm>
+#include <cmath>
+#include <vector>
 
 #include "me_device.h"
+#include "me_engine.h"
 
 namespace me {
 namespace {
@@ -347,44 +350,192 @@ __global__ void __launch_bounds__(kPopThreads) k_pop_init_families(long long *fa
   if (j < n) fam[j] = (long long)(chain_offset + (unsigned long long)j);
 }
 
+// One stage on the engine's stream: weights, scan, ancestors, and the gather of x, the ledger rows and the family ids of
+// the ancestors into the engine's scratch (the caller copies them back).  neg_dbeta = -(1/T_new - 1/T_old).
 template <typename R>
-hipError_t launch(const PopulationLaunch &L, hipStream_t stream) {
-  const int n_blocks = (int)((L.n + kPopChunk - 1) / kPopChunk);
-  const unsigned slot_blocks = (unsigned)((L.n + kPopThreads - 1) / kPopThreads);
-  double *partials = L.scratch, *factors = partials + 4 * (size_t)n_blocks, *offsets = factors + n_blocks;
+hipError_t launch(me_engine *e, double neg_dbeta) {
+  me_engine::Population &pop = e->population;
+  const long long n = e->n;
+  hipStream_t stream = e->stream;
+  const int n_blocks = (int)((n + kPopChunk - 1) / kPopChunk);
+  const unsigned slot_blocks = (unsigned)((n + kPopThreads - 1) / kPopThreads);
+  double *partials = pop.scratch.get<double>(), *factors = partials + 4 * (size_t)n_blocks, *offsets = factors + n_blocks;
   PopParams *params = (PopParams *)(offsets + n_blocks + 1);
-  hipLaunchKernelGGL(k_pop_weights<R>, dim3(n_blocks), dim3(kPopThreads), 0, stream, (const R *)L.energy, L.n, L.n_terms,
-                     L.neg_dbeta, partials);
-  hipLaunchKernelGGL(k_pop_finalize, dim3(1), dim3(kFinalThreads), 0, stream, (const double *)partials, n_blocks, L.n,
-                     L.chain_offset, L.stage, (uint32_t)L.seed, (uint32_t)(L.seed >> 32), factors, offsets, params, L.record);
-  hipLaunchKernelGGL(k_pop_scan_ancestors<R>, dim3(n_blocks), dim3(kPopThreads), 0, stream, (const R *)L.energy, L.n,
-                     L.n_terms, L.neg_dbeta, (const double *)partials, (const double *)factors, (const double *)offsets,
-                     (const PopParams *)params, L.ancestors);
-  hipLaunchKernelGGL(k_pop_gather<R>, dim3(slot_blocks), dim3(kPopThreads), 0, stream, (const R *)L.x, (const R *)L.energy,
-                     (const long long *)L.families, (R *)L.x_out, (R *)L.energy_out, L.families_out, L.n, L.d, L.n_terms,
-                     L.tiled ? 1 : 0, (const unsigned int *)L.ancestors, (const PopParams *)params);
+  double *record = pop.records.get<double>() + 3 * (size_t)pop.stages;     // this stage's (log_weight, neff_fraction, n_finite)
+  hipLaunchKernelGGL(k_pop_weights<R>, dim3(n_blocks), dim3(kPopThreads), 0, stream, e->energy.get<const R>(), n, e->n_terms,
+                     neg_dbeta, partials);
+  hipLaunchKernelGGL(k_pop_finalize, dim3(1), dim3(kFinalThreads), 0, stream, (const double *)partials, n_blocks, n,
+                     e->chain_offset, pop.stages, (uint32_t)e->seed, (uint32_t)(e->seed >> 32), factors, offsets, params, record);
+  hipLaunchKernelGGL(k_pop_scan_ancestors<R>, dim3(n_blocks), dim3(kPopThreads), 0, stream, e->energy.get<const R>(), n,
+                     e->n_terms, neg_dbeta, (const double *)partials, (const double *)factors, (const double *)offsets,
+                     (const PopParams *)params, pop.anc.get<unsigned int>());
+  hipLaunchKernelGGL(k_pop_gather<R>, dim3(slot_blocks), dim3(kPopThreads), 0, stream, e->x.get<const R>(), e->energy.get<const R>(),
+                     pop.fam.get<const long long>(), pop.x.get<R>(), pop.energy.get<R>(), pop.fam_out.get<long long>(), n, e->d,
+                     e->n_terms, e->x_tiled ? 1 : 0, pop.anc.get<const unsigned int>(), (const PopParams *)params);
   return hipGetLastError();
 }
-
-}  // namespace
 
 size_t population_scratch_doubles(long long n) {
   const long long n_blocks = (n + kPopChunk - 1) / kPopChunk;
   return (size_t)(4 * n_blocks + n_blocks + n_blocks + 1) + (sizeof(PopParams) + sizeof(double) - 1) / sizeof(double);
 }
 
-hipError_t launch_population_resample(const PopulationLaunch &L, int dtype, hipStream_t stream) {
-  if (L.n < 1 || L.n >= (1ll << 32) || !L.scratch || !L.record || !L.ancestors || !L.families || !L.families_out)
-    return hipErrorInvalidValue;
-  if (dtype == ME_F32) return launch<float>(L, stream);
-  return launch<double>(L, stream);
+// ---- entry points: the scalar temperature and population annealing -------------------------------------------------------
+int ensure_families(me_engine *e) {
+  me_engine::Population &pop = e->population;
+  if (pop.fam) return ME_OK;
+  ME_HIP(e, pop.fam.resize((size_t)e->n * sizeof(long long)));
+  hipLaunchKernelGGL(k_pop_init_families, dim3((unsigned)((e->n + kPopThreads - 1) / kPopThreads)), dim3(kPopThreads), 0, e->stream,
+                     pop.fam.get<long long>(), e->n, e->chain_offset);
+  ME_HIP(e, hipGetLastError());
+  return ME_OK;
+}
+// everything a stage writes besides x, the ledger and the families; the ledger scratch follows me_set_energy's row count
+int ensure_population_scratch(me_engine *e) {
+  me_engine::Population &pop = e->population;
+  const size_t energy_bytes = (size_t)e->n * (size_t)e->n_terms * e->esize;
+  if (pop.energy.bytes() < energy_bytes) {
+    if (pop.energy) ME_HIP(e, hipStreamSynchronize(e->stream));
+    ME_HIP(e, pop.energy.reserve(energy_bytes));
+  }
+  if (!pop.x) {
+    // same extent as x (tile-major: whole 64-chain tiles); it starts as a copy so that the padding lanes of a partial tile,
+    // which no gather writes, never carry uninitialised memory back into x
+    ME_HIP(e, pop.x.resize(e->x.bytes()));
+    ME_HIP(e, hipMemcpyAsync(pop.x.get(), e->x.get(), pop.x.bytes(), hipMemcpyDeviceToDevice, e->stream));
+  }
+  ME_HIP(e, pop.fam_out.resize((size_t)e->n * sizeof(long long)));
+  ME_HIP(e, pop.anc.resize((size_t)e->n * sizeof(unsigned int)));
+  ME_HIP(e, pop.scratch.resize(population_scratch_doubles(e->n) * sizeof(double)));
+  return ME_OK;
+}
+// room for `stages` stage records on the device (grown by doubling; a growth waits for the stream once)
+int ensure_records(me_engine *e, unsigned long long stages) {
+  me_engine::Population &pop = e->population;
+  if (stages <= pop.capacity) return ME_OK;
+  unsigned long long cap = std::max<unsigned long long>(256, pop.capacity);
+  while (cap < stages) cap *= 2;
+  DeviceBuffer grown;
+  ME_HIP(e, grown.resize((size_t)cap * 3 * sizeof(double)));
+  if (pop.records) {
+    ME_HIP(e, hipMemcpyAsync(grown.get(), pop.records.get(), (size_t)pop.stages * 3 * sizeof(double), hipMemcpyDeviceToDevice, e->stream));
+    ME_HIP(e, hipStreamSynchronize(e->stream));
+  }
+  pop.records = std::move(grown);
+  pop.capacity = cap;
+  return ME_OK;
+}
+int check_family_range(me_engine *e, int64_t chain_begin, int64_t n) {
+  if (chain_begin < 0 || n < 0 || chain_begin + n > e->n) return fail(e, ME_ERR_INVALID, "family range outside the engine's chains");
+  return ME_OK;
 }
 
-hipError_t launch_population_init_families(long long *families, long long n, unsigned long long chain_offset,
-                                           hipStream_t stream) {
-  hipLaunchKernelGGL(k_pop_init_families, dim3((unsigned)((n + kPopThreads - 1) / kPopThreads)), dim3(kPopThreads), 0, stream,
-                     families, n, chain_offset);
-  return hipGetLastError();
-}
-
+}  // namespace
 }  // namespace me
+
+using namespace me;
+
+extern "C" {
+
+int me_set_temperature(me_engine *e, double temp) {
+  if (!e) return ME_ERR_INVALID;
+  if (!(std::isfinite(temp) && temp >= 0)) return fail(e, ME_ERR_INVALID, "temp must be finite and >= 0");
+  if (e->ladder.n_rungs) return fail(e, ME_ERR_STATE, "this engine has a temperature ladder: its rungs carry the temperatures");
+  e->temp = temp;          // the next launch reads it (fill_step_launch)
+  return ME_OK;
+}
+
+int me_population_resample(me_engine *e, double new_temp) {
+  if (!e) return ME_ERR_INVALID;
+  if (!(std::isfinite(new_temp) && new_temp > 0)) return fail(e, ME_ERR_INVALID, "the new temperature must be finite and > 0");
+  int rc = refuse_stale_total(e, "population annealing is");
+  if (rc != ME_OK) return rc;
+  if (e->ladder.n_rungs) return fail(e, ME_ERR_STATE, "population annealing needs the scalar temp: this engine has a temperature ladder");
+  if (!(e->temp > 0)) return fail(e, ME_ERR_STATE, "population annealing cannot reweight from temp = 0: set a temperature first");
+  ME_HIP(e, hipSetDevice(e->device));
+  if ((rc = ensure_families(e)) || (rc = ensure_population_scratch(e)) || (rc = ensure_records(e, e->population.stages + 1))) return rc;
+  me_engine::Population &pop = e->population;
+  const double neg_dbeta = -(1.0 / new_temp - 1.0 / e->temp);
+  ME_HIP(e, e->dtype == ME_F32 ? launch<float>(e, neg_dbeta) : launch<double>(e, neg_dbeta));
+  // the scratch goes back into the engine's own buffers: their addresses stay what a captured graph recorded
+  ME_HIP(e, hipMemcpyAsync(e->x.get(), pop.x.get(), pop.x.bytes(), hipMemcpyDeviceToDevice, e->stream));
+  ME_HIP(e, hipMemcpyAsync(e->energy.get(), pop.energy.get(), (size_t)e->n * (size_t)e->n_terms * e->esize, hipMemcpyDeviceToDevice, e->stream));
+  ME_HIP(e, hipMemcpyAsync(pop.fam.get(), pop.fam_out.get(), (size_t)e->n * sizeof(long long), hipMemcpyDeviceToDevice, e->stream));
+  e->temp = new_temp;
+  e->population.temps.push_back(new_temp);
+  e->population.stages += 1;
+  return ME_OK;
+}
+
+int me_population_stats(me_engine *e, uint64_t *stages, double *stage_temps, double *log_weight, double *neff_fraction,
+                        int64_t *n_finite, int64_t capacity) {
+  if (!e) return ME_ERR_INVALID;
+  if (stages) *stages = e->population.stages;
+  if (!stage_temps && !log_weight && !neff_fraction && !n_finite) return ME_OK;
+  if (capacity < 0 || (unsigned long long)capacity < e->population.stages)
+    return fail(e, ME_ERR_INVALID, "the arrays must hold one entry per stage");
+  if (e->population.stages == 0) return ME_OK;
+  ME_HIP(e, hipSetDevice(e->device));
+  std::vector<double> rec(3 * (size_t)e->population.stages);
+  ME_HIP(e, hipMemcpyAsync(rec.data(), e->population.records.get(), rec.size() * sizeof(double), hipMemcpyDeviceToHost, e->stream));
+  ME_HIP(e, hipStreamSynchronize(e->stream));
+  for (size_t k = 0; k < e->population.stages; ++k) {
+    if (stage_temps) stage_temps[k] = e->population.temps[k];
+    if (log_weight) log_weight[k] = rec[3 * k];
+    if (neff_fraction) neff_fraction[k] = rec[3 * k + 1];
+    if (n_finite) n_finite[k] = (int64_t)rec[3 * k + 2];
+  }
+  return ME_OK;
+}
+
+int me_set_population_stats(me_engine *e, uint64_t stages, const double *stage_temps, const double *log_weight,
+                            const double *neff_fraction, const int64_t *n_finite) {
+  if (!e) return ME_ERR_INVALID;
+  if (stages > 0 && (!stage_temps || !log_weight || !neff_fraction || !n_finite))
+    return fail(e, ME_ERR_INVALID, "stage_temps / log_weight / neff_fraction / n_finite missing");
+  std::vector<double> rec(3 * (size_t)stages);
+  for (uint64_t k = 0; k < stages; ++k) {
+    if (!(std::isfinite(stage_temps[k]) && stage_temps[k] > 0)) return fail(e, ME_ERR_INVALID, "stage temperatures must be finite and > 0");
+    if (n_finite[k] < 0 || n_finite[k] > e->n) return fail(e, ME_ERR_INVALID, "n_finite must lie in [0, n_chains]");
+    rec[3 * k] = log_weight[k];
+    rec[3 * k + 1] = neff_fraction[k];
+    rec[3 * k + 2] = (double)n_finite[k];
+  }
+  ME_HIP(e, hipSetDevice(e->device));
+  int rc = ensure_records(e, std::max<uint64_t>(stages, 1));
+  if (rc) return rc;
+  if (stages > 0) {
+    ME_HIP(e, hipMemcpyAsync(e->population.records.get(), rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice, e->stream));
+    ME_HIP(e, hipStreamSynchronize(e->stream));
+  }
+  e->population.temps.assign(stage_temps, stage_temps + stages);
+  e->population.stages = stages;
+  return ME_OK;
+}
+
+int me_population_families(me_engine *e, int64_t chain_begin, int64_t n, int64_t *dst) {
+  if (!e || (!dst && n > 0)) return ME_ERR_INVALID;
+  int rc = check_family_range(e, chain_begin, n);
+  if (rc || n == 0) return rc;
+  if (!e->population.fam) {                  // never resampled: every chain is its own family, the global chain id
+    for (int64_t k = 0; k < n; ++k) dst[k] = (int64_t)(e->chain_offset + (unsigned long long)(chain_begin + k));
+    return ME_OK;
+  }
+  ME_HIP(e, hipSetDevice(e->device));
+  ME_HIP(e, hipMemcpyAsync(dst, e->population.fam.get<long long>() + chain_begin, (size_t)n * sizeof(long long), hipMemcpyDeviceToHost, e->stream));
+  ME_HIP(e, hipStreamSynchronize(e->stream));
+  return ME_OK;
+}
+
+int me_set_population_families(me_engine *e, int64_t chain_begin, int64_t n, const int64_t *src) {
+  if (!e || (!src && n > 0)) return ME_ERR_INVALID;
+  int rc = check_family_range(e, chain_begin, n);
+  if (rc || n == 0) return rc;
+  ME_HIP(e, hipSetDevice(e->device));
+  if ((rc = ensure_families(e))) return rc;
+  ME_HIP(e, hipMemcpyAsync(e->population.fam.get<long long>() + chain_begin, src, (size_t)n * sizeof(long long), hipMemcpyHostToDevice, e->stream));
+  ME_HIP(e, hipStreamSynchronize(e->stream));
+  return ME_OK;
+}
+
+}  // extern "C"

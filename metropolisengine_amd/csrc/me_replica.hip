@@ -15,8 +15,12 @@
 // and counter.  (The first version, one atomic per wavefront on a grid of one lane per pair, spent most of its 136 us at
 // 2^20 chains x 16 parameters on ~15 000 same-address atomics.)
 #include <algorithm>
+#include <cmath>
+#include <string>
+#include <vector>
 
 #include "me_device.h"
+#include "me_engine.h"
 
 namespace me {
 namespace {
@@ -134,15 +138,121 @@ hipError_t launch(void *x, void *energy, long long n, int d, int n_terms, bool t
   return hipGetLastError();
 }
 
+// ---- entry points: temperature ladders and replica exchange ---------------------------------------------------------------
+// why this engine cannot carry a ladder (ME_OK: it can)
+int check_ladder_capable(me_engine *e) {
+  if (e->ks->n_real < 0)
+    return fail(e, ME_ERR_UNSUPPORTED, "temperature ladders are not available on the runtime-dimension kernel set (beyond " +
+                                           std::to_string(kMaxRegisterDof) + " real degrees of freedom)");
+  if (e->energy_kind == ME_ENERGY_DENSE_QUAD && e->nr == 64 && e->nc == 0)
+    return fail(e, ME_ERR_UNSUPPORTED, "temperature ladders are not available on the matrix-core kernels of the dense 64-parameter form");
+  return refuse_stale_total(e, "temperature ladders are");
+}
+int free_ladder(me_engine *e) {
+  ME_HIP(e, hipStreamSynchronize(e->stream));     // launches in flight read the table
+  e->ladder = me_engine::Ladder();
+  e->samples.rows = 0;        // recorded energies belong to the rungs of the ladder they were taken under
+  return ME_OK;
+}
 }  // namespace
+}  // namespace me
 
-hipError_t launch_replica_swap(void *x, void *energy, long long n, int d, int n_terms, bool tiled_state, int dtype,
-                               const void *ladder, int n_rungs, unsigned long long round, unsigned long long chain_offset,
-                               unsigned long long seed, unsigned long long *pair_counts, hipStream_t stream) {
-  if (n_rungs < 1 || n % ((long long)n_rungs * 64) != 0 || !ladder || !pair_counts) return hipErrorInvalidValue;
-  if (dtype == ME_F32)
-    return launch<float>(x, energy, n, d, n_terms, tiled_state, ladder, n_rungs, round, chain_offset, seed, pair_counts, stream);
-  return launch<double>(x, energy, n, d, n_terms, tiled_state, ladder, n_rungs, round, chain_offset, seed, pair_counts, stream);
+using namespace me;
+
+extern "C" {
+
+int me_set_temperature_ladder(me_engine *e, const double *temps, int32_t n_rungs) {
+  if (!e) return ME_ERR_INVALID;
+  if (n_rungs < 0 || (n_rungs > 0 && !temps)) return fail(e, ME_ERR_INVALID, "n_rungs must be >= 0 and temps given");
+  ME_HIP(e, hipSetDevice(e->device));
+  if (n_rungs == 0) return free_ladder(e);
+  int rc = check_ladder_capable(e);
+  if (rc != ME_OK) return rc;
+  for (int k = 0; k < n_rungs; ++k) {
+    if (!(std::isfinite(temps[k]) && temps[k] > 0))
+      return fail(e, ME_ERR_INVALID, "ladder temperatures must be finite and > 0");
+    if (k > 0 && !(temps[k] > temps[k - 1]))
+      return fail(e, ME_ERR_INVALID, "ladder temperatures must be strictly increasing");
+  }
+  if (e->n % (64ll * n_rungs) != 0)
+    return fail(e, ME_ERR_INVALID, "n_chains must be a multiple of 64 * n_rungs: every rung is a run of whole 64-chain tiles");
+  // the step kernels' scalar constants, per rung (me_kernels.hip: typed)
+  std::vector<double> table(2 * (size_t)n_rungs);
+  for (int k = 0; k < n_rungs; ++k) {
+    table[2 * k] = 1.0 / temps[k];
+    table[2 * k + 1] = 1.4426950408889634 / temps[k];
+  }
+  if ((rc = free_ladder(e)) != ME_OK) return rc;
+  ME_HIP(e, upload(e->ladder.table, table.data(), table.size(), e->dtype));
+  ME_HIP(e, e->ladder.pair_counts.resize(2 * (size_t)std::max(n_rungs - 1, 1) * sizeof(unsigned long long)));
+  ME_HIP(e, hipMemset(e->ladder.pair_counts.get(), 0, e->ladder.pair_counts.bytes()));
+  e->ladder.temps.assign(temps, temps + n_rungs);
+  e->ladder.n_rungs = n_rungs;
+  return ME_OK;
 }
 
-}  // namespace me
+int me_temperature_ladder(me_engine *e, double *temps, int32_t capacity, int32_t *n_rungs) {
+  if (!e || !n_rungs) return ME_ERR_INVALID;
+  *n_rungs = e->ladder.n_rungs;
+  if (e->ladder.n_rungs == 0 || !temps) return ME_OK;      // (temps = NULL: the count only)
+  if (capacity < e->ladder.n_rungs) return fail(e, ME_ERR_INVALID, "temps must hold n_rungs doubles");
+  std::copy(e->ladder.temps.begin(), e->ladder.temps.end(), temps);
+  return ME_OK;
+}
+
+// One round: rung k pairs with rung k+1 for every k = round (mod 2); slot j of the two rungs swaps x and its energy-ledger
+// rows with the Metropolis probability of the two temperatures; the pair's attempted / accepted counts are added to.
+int me_replica_exchange(me_engine *e, int32_t n_rounds) {
+  if (!e) return ME_ERR_INVALID;
+  if (n_rounds < 0) return fail(e, ME_ERR_INVALID, "n_rounds must be >= 0");
+  if (e->ladder.n_rungs == 0) return fail(e, ME_ERR_STATE, "no temperature ladder: call me_set_temperature_ladder first");
+  ME_HIP(e, hipSetDevice(e->device));
+  const auto swap = e->dtype == ME_F32 ? launch<float> : launch<double>;
+  for (int i = 0; i < n_rounds; ++i) {
+    ME_HIP(e, swap(e->x.get(), e->energy.get(), e->n, e->d, e->n_terms, e->x_tiled, e->ladder.table.get(), e->ladder.n_rungs, e->ladder.round,
+                   e->chain_offset, e->seed, e->ladder.pair_counts.get<unsigned long long>(), e->stream));
+    e->ladder.round += 1;
+  }
+  return ME_OK;
+}
+
+int me_replica_stats(me_engine *e, uint64_t *round, uint64_t *attempted, uint64_t *accepted, int32_t n_pairs) {
+  if (!e) return ME_ERR_INVALID;
+  if (e->ladder.n_rungs == 0) return fail(e, ME_ERR_STATE, "no temperature ladder");
+  if (n_pairs != e->ladder.n_rungs - 1) return fail(e, ME_ERR_INVALID, "n_pairs must be n_rungs - 1");
+  if (round) *round = e->ladder.round;
+  if (n_pairs == 0) return ME_OK;
+  ME_HIP(e, hipSetDevice(e->device));
+  std::vector<unsigned long long> counts(2 * (size_t)n_pairs);
+  ME_HIP(e, hipMemcpyAsync(counts.data(), e->ladder.pair_counts.get(), counts.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                           e->stream));
+  ME_HIP(e, hipStreamSynchronize(e->stream));
+  for (int k = 0; k < n_pairs; ++k) {
+    if (attempted) attempted[k] = counts[2 * k];
+    if (accepted) accepted[k] = counts[2 * k + 1];
+  }
+  return ME_OK;
+}
+
+int me_set_replica_stats(me_engine *e, uint64_t round, const uint64_t *attempted, const uint64_t *accepted, int32_t n_pairs) {
+  if (!e) return ME_ERR_INVALID;
+  if (e->ladder.n_rungs == 0) return fail(e, ME_ERR_STATE, "no temperature ladder");
+  if (n_pairs != e->ladder.n_rungs - 1) return fail(e, ME_ERR_INVALID, "n_pairs must be n_rungs - 1");
+  if (n_pairs > 0 && (!attempted || !accepted)) return fail(e, ME_ERR_INVALID, "attempted / accepted missing");
+  std::vector<unsigned long long> counts(2 * (size_t)n_pairs);
+  for (int k = 0; k < n_pairs; ++k) {
+    if (accepted[k] > attempted[k]) return fail(e, ME_ERR_INVALID, "accepted swaps exceed attempted ones");
+    counts[2 * k] = attempted[k];
+    counts[2 * k + 1] = accepted[k];
+  }
+  ME_HIP(e, hipSetDevice(e->device));
+  if (n_pairs > 0) {
+    ME_HIP(e, hipMemcpyAsync(e->ladder.pair_counts.get(), counts.data(), counts.size() * sizeof(unsigned long long), hipMemcpyHostToDevice,
+                             e->stream));
+    ME_HIP(e, hipStreamSynchronize(e->stream));
+  }
+  e->ladder.round = round;
+  return ME_OK;
+}
+
+}  // extern "C"

@@ -8,7 +8,9 @@
 // lags t = 1, 2, 4, 7, 11, ... ("fast": the increment grows by one; otherwise 1, 2, 3, ...) until the normalised
 // autocorrelation first turns non-positive after `mintime` lags, accumulating g = 1 + 2 sum C_t (1 - t/n) dt, and
 // writes Neff(t0) = (T - t0 + 1) / g.  k_best_start: one workgroup per series takes the first maximum of Neff.
-#include "me_internal.h"
+#include <string>
+
+#include "me_engine.h"
 
 namespace me {
 namespace {
@@ -98,8 +100,6 @@ __global__ void __launch_bounds__(kBlockThreads) k_fill(double *p, long long cou
   for (long long i = (long long)blockIdx.x * kBlockThreads + threadIdx.x; i < count; i += stride) p[i] = value;
 }
 
-}  // namespace
-
 // series: device [n_series][length]; scratch: device 2 * n_series * (length - 1) doubles; results: device arrays.
 hipError_t launch_detect_equilibration(const double *series, long long n_series, long long length, int fast, int nskip,
                                        double *scratch, long long *t0_out, double *g_out, double *neff_out,
@@ -119,4 +119,37 @@ hipError_t launch_detect_equilibration(const double *series, long long n_series,
   return hipGetLastError();
 }
 
+}  // namespace
 }  // namespace me
+
+using namespace me;
+
+extern "C" int me_detect_equilibration(int32_t device_id, const double *series, int64_t n_series, int64_t length, int32_t fast,
+                                       int32_t nskip, int64_t *t0, double *g, double *neff_max) {
+  if (!series || !t0 || !g || !neff_max) return fail(nullptr, ME_ERR_INVALID, "null pointer");
+  if (n_series <= 0 || length < 3 || nskip < 1) return fail(nullptr, ME_ERR_INVALID, "need n_series > 0, length >= 3, nskip >= 1");
+  ME_HIP(nullptr, hipSetDevice(device_id));
+  const size_t m = (size_t)(length - 1), ns = (size_t)n_series;
+  DeviceBuffer d_series, d_scratch, d_g, d_neff, d_t0;     // double, except d_t0: long long
+  ME_HIP(nullptr, d_series.resize(sizeof(double) * ns * (size_t)length));
+  ME_HIP(nullptr, d_scratch.resize(sizeof(double) * 2 * ns * m));
+  ME_HIP(nullptr, d_g.resize(sizeof(double) * ns));
+  ME_HIP(nullptr, d_neff.resize(sizeof(double) * ns));
+  ME_HIP(nullptr, d_t0.resize(sizeof(long long) * ns));
+  ME_HIP(nullptr, hipMemcpy(d_series.get(), series, d_series.bytes(), hipMemcpyHostToDevice));
+  ME_HIP(nullptr, launch_detect_equilibration(d_series.get<double>(), n_series, length, fast, nskip, d_scratch.get<double>(),
+                                              d_t0.get<long long>(), d_g.get<double>(), d_neff.get<double>(), nullptr));
+  ME_HIP(nullptr, hipDeviceSynchronize());
+  static_assert(sizeof(long long) == sizeof(int64_t), "t0 is copied out as int64");
+  ME_HIP(nullptr, hipMemcpy(t0, d_t0.get(), sizeof(int64_t) * ns, hipMemcpyDeviceToHost));
+  ME_HIP(nullptr, hipMemcpy(g, d_g.get(), sizeof(double) * ns, hipMemcpyDeviceToHost));
+  ME_HIP(nullptr, hipMemcpy(neff_max, d_neff.get(), sizeof(double) * ns, hipMemcpyDeviceToHost));
+  // a constant series has no autocorrelation: the host convention is (0, 1, 1)
+  for (size_t s = 0; s < ns; ++s) {
+    const double *row = series + s * (size_t)length;
+    bool constant = true;
+    for (int64_t i = 1; i < length && constant; ++i) constant = row[i] == row[0];
+    if (constant) { t0[s] = 0; g[s] = 1.0; neff_max[s] = 1.0; }
+  }
+  return ME_OK;
+}

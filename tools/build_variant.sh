@@ -6,7 +6,8 @@ set -e
 cd "$(dirname "$0")/.."
 name=$1; shift
 mkdir -p tools/variants/obj_$name
-for u in me_api me_generic me_statistics me_runtime_dims me_replica; do
+# the host units of build.py (every unit but me_kernels and me_population)
+for u in me_generic me_statistics me_runtime_dims me_replica me_mbar me_api; do
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -I include "$@" -c metropolisengine_amd/csrc/$u.hip -o tools/variants/obj_$name/$u.o &
 done
 # population annealing: built with the flag build.py gives it (its scan relies on unfused products, me_population.hip)
