@@ -1,6 +1,7 @@
 """Headline benchmark: MC steps/sec (chains x sweeps), BASELINE.json config 2.
 
-    python bench.py --gpus 1 --steps 4000 --warmup 1000
+    python bench.py --gpus 1 --steps 4000 --warmup 1000             # the headline figure and nothing else
+    python bench.py --gpus 1 --steps 4000 --warmup 1000 --full      # ... and every side measurement
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -11,9 +12,16 @@ One "step" = one ``step_all()`` = ONE launch of k_step advancing every chain by 
 accept/reject -> width-adaptation sweep (``--sweeps K`` fuses K sweeps per launch; reported separately as
 ``fused``).  State is resident in HBM before the timed region.  Prints ONE JSON line on rank 0.
 
+A plain run sets up, warms up, times the steps, writes ``--dump-outputs`` and prints the line: ``metric``, ``value``,
+``unit``, ``higher_is_better``, ``dtype``, ``ms_per_step`` and the ``roofline`` of the timed region itself.  Everything
+that takes a run of its own -- the CPU baselines, the fused-sweep run, ``roofline_hbm``, the ``f32`` block, BASELINE
+configs 3-5 (``other_configs``) and the pooled-moments all-reduce behind ``multi_gpu`` / ``acceptance_rate`` /
+``pooled_variance_mean`` -- runs with ``--full`` only; in a plain line those keys are null.  The timed region is the same
+either way.
+
 The top-level ``value`` / ``dtype`` / ``roofline`` are the FLOAT64 run: float64 / complex128 is the reference's
-arithmetic (metropolis_engine.py:41, :51), 288 B of state traffic per chain-step.  The float32 build of the same
-kernels (144 B per chain-step, the production dtype) is the sibling block ``f32``.  ``roofline_hbm`` is the same
+arithmetic (metropolis_engine.py:41, :51), 288 B of state traffic per chain-step.  With ``--full`` the float32 build of
+the same kernels (144 B per chain-step, the production dtype) is the sibling block ``f32``, and ``roofline_hbm`` is the
 float64 kernel at 2^22 chains, where the state (604 MB) no longer fits the 256 MiB Infinity Cache.
 
 ``--dump-outputs DIR`` writes the headline engine's state after the last timed step (parameters, energies and widths of a
@@ -320,7 +328,7 @@ def bound_label(state_bytes):
     return "hbm+infinity-cache" if state_bytes <= INFINITY_CACHE_BYTES else "hbm"
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=4000)
@@ -328,19 +336,32 @@ def main():
     ap.add_argument("--chains-log2", type=int, default=20, help="chains per GPU = 2**this")
     ap.add_argument("--dtype", default="f64", choices=("f64", "f32"), help="arithmetic of the headline run")
     ap.add_argument("--sweeps", type=int, default=1, help="sweeps fused per launch in the headline run")
-    ap.add_argument("--fused-sweeps", type=int, default=32, help="extra fused-sweep measurement (0 = skip)")
-    ap.add_argument("--hbm-chains-log2", type=int, default=22, help="chains of the cache-free roofline_hbm run (0 = skip)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline sample length (0 = skip)")
-    ap.add_argument("--extras", type=int, default=1, help="1: also time the float32 build of the headline kernel and "
-                    "BASELINE configs 3-5 through their protocols (a few seconds; at every --gpus N)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every side measurement: CPU baselines, fused sweeps, the "
+                         "cache-free roofline_hbm, the float32 build, BASELINE configs 3-5 and the pooled-moments "
+                         "all-reduce (the four options below choose among them; without --full none of them runs)")
+    ap.add_argument("--fused-sweeps", type=int, default=32, help="--full: extra fused-sweep measurement (0 = skip)")
+    ap.add_argument("--hbm-chains-log2", type=int, default=22,
+                    help="--full: chains of the cache-free roofline_hbm run (0 = skip)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: CPU baseline sample length (0 = skip)")
+    ap.add_argument("--extras", type=int, default=1, help="--full: 1 = also time the float32 build of the headline kernel "
+                    "and BASELINE configs 3-5 through their protocols (a few seconds; at every --gpus N)")
     ap.add_argument("--pool-backend", default="native", choices=("native", "torch"),
                     help="all-reduce of the pooled moments: the engine's own RCCL communicator, or torch.distributed")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the headline engine's state (rank 0's shard, a fixed sample of "
                          "chains) as DIR/<name>.npy")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full:
+        # a plain run is the headline figure alone: no side measurement runs, whatever its own option says
+        args.cpu_seconds, args.fused_sweeps, args.hbm_chains_log2, args.extras = 0.0, 0, 0, 0
+    return args
+
+
+def main():
+    args = parse_args()
 
     # stdout carries exactly ONE line, the JSON record: RCCL prints a version banner to stdout when a communicator is
     # created, and child libraries may print too -- everything before the record goes to stderr instead
@@ -467,7 +488,7 @@ def main():
     # (me_comm_init_rank + me_pooled_moments_allreduce, no PyTorch in the data path) unless --pool-backend torch
     # The first communicator decides the backend for the whole run, collectively: if it cannot be created on ANY rank
     # (librccl missing, an id that does not arrive) every rank falls back to torch.distributed, and the line says so.
-    if pool["backend"] == "rccl-native":
+    if args.full and pool["backend"] == "rccl-native":
         ok, why = 1.0, None
         try:
             native_comm(engine)
@@ -484,8 +505,8 @@ def main():
             except Exception:
                 pass
     pool_backend = pool["backend"]
-    stats = pooled_statistics(engine, backend=pool_backend)
-    rccl_version = engine.comm_info()[2] if pool_backend == "rccl-native" else None
+    stats = pooled_statistics(engine, backend=pool_backend) if args.full else None
+    rccl_version = engine.comm_info()[2] if (args.full and pool_backend == "rccl-native") else None
     engine.sync()
     engine.close()
     del engine
@@ -534,11 +555,16 @@ def main():
         extras = other_configs(me, rank, world, local_rank, args.chains_log2, reduce_max, pool_backend, native_comm)
 
     if rank == 0:
+        pooled = None
+        if stats is not None:
+            pooled = {"chains": stats["n_chains"], "backend": pool_backend or "torch.distributed",
+                      "ranks": int(round(stats["n_chains"] / float(n_local))), "acceptance_rate": stats["acceptance_rate"],
+                      "variance_mean": float(sum(stats["covariance"][i][i] for i in range(N_REAL)) / N_REAL)}
         line = {
             "metric": "MC steps/sec (chains x sweeps) at 2^20 chains, 16 params",
             "value": value, "unit": "chain-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": wall / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
+            "vs_baseline": None, "dtype": args.dtype, "data": "synthetic", "full": args.full,
             "config": {"workload": "config 2: 16 real params, isotropic quadratic E=sum x^2, T=1, 2^%d chains per GPU, "
                                    "identity proposal shape, %d sweep(s) per launch, Philox4x32-10 streams, %s state "
                                    "and arithmetic%s"
@@ -554,12 +580,12 @@ def main():
             "fused": fused,
             "other_configs": extras,
             "multi_gpu": {"backend": backend, "ranks_seen_by_allreduce": ranks_seen, "chain_offsets": offsets,
-                          "pooled_chains": stats["n_chains"],
-                          "pooled_moments_backend": pool_backend or "torch.distributed", "rccl_version": rccl_version,
+                          "pooled_chains": pooled and pooled["chains"],
+                          "pooled_moments_backend": pooled and pooled["backend"], "rccl_version": rccl_version,
                           "native_comm_fallback": pool["fallback"],
-                          "ranks_seen_by_pooled_allreduce": int(round(stats["n_chains"] / float(n_local)))},
-            "acceptance_rate": stats["acceptance_rate"],
-            "pooled_variance_mean": float(sum(stats["covariance"][i][i] for i in range(N_REAL)) / N_REAL),
+                          "ranks_seen_by_pooled_allreduce": pooled and pooled["ranks"]},
+            "acceptance_rate": pooled and pooled["acceptance_rate"],
+            "pooled_variance_mean": pooled and pooled["variance_mean"],
         }
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(line) + "\n").encode())

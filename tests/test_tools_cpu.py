@@ -22,3 +22,32 @@ def test_compare_bench_flags_a_fallen_throughput(tmp_path):
     assert ok.returncode == 0 and "config3_cycle_f64.chain_steps_per_s" in ok.stdout
     bad = subprocess.run([sys.executable, tool, str(old), str(fallen)], capture_output=True, text=True)
     assert bad.returncode == 1 and "<-- fell" in bad.stdout
+
+
+def test_compare_bench_reads_a_plain_line(tmp_path):
+    """A plain bench line (no --full) carries null side blocks: only the headline is compared."""
+    old, new = tmp_path / "old.json", tmp_path / "new.json"
+    old.write_text(json.dumps({"value": 2.0e10, "other_configs": None, "fused": None}) + "\n")
+    new.write_text(json.dumps({"value": 1.5e10, "other_configs": None, "fused": None}) + "\n")
+    tool = os.path.join(ROOT, "tools", "compare_bench.py")
+    ok = subprocess.run([sys.executable, tool, str(old), str(old)], capture_output=True, text=True)
+    assert ok.returncode == 0 and "headline" in ok.stdout
+    bad = subprocess.run([sys.executable, tool, str(old), str(new)], capture_output=True, text=True)
+    assert bad.returncode == 1 and "<-- fell" in bad.stdout
+
+
+def test_bench_side_measurements_need_full():
+    """bench.py without --full runs no side measurement, whatever the side options say; --full keeps their defaults and
+    honours each of them.  The headline options are untouched by it."""
+    import bench
+    side = ("cpu_seconds", "fused_sweeps", "hbm_chains_log2", "extras")
+    plain = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert not plain.full and all(getattr(plain, name) == 0 for name in side)
+    forced = bench.parse_args(["--cpu-seconds", "5", "--fused-sweeps", "8", "--extras", "1", "--hbm-chains-log2", "22"])
+    assert not forced.full and all(getattr(forced, name) == 0 for name in side)
+    full = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3", "--full"])
+    assert full.full and (full.cpu_seconds, full.fused_sweeps, full.hbm_chains_log2, full.extras) == (12.0, 32, 22, 1)
+    chosen = bench.parse_args(["--full", "--cpu-seconds", "0", "--fused-sweeps", "4"])
+    assert (chosen.cpu_seconds, chosen.fused_sweeps, chosen.hbm_chains_log2, chosen.extras) == (0.0, 4, 22, 1)
+    for args in (plain, full):
+        assert (args.gpus, args.steps, args.warmup, args.dtype, args.sweeps, args.chains_log2) == (1, 7, 3, "f64", 1, 20)

@@ -1,5 +1,5 @@
-"""Compare two bench.py JSON lines (files holding the line last, e.g. profiles/rNN_bench_n1.json): every throughput in the
-headline and in other_configs, with the relative change -- run it after ANY change to a shared header (round 3 lost 40 % of
+"""Compare two ``bench.py --full`` JSON lines (files holding the line last, e.g. profiles/rNN_bench_n1.json; of a plain
+line only the headline is compared): every throughput in the headline and in other_configs, with the relative change -- run it after ANY change to a shared header (round 3 lost 40 % of
 config 3's float64 cycle to an energy-functor change that only the closing bench line showed).
 
     python tools/compare_bench.py old.json new.json [tolerance, default 0.05]       exit code 1 if something fell by more
@@ -15,7 +15,7 @@ def load(path):
 
 def rates(record):
     out = {"headline": record["value"]}
-    for name, block in record.get("other_configs", {}).items():
+    for name, block in (record.get("other_configs") or {}).items():
         for key, value in block.items():
             if isinstance(value, (int, float)) and "chain_steps_per_s" in key:
                 out["%s.%s" % (name, key)] = value

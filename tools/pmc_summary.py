@@ -40,7 +40,7 @@ if not fetch or not write:
 f_kib, w_kib = statistics.median(fetch), statistics.median(write)
 chains_log2 = int(sys.argv[4]) if len(sys.argv) > 4 else 20
 per_chain = int(sys.argv[5]) if len(sys.argv) > 5 else 144
-flags = sys.argv[6] if len(sys.argv) > 6 else "--gpus 1 --steps 50 --warmup 20 --cpu-seconds 0 --fused-sweeps 0 --extras 0"
+flags = sys.argv[6] if len(sys.argv) > 6 else "--gpus 1 --steps 50 --warmup 20"
 chains = 1 << chains_log2
 out = {
     "command": "rocprofv3 --pmc <COUNTER> --kernel-trace --output-format csv -- python3 %s "

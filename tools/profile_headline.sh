@@ -6,7 +6,7 @@ set -e
 export TMPDIR=/tmp
 OUT=${OUT:-gpurun_out/r03_prof}
 mkdir -p $OUT
-COMMON="--gpus 1 --cpu-seconds 0 --fused-sweeps 0 --extras 0 --hbm-chains-log2 0"
+COMMON="--gpus 1"      # a plain run: the headline kernel alone (no --full)
 for dt in f64 f32; do
   for lg in 20 22; do
     tag=${dt}_2p${lg}
