@@ -207,6 +207,12 @@ def build_dims(n_real, n_complex, force=False):
     return _build_plugin(dims_plugin_path(n_real, n_complex), defines, [], force=force)
 
 
+# (17,0) 153 and (0,12) 144 packed entries: the largest register-resident real / complex factorisations; 18 (171 entries)
+# the smallest streamed size; 31, 32 the full 32-lane group; 33, 63 odd sizes with two rows per lane in float32; 65 the
+# first size past the tile kernel; (20,6) a streamed complex block behind a large real block
+CHOLESKY_CONFORMANCE_DIMS = [(17, 0), (0, 12), (18, 0), (31, 0), (32, 0), (33, 0), (63, 0), (65, 0), (20, 6)]
+
+
 def build_examples(force=False):
     """The shipped plugins: the cylinder-style user energy for BASELINE config 5 (2 real + 7 complex), the term-wise
     Landau plugin (energy dictionary, 2 real + 1 complex) and one kernel set outside KERNEL_DIMS, (3, 2), which
@@ -222,6 +228,8 @@ def build_examples(force=False):
                 pool.submit(build_dims, 24, 0, force),     # streamed per-chain shapes with two chains per wavefront
                 pool.submit(build_dims, 96, 0, force),     # the largest register-resident parameter space built by default
                 pool.submit(build_dims, 100, 0, force)]    # beyond it: compiled for cov_mode="reference" (per-chain shapes)
+        # the sizes tests/test_gpu_cholesky_conformance.py adds, one per edge of a factor kernel's dispatch
+        jobs += [pool.submit(build_dims, nr, nc, force) for nr, nc in CHOLESKY_CONFORMANCE_DIMS]
         return [job.result() for job in jobs]
 
 
