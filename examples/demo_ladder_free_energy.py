@@ -71,17 +71,32 @@ def subset_estimates(engine, grid):
     return np.array(ln_z), np.array(heat)
 
 
+def asymptotic_sigma(engine, grid):
+    """The asymptotic standard error of ``ln Z(T) / Z(T_max)`` on ``grid`` from ALL samples in one further pass
+    (``statistics.mbar_uncertainties``).  The errors are relative to rung 0, so the ladder is handed over hottest rung first.
+    The formula takes the samples as independent; records a few sweeps apart are not, so this is a lower bound here."""
+    temps = engine.temperatures
+    energies = engine.energy_samples()
+    rungs = np.tile(np.repeat(np.arange(temps.size), engine.n_chains // temps.size), energies.shape[0])
+    f = engine.ladder_free_energies()["f"]
+    out = statistics.mbar_uncertainties(energies, temps.size - 1 - rungs, temps[::-1], (f - f[-1])[::-1], targets=grid)
+    return out["d_ln_z"]
+
+
 def main(grid=None, **kw):
     engine = sample(**kw)
     temps = engine.temperatures
     grid = np.geomspace(temps[0], temps[-1], 22) if grid is None else np.asarray(grid, dtype=np.float64)
     whole = engine.reweight(grid, engine.ladder_free_energies()["f"])
     ln_z, heat = subset_estimates(engine, grid)
+    sigma = asymptotic_sigma(engine, grid)
     exact = quadrature(np.append(grid, temps[-1]))
     exact_ln_z, exact_heat = exact[0, :-1] - exact[0, -1], exact[2, :-1] / grid ** 2
     se = lambda a: a.std(axis=0, ddof=1) / np.sqrt(a.shape[0])      # noqa: E731
+    print("asymptotic sigma ", end="")       # of ln Z(T)/Z(T_max), from all samples taken as independent: beside the se
     print("     T   ln Z(T)/Z(T_max): MBAR +- se   quadrature      C(T): MBAR +- se   quadrature   neff")
     for i, t in enumerate(grid):
+        print("     %.5f     " % sigma[i], end="")
         print("%6.3f   %10.5f +- %.5f   %10.5f       %8.5f +- %.5f   %8.5f   %6.4f"
               % (t, ln_z[:, i].mean(), se(ln_z)[i], exact_ln_z[i], heat[:, i].mean(), se(heat)[i], exact_heat[i],
                  whole["neff_fraction"][i]))

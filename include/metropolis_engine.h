@@ -361,7 +361,26 @@ int me_set_population_families(me_engine *engine, int64_t chain_begin, int64_t n
  *                       of the reweighting weights w (N = all finite samples).  Any output pointer may be NULL.
  *   me_mbar_solve_samples / me_mbar_reweight_samples   the same kernels on host arrays (engine-independent, like
  *                       me_detect_equilibration): energies[n_samples], rungs[n_samples] in [0, n_rungs), ladder_temps[n_rungs]
- *                       finite and > 0 (any order).  For samples gathered from several shards, and for subsets of a run. */
+ *                       finite and > 0 (any order).  For samples gathered from several shards, and for subsets of a run.
+ *   me_mbar_gram               the Gram matrix G = W^T W of the MBAR weight matrix, from which the asymptotic covariance of
+ *                       the free energies and of reweighted energies follows on the host (Shirts & Chodera 2008, eqs. 8,
+ *                       D8; csrc/me_mbar_cov.hip has the definition).  f from me_mbar_solve; n_targets >= 0 target
+ *                       temperatures (finite, > 0; temps may be NULL when there are none).  W has C = n_rungs + 2 n_targets
+ *                       columns: column k < n_rungs is rung k (column_counts[k] = its finite samples), columns n_rungs + 2 t
+ *                       and n_rungs + 2 t + 1 are the state and the energy-weighted state of target t (counts 0).  gram is
+ *                       [C][C], full and bitwise symmetric; column_counts is [C]; ln_z and mean_e ([n_targets], may be NULL)
+ *                       are me_mbar_reweight's values (bit for bit when every energy is finite; otherwise the finite samples
+ *                       are packed first, in their order, and every result is bit for bit the result on the samples with
+ *                       the others removed); *n_used (may be NULL) the finite samples.  Any number of
+ *                       targets: they go through the device in chunks with n_rungs + 2 chunk <= 128, every chunk with the
+ *                       ladder columns, and the blocks of gram that pair targets of different chunks are NaN (the variances
+ *                       need the ladder-target and the same-target blocks only).  All sums have a fixed order.  Error codes
+ *                       as for me_mbar_reweight.
+ *   me_mbar_gram_samples       the same on host arrays, as me_mbar_reweight_samples.
+ *   me_mbar_energy_shift       E_shift of me_mbar_gram's energy columns over the engine's records, (the least finite recorded
+ *                       energy) - 1, from the device by the kernels me_mbar_gram takes it from: one read of the samples and
+ *                       8 bytes to the host.  The standard error of a reweighted energy needs mean_t = mean_e - E_shift.
+ *                       ME_ERR_STATE without a ladder, without records or without a finite sample. */
 int me_energy_samples_enable(me_engine *engine, int64_t capacity_records);
 int me_energy_samples_record(me_engine *engine);
 int me_energy_samples_count(me_engine *engine, int64_t *records, int64_t *capacity);
@@ -377,6 +396,12 @@ int me_mbar_solve_samples(int32_t device_id, const double *energies, const int32
 int me_mbar_reweight_samples(int32_t device_id, const double *energies, const int32_t *rungs, int64_t n_samples,
                              const double *ladder_temps, int32_t n_rungs, const double *f, const double *temps, int32_t n,
                              double *ln_z, double *mean_e, double *var_e, double *neff_fraction);
+int me_mbar_gram(me_engine *engine, const double *f, const double *temps, int32_t n_targets, double *gram,
+                 double *column_counts, double *ln_z, double *mean_e, int64_t *n_used);
+int me_mbar_gram_samples(int32_t device_id, const double *energies, const int32_t *rungs, int64_t n_samples,
+                         const double *ladder_temps, int32_t n_rungs, const double *f, const double *temps, int32_t n_targets,
+                         double *gram, double *column_counts, double *ln_z, double *mean_e, int64_t *n_used);
+int me_mbar_energy_shift(me_engine *engine, double *shift);
 
 /* Text of the last error on this engine (or of the last failed me_create when engine is NULL). */
 int me_last_error(me_engine *engine, char *buf, size_t buf_bytes);

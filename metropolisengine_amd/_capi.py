@@ -120,6 +120,11 @@ SYMBOLS = {
                                              ctypes.POINTER(ctypes.c_int32), _dp, ctypes.POINTER(ctypes.c_int64)]),
     "me_mbar_reweight_samples": (ctypes.c_int, [ctypes.c_int32, _dp, ctypes.POINTER(ctypes.c_int32), ctypes.c_int64, _dp,
                                                 ctypes.c_int32, _dp, _dp, ctypes.c_int32, _dp, _dp, _dp, _dp]),
+    "me_mbar_gram": (ctypes.c_int, [_H, _dp, _dp, ctypes.c_int32, _dp, _dp, _dp, _dp, ctypes.POINTER(ctypes.c_int64)]),
+    "me_mbar_gram_samples": (ctypes.c_int, [ctypes.c_int32, _dp, ctypes.POINTER(ctypes.c_int32), ctypes.c_int64, _dp,
+                                            ctypes.c_int32, _dp, _dp, ctypes.c_int32, _dp, _dp, _dp, _dp,
+                                            ctypes.POINTER(ctypes.c_int64)]),
+    "me_mbar_energy_shift": (ctypes.c_int, [_H, _dp]),
 }
 
 

@@ -34,34 +34,15 @@
 // 16 bytes per batch of kBatch iterations; no per-sample data leaves the device and there are no floating-point atomics.
 // k_mbar_count counts N_k (integer atomics); k_mbar_reweight / k_mbar_reweight_finish follow the same order for the merged
 // states, kTargets temperatures per pass.
-#include <algorithm>
-#include <cmath>
-#include <vector>
-
-#include "me_device.h"
-#include "me_engine.h"
-#include "me_math64.h"
+#include "me_mbar.h"
 
 namespace me {
+namespace mbar {
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kItems = 8;                       // samples per thread and tile
-constexpr int kTile = kThreads * kItems;        // 2048 samples
 constexpr int kChunk = 16;                      // rungs whose per-lane partial sums are in registers at a time
-constexpr int kMaxBlocks = 2048;                // about 8 blocks per CU; the grid depends on the sample count only
 constexpr int kUpdateThreads = 1024;
 constexpr int kBatch = 16;                      // iterations enqueued between two looks at the residual
-constexpr int kTargets = 8;                     // reweighting temperatures per pass over the samples
-constexpr int kK = 64;                          // most rungs of one problem
-
-// device-side state of a solve: doubles [beta | c = ln N + f | ln N | N | f], then the control words
-constexpr int kBeta = 0, kC = kK, kLnN = 2 * kK, kN = 3 * kK, kF = 4 * kK, kTableDoubles = 5 * kK;
-struct MbarControl {
-  double residual;
-  int iterations, done;
-};
 
 template <typename R>
 __global__ void __launch_bounds__(kThreads) k_energy_record(const R *energy, long long n, int n_terms, double *dst) {
@@ -110,14 +91,6 @@ __device__ __forceinline__ void flush_chunk(double (&acc)[kChunk], int c0, int n
     total[c0 + threadIdx.x] = total[c0 + threadIdx.x] + s;
   }
   __syncthreads();
-}
-
-// m_n and s_n of one sample over all rungs (table indices are wave-uniform)
-__device__ __forceinline__ void sample_max_sum(const double *__restrict__ table, int n_rungs, double e, double &m, double &s) {
-  m = -INFINITY;
-  for (int j = 0; j < n_rungs; ++j) m = fmax(m, __builtin_fma(-table[kBeta + j], e, table[kC + j]));
-  s = 0.0;
-  for (int j = 0; j < n_rungs; ++j) s = s + math64::exp_nonpos(__builtin_fma(-table[kBeta + j], e, table[kC + j]) - m);
 }
 
 // one sample of a tile: its energy (0 when it does not count) and whether it counts
@@ -340,32 +313,9 @@ __global__ void __launch_bounds__(kThreads) k_mbar_reweight_finish(const Moments
   out[4 * t + 3] = (b.W * b.W) / (n_used * b.Q);
 }
 
+}  // namespace
+
 // ---- host side --------------------------------------------------------------------------------------------------------
-// The samples of one MBAR problem, all in device memory.  rungs != nullptr: the rung of sample i is rungs[i]; otherwise
-// sample i is slot i % n_chains of an engine and its rung is (i % n_chains) / rung_chains.
-struct MbarSamples {
-  const double *energies;
-  const int *rungs;
-  long long n_samples, n_chains, rung_chains;
-};
-
-// device scratch of one solve / reweighting
-struct Work {
-  DeviceBuffer table, partials, inv_temps, out;   // double
-  DeviceBuffer moments;                           // Moments
-  DeviceBuffer counts;                            // unsigned long long
-  DeviceBuffer control;                           // MbarControl
-};
-
-#define ME_MBAR_HIP(call)                 \
-  do {                                    \
-    hipError_t err__ = (call);            \
-    if (err__ != hipSuccess) return err__; \
-  } while (0)
-
-long long tiles_of(long long n) { return (n + kTile - 1) / kTile; }
-int blocks_of(long long n) { return (int)std::min<long long>(tiles_of(n), kMaxBlocks); }
-
 // N_k into host `counts`; *empty_rung = the first rung without a finite sample or -1
 hipError_t count_used(const MbarSamples &sm, int n_rungs, Work &w, std::vector<unsigned long long> &counts, int *empty_rung,
                       hipStream_t stream) {
@@ -399,6 +349,28 @@ hipError_t upload_table(Work &w, const double *ladder_temps, int n_rungs, const 
   ME_MBAR_HIP(hipStreamSynchronize(stream));      // `table` leaves scope
   return hipSuccess;
 }
+
+hipError_t reweight_enqueue(const MbarSamples &sm, int n_rungs, Work &w, const double *temps, int n_temps, double n_used,
+                            std::vector<double> &inv, hipStream_t stream) {
+  const int n_blocks = blocks_of(sm.n_samples);
+  const long long n_tiles = tiles_of(sm.n_samples);
+  inv.resize((size_t)n_temps);
+  for (int t = 0; t < n_temps; ++t) inv[t] = 1.0 / temps[t];
+  ME_MBAR_HIP(w.inv_temps.resize(inv.size() * sizeof(double)));
+  ME_MBAR_HIP(w.out.resize(4 * inv.size() * sizeof(double)));
+  ME_MBAR_HIP(w.moments.resize((size_t)n_blocks * kTargets * sizeof(Moments)));
+  ME_MBAR_HIP(hipMemcpyAsync(w.inv_temps.get(), inv.data(), inv.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+  for (int t0 = 0; t0 < n_temps; t0 += kTargets) {
+    const int nt = std::min(kTargets, n_temps - t0);
+    hipLaunchKernelGGL(k_mbar_reweight, dim3(n_blocks), dim3(kThreads), 0, stream, sm.energies, sm.n_samples, n_rungs,
+                       w.table.get<const double>(), w.inv_temps.get<const double>() + t0, nt, n_tiles, w.moments.get<Moments>());
+    hipLaunchKernelGGL(k_mbar_reweight_finish, dim3(nt), dim3(kThreads), 0, stream, w.moments.get<const Moments>(), n_blocks, n_used,
+                       w.out.get<double>() + 4 * (size_t)t0);
+  }
+  return hipGetLastError();
+}
+
+namespace {
 
 // Both wait for the stream and write host arrays.  *empty_rung = the first rung without a finite sample (nothing else is
 // computed then), or -1.  mbar_solve: f[K], n_used[K].  mbar_reweight: any of the four outputs may be nullptr.
@@ -447,22 +419,8 @@ hipError_t mbar_reweight(const MbarSamples &sm, const double *ladder_temps, int 
   double n_used = 0.0;
   for (int k = 0; k < n_rungs; ++k) n_used += (double)counts[k];
   ME_MBAR_HIP(upload_table(w, ladder_temps, n_rungs, counts, f, stream));
-  const int n_blocks = blocks_of(sm.n_samples);
-  const long long n_tiles = tiles_of(sm.n_samples);
-  std::vector<double> inv((size_t)n_temps), out(4 * (size_t)n_temps);
-  for (int t = 0; t < n_temps; ++t) inv[t] = 1.0 / temps[t];
-  ME_MBAR_HIP(w.inv_temps.resize(inv.size() * sizeof(double)));
-  ME_MBAR_HIP(w.out.resize(out.size() * sizeof(double)));
-  ME_MBAR_HIP(w.moments.resize((size_t)n_blocks * kTargets * sizeof(Moments)));
-  ME_MBAR_HIP(hipMemcpyAsync(w.inv_temps.get(), inv.data(), inv.size() * sizeof(double), hipMemcpyHostToDevice, stream));
-  for (int t0 = 0; t0 < n_temps; t0 += kTargets) {
-    const int nt = std::min(kTargets, n_temps - t0);
-    hipLaunchKernelGGL(k_mbar_reweight, dim3(n_blocks), dim3(kThreads), 0, stream, sm.energies, sm.n_samples, n_rungs,
-                       w.table.get<const double>(), w.inv_temps.get<const double>() + t0, nt, n_tiles, w.moments.get<Moments>());
-    hipLaunchKernelGGL(k_mbar_reweight_finish, dim3(nt), dim3(kThreads), 0, stream, w.moments.get<const Moments>(), n_blocks, n_used,
-                       w.out.get<double>() + 4 * (size_t)t0);
-  }
-  ME_MBAR_HIP(hipGetLastError());
+  std::vector<double> inv, out(4 * (size_t)n_temps);
+  ME_MBAR_HIP(reweight_enqueue(sm, n_rungs, w, temps, n_temps, n_used, inv, stream));
   ME_MBAR_HIP(hipMemcpyAsync(out.data(), w.out.get(), out.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
   ME_MBAR_HIP(hipStreamSynchronize(stream));
   for (int t = 0; t < n_temps; ++t) {
@@ -473,6 +431,8 @@ hipError_t mbar_reweight(const MbarSamples &sm, const double *ladder_temps, int 
   }
   return hipSuccess;
 }
+
+}  // namespace
 
 // ---- entry points: energy samples, MBAR free energies and reweighting --------------------------------------------------
 int mbar_check_common(me_engine *e, int n_rungs, int empty_rung, hipError_t err) {
@@ -521,6 +481,7 @@ int upload_samples(int device_id, const double *energies, const int32_t *rungs, 
   sm.n_chains = sm.rung_chains = 1;
   return ME_OK;
 }
+namespace {
 int solve_common(me_engine *e, const MbarSamples &sm, const double *ladder_temps, int n_rungs, double tolerance, int max_iterations,
                  double *f_out, int32_t *iterations, double *residual, int64_t *n_used_out, hipStream_t stream) {
   if (!f_out) return fail(e, ME_ERR_INVALID, "f_out missing");
@@ -549,9 +510,11 @@ int reweight_common(me_engine *e, const MbarSamples &sm, const double *ladder_te
   return mbar_check_common(e, n_rungs, empty, err);
 }
 }  // namespace
+}  // namespace mbar
 }  // namespace me
 
 using namespace me;
+using namespace me::mbar;
 
 extern "C" {
 

@@ -697,6 +697,36 @@ class MetropolisEngine:
                                                *[_as_double_ptr(o) for o in out]))
         return _reweight_result(temps, *out)
 
+    def ladder_free_energy_uncertainties(self, f, targets=None, inefficiency=1.0):
+        """Asymptotic standard errors of the ladder's MBAR free energies ``f`` (of :meth:`ladder_free_energies`) and, with
+        ``targets``, of the reweighted ``ln_z`` and mean energy at those temperatures (``me_mbar_gram``: one further pass
+        over the recorded samples; see :func:`metropolisengine_amd.statistics.mbar_uncertainties` for the dictionary).  The
+        formula assumes independent samples: pass the statistical inefficiency of the energy series
+        (:func:`metropolisengine_amd.statistics.statistical_inefficiency`) as ``inefficiency`` (finite, ``>= 1``) and every
+        variance is multiplied by it.  ``ValueError`` for invalid ``targets`` or ``inefficiency``; raises like
+        :meth:`ladder_free_energies` without a ladder or without records."""
+        from .statistics import validate_mbar_temps, validate_mbar_inefficiency, _uncertainty_result
+        g = validate_mbar_inefficiency(inefficiency)
+        if targets is not None:
+            targets = validate_mbar_temps(targets, "targets")
+        f = np.ascontiguousarray(f, dtype=np.float64)
+        ladder = self.temperatures
+        if ladder is not None and (f.shape != ladder.shape or not np.all(np.isfinite(f))):
+            raise ValueError("f must hold one finite free energy per rung")
+        k = f.size if ladder is not None else 1
+        n_targets = 0 if targets is None else targets.size
+        c = k + 2 * n_targets
+        gram, counts = np.zeros((c, c)), np.zeros(c)
+        ln_z, mean_e = np.zeros(n_targets), np.zeros(n_targets)
+        n_used = ctypes.c_int64()
+        self._check(self._lib.me_mbar_gram(self._handle, _as_double_ptr(f), _as_double_ptr(targets) if n_targets else None, n_targets,
+                                           _as_double_ptr(gram), _as_double_ptr(counts), _as_double_ptr(ln_z), _as_double_ptr(mean_e),
+                                           ctypes.byref(n_used)))
+        shift = ctypes.c_double(0.0)
+        if n_targets:       # the shift of the energy columns, from the device: the samples stay there
+            self._check(self._lib.me_mbar_energy_shift(self._handle, ctypes.byref(shift)))
+        return _uncertainty_result(gram, counts, k, targets, ln_z, mean_e, n_used.value, g, shift.value)
+
     # ------------------------------------------------------------------ scalar temperature and population annealing
     def set_temp(self, temp):
         """Change the scalar temperature of the running engine (``me_set_temperature``); the next step uses it, so a schedule

@@ -168,6 +168,98 @@ def mbar_reweight(energies, rungs, temps, f, targets, device=0):
     return _reweight_result(targets, *out)
 
 
+MBAR_GRAM_MAX_COLUMNS = 128     # columns of the weight matrix per device pass (csrc/me_mbar_cov.hip)
+
+
+def validate_mbar_inefficiency(inefficiency):
+    """The statistical inefficiency that scales the asymptotic variances: a finite scalar ``>= 1`` (``ValueError``
+    otherwise)."""
+    g = float(inefficiency)
+    if not (np.isfinite(g) and g >= 1.0):
+        raise ValueError("inefficiency must be finite and >= 1")
+    return g
+
+
+def mbar_theta(gram, column_counts):
+    """The asymptotic covariance matrix of MBAR from the Gram matrix ``G = W^T W`` of the weight matrix (Shirts & Chodera,
+    J. Chem. Phys. 129:124105, 2008, eq. D8 through the eigendecomposition of ``G``): ``G = V diag(lam) V^T``, ``lam``
+    clamped at 0, ``S = diag(sqrt(lam))``, ``Theta = V S (I - S V^T diag(N) V S)^+ S V^T`` with the pseudo-inverse cut at
+    ``rcond = 1e-10``.  Host float64."""
+    g = np.asarray(gram, dtype=np.float64)
+    n = np.asarray(column_counts, dtype=np.float64)
+    lam, v = np.linalg.eigh(g)
+    sv = v * np.sqrt(np.clip(lam, 0.0, None))[None, :]
+    m = np.eye(lam.size) - sv.T @ (n[:, None] * sv)
+    return sv @ np.linalg.pinv(m, rcond=1e-10) @ sv.T
+
+
+def _uncertainty_result(gram, column_counts, n_rungs, targets, ln_z, mean_e, n_used, inefficiency, energy_shift):
+    """The dictionary of :func:`mbar_uncertainties` from what ``me_mbar_gram`` returns.  Targets are taken in the chunks the
+    device used (each with the ladder columns): the blocks of ``gram`` between chunks are not computed.  ``energy_shift`` =
+    the least finite energy - 1, the shift of the energy columns."""
+    k = n_rungs
+    n_targets = 0 if targets is None else targets.size
+    per = (MBAR_GRAM_MAX_COLUMNS - k) // 2
+    out = {"n_samples": int(n_used)}
+    d_ln_z, d_mean = np.zeros(n_targets), np.zeros(n_targets)
+    for t0 in range(0, max(n_targets, 1), per):
+        nt = min(per, n_targets - t0)
+        idx = np.concatenate([np.arange(k), k + 2 * t0 + np.arange(2 * nt)]).astype(np.intp)
+        theta = mbar_theta(gram[np.ix_(idx, idx)], column_counts[idx])
+        if t0 == 0:
+            diag = np.diag(theta)[:k]
+            out["theta"] = theta[:k, :k] * inefficiency
+            var = diag[:, None] + diag[None, :] - 2.0 * theta[:k, :k]
+            out["d_f_matrix"] = np.sqrt(np.clip(var, 0.0, None) * inefficiency)
+            np.fill_diagonal(out["d_f_matrix"], 0.0)
+            out["d_f"] = out["d_f_matrix"][:, 0].copy()
+        for t in range(nt):
+            a, b = k + 2 * t, k + 2 * t + 1
+            var_z = theta[a, a] + theta[0, 0] - 2.0 * theta[a, 0]
+            var_e = theta[b, b] + theta[a, a] - 2.0 * theta[b, a]
+            d_ln_z[t0 + t] = np.sqrt(max(var_z, 0.0) * inefficiency)
+            # (the energy column holds E - E_shift, whose mean is mean_e - E_shift; the shift drops out of the variance)
+            d_mean[t0 + t] = (mean_e[t0 + t] - energy_shift) * np.sqrt(max(var_e, 0.0) * inefficiency)
+    if n_targets:
+        out.update({"temps": targets, "ln_z": ln_z, "d_ln_z": d_ln_z, "energy_mean": mean_e, "d_energy_mean": d_mean})
+    return out
+
+
+def mbar_uncertainties(energies, rungs, temps, f, targets=None, inefficiency=1.0, device=0):
+    """Asymptotic standard errors of MBAR free energies and of reweighted energies from samples on the host
+    (``me_mbar_gram_samples``: one further pass over the samples builds the Gram matrix of the weight matrix on the matrix
+    cores; the C x C algebra of Shirts & Chodera 2008, eqs. 8 and D8, runs here in float64; the engine form is
+    ``MetropolisEngine.ladder_free_energy_uncertainties``).  ``f``: the converged free energies of
+    :func:`mbar_free_energies`.  Returns ``{"theta", "d_f", "d_f_matrix", "n_samples"}``: the K x K ladder block of the
+    covariance matrix, the standard error of ``f[k] - f[0]`` (``d_f[0] == 0``) and of every ``f[i] - f[j]``, and the number
+    of finite samples; with ``targets`` also ``{"temps", "ln_z", "d_ln_z", "energy_mean", "d_energy_mean"}``, the values of
+    :func:`mbar_reweight` with their standard errors.
+
+    The asymptotic formula assumes INDEPENDENT samples.  For correlated samples pass their statistical inefficiency
+    (:func:`statistical_inefficiency` of the energy series, ``>= 1``) as ``inefficiency``: every variance is multiplied by
+    it, the customary correction.  ``ValueError`` for an ``inefficiency`` that is not a finite scalar ``>= 1``."""
+    import ctypes
+    from . import _capi
+    g = validate_mbar_inefficiency(inefficiency)
+    e, r, t = validate_mbar_samples(energies, rungs, temps)
+    if targets is not None:
+        targets = validate_mbar_temps(targets, "targets")
+    f = np.ascontiguousarray(f, dtype=np.float64)
+    if f.shape != t.shape or not np.all(np.isfinite(f)):
+        raise ValueError("f must hold one finite free energy per rung")
+    n_targets = 0 if targets is None else targets.size
+    c = t.size + 2 * n_targets
+    gram, counts = np.zeros((c, c)), np.zeros(c)
+    ln_z, mean_e = np.zeros(n_targets), np.zeros(n_targets)
+    n_used = ctypes.c_int64()
+    dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)
+    _capi.check(_capi.load().me_mbar_gram_samples(
+        int(device), e.ctypes.data_as(dp), r.ctypes.data_as(ip), e.size, t.ctypes.data_as(dp), t.size, f.ctypes.data_as(dp),
+        targets.ctypes.data_as(dp) if n_targets else None, n_targets, gram.ctypes.data_as(dp), counts.ctypes.data_as(dp),
+        ln_z.ctypes.data_as(dp), mean_e.ctypes.data_as(dp), ctypes.byref(n_used)))
+    return _uncertainty_result(gram, counts, t.size, targets, ln_z, mean_e, n_used.value, g, e[np.isfinite(e)].min() - 1.0)
+
+
 def get_equilibration_points(df, device=None):
     """Per column ``[t0, g, Neff_max]``; constant columns are skipped and complex columns split into ``_real`` /
     ``_imag`` (statistics.py:25-48).  With ``device`` set, all columns go to the GPU in one batch."""

@@ -2,6 +2,7 @@
 
     python tools/bench_mbar.py [--log2-chains 15] [--records 1024] [--rungs 8 16 32] [--reference-log2 20]
     python tools/bench_mbar.py --one-solve 16       (a single solve, for a kernel trace around it)
+    python tools/bench_mbar.py --gram               (the Gram pass of the asymptotic error bars, profiles/mbar_uncertainty.txt)
 
 Per ladder size K: synthetic energies of a 16-dimensional quadratic form (E / T Gamma(8) distributed) on T_k = 0.5 r^k with
 r chosen so that the ladder spans the same range for every K, injected with set_energy_samples; one warm-up solve, then a
@@ -57,6 +58,32 @@ def time_solve(k, log2_chains, records):
     print("        reweighting to 8 temperatures: %.3f ms" % (1e3 * (time.perf_counter() - t0)), flush=True)
 
 
+def time_gram(k, log2_chains, records, n_targets=8):
+    """me_mbar_gram (csrc/me_mbar_cov.hip) without targets and with ``n_targets``, beside the solver's time per iteration on
+    the same samples.  The call includes its counting pass, the reweighting of the targets and the copy of G to the host."""
+    import ctypes
+    eng, _ = loaded_engine(k, log2_chains, records)
+    eng.ladder_free_energies(tol=1e-10, max_iter=16)
+    t0 = time.perf_counter()
+    out = eng.ladder_free_energies(tol=1e-10)
+    per_iteration = 1e3 * (time.perf_counter() - t0) / out["iterations"]
+    f, dp = out["f"], ctypes.POINTER(ctypes.c_double)
+    line = "K = %2d: %d samples, solver %.3f ms per iteration;" % (k, records << log2_chains, per_iteration)
+    for nt in (0, n_targets):
+        targets = np.geomspace(0.5, 3.0, nt) if nt else np.zeros(0)
+        c = k + 2 * nt
+        gram, counts = np.zeros((c, c)), np.zeros(c)
+        call = lambda: eng._check(eng._lib.me_mbar_gram(      # noqa: E731
+            eng._handle, f.ctypes.data_as(dp), targets.ctypes.data_as(dp) if nt else None, nt, gram.ctypes.data_as(dp),
+            counts.ctypes.data_as(dp), None, None, None))
+        call()                                                  # warm-up
+        t0 = time.perf_counter()
+        call()
+        ms = 1e3 * (time.perf_counter() - t0)
+        line += " Gram with %d targets (C = %d) %.3f ms = %.1f iterations;" % (nt, c, ms, ms / per_iteration)
+    print(line, flush=True)
+
+
 def time_reference(k, log2_samples):
     n = 1 << log2_samples
     temps = ladder(k)
@@ -96,7 +123,12 @@ if __name__ == "__main__":
     ap.add_argument("--rungs", type=int, nargs="*", default=[8, 16, 32])
     ap.add_argument("--reference-log2", type=int, default=20)
     ap.add_argument("--one-solve", type=int, default=0)
+    ap.add_argument("--gram", action="store_true")
     cli = ap.parse_args()
+    if cli.gram:
+        for k in cli.rungs:
+            time_gram(k, cli.log2_chains, cli.records)
+        sys.exit(0)
     if cli.one_solve:
         time_solve(cli.one_solve, cli.log2_chains, cli.records)
         sys.exit(0)
