@@ -403,6 +403,53 @@ int me_mbar_gram_samples(int32_t device_id, const double *energies, const int32_
                          double *gram, double *column_counts, double *ln_z, double *mean_e, int64_t *n_used);
 int me_mbar_energy_shift(me_engine *engine, double *shift);
 
+/* Recorded observables of a ladder and their reweighting to any temperature (no reference counterpart; csrc/me_mbar_obs.hip
+ * has the definition).  A chain's recordable quantities form a catalogue indexed q (D = n_real + 2 n_complex, NOBS = 2 n_real
+ * + n_complex, T = me_energy_terms):
+ *     [0, D)                     the state rows in ME_FIELD_PARAMS component order (x_r, Re z_c, Im z_c), widened to float64
+ *     [D, D + NOBS)              |x_r|, |z_c|, x_r^2 in ME_FIELD_OBS_MEAN order, formed in float64 from the WIDENED components:
+ *                                fabs(x), sqrt(fma(re, re, im * im)) with the correctly rounded square root, x * x -- so that
+ *                                the host can restate a record exactly whatever the device dtype (this is not the device-dtype
+ *                                arithmetic of me_measure)
+ *     [D + NOBS, D + NOBS + T)   the ledger rows (energy terms, row order), widened to float64
+ *   me_observable_samples_enable   needs an enabled energy store (ME_ERR_STATE otherwise); 1 <= n_observables <=
+ *                       ME_MAX_RECORDED_OBSERVABLES indices inside the catalogue (ME_ERR_INVALID otherwise; duplicates are
+ *                       allowed).  Allocates a zero-filled float64 device field [capacity][n_observables][n_chains] for the
+ *                       energy store's capacity and sets the record count of BOTH stores to 0: from then on
+ *                       me_energy_samples_record also enqueues the kernel that fills the observables' row, so record r of
+ *                       both stores is the same moment.  n_observables = 0 frees the field (the energy records stay).
+ *                       me_energy_samples_enable frees it too (a new energy store forgets everything), and
+ *                       me_set_temperature_ladder empties both stores together.  ME_ERR_UNSUPPORTED with
+ *                       ME_FLAG_REFERENCE_ENERGY_LEDGERS.
+ *   me_observable_samples_info     the number of recorded columns (0: no store) and their catalogue indices (`indices` has room
+ *                       for ME_MAX_RECORDED_OBSERVABLES entries, may be NULL).
+ *   me_observable_samples_get      rows [record_begin, record_begin + n_records) as [record][column][chain] doubles (waits for
+ *                       the stream).
+ *   me_observable_samples_set      replace the rows by n_records host rows; n_records must equal the current energy record
+ *                       count (ME_ERR_INVALID otherwise): to resume a run call me_energy_samples_set first, then this.
+ *                       me_energy_samples_set leaves the observable rows as they are; rows never written are zero.
+ *   me_mbar_reweight_observables   for each of the n target temperatures (finite, > 0) and each recorded column A_q, with the
+ *                       weights w of me_mbar_reweight (a sample is used when its ENERGY is finite): mean = sum w A_q / sum w,
+ *                       var = sum w (A_q - mean)^2 / sum w, cov_energy = sum w (A_q - mean)(E - mean_E) / sum w, all [n][Q],
+ *                       and neff_fraction [n]; d<A_q>/dT = cov_energy / T^2.  Any output may be NULL.  A non-finite value of
+ *                       column q in a used sample makes column q's results non-finite and leaves every other column's results
+ *                       bitwise unchanged.  All sums have a fixed order, and column q at target t is bit for bit the same
+ *                       whether it is asked for alone or among 16 columns and any number of targets.  Errors as for
+ *                       me_mbar_reweight, plus ME_ERR_STATE without an observable store.
+ *   me_mbar_reweight_observables_samples   the same kernels on host arrays, like me_mbar_reweight_samples; observables is
+ *                       [n_observables][n_samples], 1 <= n_observables <= ME_MAX_RECORDED_OBSERVABLES. */
+#define ME_MAX_RECORDED_OBSERVABLES 16
+int me_observable_samples_enable(me_engine *engine, const int32_t *indices, int32_t n_observables);
+int me_observable_samples_info(me_engine *engine, int32_t *n_observables, int32_t *indices);
+int me_observable_samples_get(me_engine *engine, int64_t record_begin, int64_t n_records, double *dst);
+int me_observable_samples_set(me_engine *engine, int64_t n_records, const double *src);
+int me_mbar_reweight_observables(me_engine *engine, const double *f, const double *temps, int32_t n, double *mean, double *var,
+                                 double *cov_energy, double *neff_fraction);
+int me_mbar_reweight_observables_samples(int32_t device_id, const double *energies, const int32_t *rungs, int64_t n_samples,
+                                         const double *observables, int32_t n_observables, const double *ladder_temps,
+                                         int32_t n_rungs, const double *f, const double *temps, int32_t n, double *mean,
+                                         double *var, double *cov_energy, double *neff_fraction);
+
 /* Text of the last error on this engine (or of the last failed me_create when engine is NULL). */
 int me_last_error(me_engine *engine, char *buf, size_t buf_bytes);
 

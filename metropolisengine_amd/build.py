@@ -99,7 +99,7 @@ def build(force=False, jobs=None, verbose=True):
             units.append((os.path.join(OBJ_DIR, "me_kernels_%d_%d_f%d.o" % (nr, nc, bits)), os.path.join(CSRC, "me_kernels.hip"),
                           ["-DME_NR=%d" % nr, "-DME_NC=%d" % nc, "-DME_DENSE=%d" % dense, "-DME_PER_CHAIN=%d" % per_chain,
                            "-DME_ONLY_DTYPE=%d" % bits]))
-    for name in ("me_generic", "me_statistics", "me_runtime_dims", "me_replica", "me_mbar", "me_mbar_cov", "me_api"):
+    for name in ("me_generic", "me_statistics", "me_runtime_dims", "me_replica", "me_mbar", "me_mbar_cov", "me_mbar_obs", "me_api"):
         units.append((os.path.join(OBJ_DIR, name + ".o"), os.path.join(CSRC, name + ".hip"), []))
     # population annealing: the weights, sums and slot boundaries must round exactly as written (no fused multiply-adds),
     # so that the scan pass reproduces the weight pass's sums bit for bit and tests/population_reference.py can restate them

@@ -202,10 +202,14 @@ struct me_engine {
     unsigned long long stages = 0, capacity = 0;
     std::vector<double> temps;       // T_new of every stage
   } population;
-  // recorded energy samples (me_energy_samples_*, me_mbar.hip): float64 [capacity][n], `rows` of them filled
+  // recorded energy samples (me_energy_samples_*, me_mbar.hip): float64 [capacity][n], `rows` of them filled; and the
+  // observables recorded with them (me_observable_samples_*, me_mbar_obs.hip): float64 [capacity][n_obs][n], the same `rows`
   struct Samples {
     me::DeviceBuffer data;
     long long capacity = 0, rows = 0;
+    me::DeviceBuffer obs;
+    int n_obs = 0;                                      // 0: no observable store
+    int obs_index[ME_MAX_RECORDED_OBSERVABLES] = {};    // catalogue indices of the recorded columns
   } samples;
   std::string err;
 

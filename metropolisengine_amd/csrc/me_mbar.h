@@ -1,6 +1,7 @@
-// What the two MBAR units share (me_mbar.hip: samples, solve, reweighting; me_mbar_cov.hip: the Gram matrix of the weight
-// matrix for the asymptotic covariance): the tile policy, the device table of a ladder, the per-sample sums and the host
-// helpers that me_mbar.hip defines.  Private to the host side, like me_engine.h.
+// What the MBAR units share (me_mbar.hip: samples, solve, reweighting; me_mbar_cov.hip: the Gram matrix of the weight
+// matrix for the asymptotic covariance; me_mbar_obs.hip: recorded observables and their reweighting): the tile policy, the
+// device table of a ladder, the per-sample sums and the host helpers that me_mbar.hip defines.  Private to the host side,
+// like me_engine.h.
 #pragma once
 
 #include <algorithm>
@@ -84,6 +85,10 @@ int engine_samples(me_engine *e, MbarSamples &sm);
 // host samples of the engine-less forms on the device (`energies_dev`, `rungs_dev`: theirs for the length of the call)
 int upload_samples(int device_id, const double *energies, const int32_t *rungs, int64_t n_samples, const double *ladder_temps,
                    int n_rungs, DeviceBuffer &energies_dev, DeviceBuffer &rungs_dev, MbarSamples &sm);
+
+// ---- defined in me_mbar_obs.hip -----------------------------------------------------------------------------------------
+// me_energy_samples_record's second kernel: row `row` of the engine's observable store (which exists) on the engine's stream
+hipError_t observable_record_enqueue(me_engine *e, long long row);
 
 }  // namespace mbar
 }  // namespace me

@@ -544,6 +544,7 @@ int me_energy_samples_record(me_engine *e) {
     hipLaunchKernelGGL(k_energy_record<float>, grid, dim3(kThreads), 0, e->stream, e->energy.get<const float>(), e->n, e->n_terms, dst);
   else hipLaunchKernelGGL(k_energy_record<double>, grid, dim3(kThreads), 0, e->stream, e->energy.get<const double>(), e->n, e->n_terms, dst);
   ME_HIP(e, hipGetLastError());
+  if (e->samples.n_obs) ME_HIP(e, observable_record_enqueue(e, e->samples.rows));     // the same moment, the same row
   e->samples.rows += 1;
   return ME_OK;
 }

@@ -1,0 +1,513 @@
+// Recorded per-chain observables of a ladder engine and their MBAR reweighting to any temperature
+// (me_observable_samples_*, me_mbar_reweight_observables and its engine-less twin in the public header).
+//
+// The store.  Coupled to the energy store of me_mbar.hip (me_engine::Samples): record r of both is the same moment, there is
+// ONE record count.  A float64 device field [capacity][Q][n_chains], Q <= 16 selected entries of the catalogue of a chain's
+// recordable quantities (D = nr + 2 nc, NOBS = 2 nr + nc):
+//     [0, D)                        the state rows in ME_FIELD_PARAMS component order (x_r, Re z_c, Im z_c), widened to float64
+//     [D, D + NOBS)                 |x_r|, |z_c|, x_r^2 in ME_FIELD_OBS_MEAN order, formed IN FLOAT64 FROM THE WIDENED COMPONENTS:
+//                                   fabs(x), sqrt(fma(re, re, im * im)) with the correctly rounded square root, x * x
+//     [D + NOBS, D + NOBS + T)      the ledger rows (energy terms, row order), widened to float64
+// The derived quantities are NOT the N_::sqrt_ / N_::abs_ of k_measure, which work in the device dtype: they are formed after
+// widening so that the host can restate a record exactly whatever the device dtype (float32 widens exactly).
+// k_observable_record: one lane per chain, Q coalesced float64 stores per lane; the selection is a kernel argument read with
+// wave-uniform indices (scalar registers), the state is read through the layout of the engine's kernel set (a launch flag,
+// as in k_trace: tile-major for register-resident sets with D >= 16, component-major otherwise), the ledger is component-major.
+// No kernel is instantiated per Q or per D.
+//
+// Reweighting.  With the weights of me_mbar_reweight (me_mbar.hip: d_n = m_n + ln s_n, l_n = -E_n / T - d_n, w_n = exp(l_n -
+// M); a sample is USED when its ENERGY is finite), for observable column A_q:
+//     mean_q = sum w A_q / sum w,  var_q = sum w (A_q - mean_q)^2 / sum w,  cov_energy_q = sum w (A_q - mean_q)(E - mean_E) / sum w
+// and neff_fraction = (sum w)^2 / (N sum w^2); d<A_q>/dT = cov_energy_q / T^2.  The running state of some samples is, per
+// target, (M, W = sum w, Q2 = sum w^2, mean_E) and, per target and observable, (mean_q, M2_q, C_q), all relative to the running
+// maximum M.  One more sample (weight w, the old sums rescaled by `scale`; one of the two is 1, the other exp of a
+// non-positive number):
+//     W <- W scale + w;  mean <- mean + (A - mean) w / W;  M2 <- M2 scale + w (A - mean_old)(A - mean_new);
+//     C <- C scale + w (A - mean_A_old)(E - mean_E_new)
+// and two states a (earlier), b merge by  C = C_a s_a + C_b s_b + (mean_A,b - mean_A,a)(mean_E,b - mean_E,a) W_a W_b / W, M2
+// likewise: the weighted form of Chan's update, no difference of large sums anywhere.  A non-finite A_q in a used sample
+// reaches (mean_q, M2_q, C_q) only: the other observables' results are bitwise what they are without it.
+//
+// The split.  Sixteen observables times eight targets of running state (16 x 8 x 3 + 8 x 4 doubles = 832 registers) do not fit
+// a lane, so:
+//   k_mbar_log_denominator   writes d_n once into a scratch buffer of 8 bytes per sample (K exponentials, exp_nonpos, and one
+//                            log per sample), NaN for unused samples and for the padding behind the store's records;
+//   k_mbar_reweight_obs      one pass per (up to kObsTargets = 4 targets) x (up to kObsCols = 4 observables): reads E_n, d_n
+//                            and its observable columns -- (1 + q) 8 + 8 bytes per sample -- and spends ONE exponential per
+//                            (sample, target).  4 x 4 + 4 x 4 x 3 = 64 doubles of running state per lane;
+//   k_mbar_reweight_obs_finish   block t: the block partials of target t joined in a fixed order, written straight into the
+//                            [n][Q] device outputs.
+// Grid policy of k_mbar_weights: tiles of 2048 samples walked grid-stride, at most 2048 blocks, the grid depends on the sample
+// count only.  Summation order, fixed (no floating-point atomics, bitwise reproducible), that of k_mbar_reweight: a lane's
+// state runs over its samples of ALL the block's tiles, tile by tile -> butterfly in the wavefront, the lower lane's state
+// the first operand -> the block's wavefronts in order -> partials[block][target] -> the finish kernel, in which lane l
+// first joins blocks l, l + 256, ... and the lanes are then joined as in a block: a fixed order, not block by block.
+// Every (q, t) pair sees exactly the operations of its own state and of its target's (M, W, Q2, mean_E), written without contraction (`fp
+// contract(off)`, fused multiply-adds spelled out) so that the position of a pair inside a pass cannot change how the
+// compiler rounds it: observable q at target t is bit for bit the same alone or among 16 x 9.  For the same reason the
+// engine form and the engine-less form agree bit for bit (the store's [record][Q][chain] and the host's [Q][sample] are
+// addressed through strides; the sample order is the same).  W and Q2 are me_mbar_reweight's up to that difference in
+// contraction: neff_fraction agrees with it to rounding, not bit for bit.
+// Registers (hipcc -O3, gfx950, -Rpass-analysis=kernel-resource-usage): k_mbar_reweight_obs 194 VGPRs, 2 wavefronts per SIMD;
+// k_mbar_reweight_obs_finish 94, k_mbar_log_denominator 54, k_observable_record 18; no kernel uses scratch.  (Columns beyond a
+// pass's nq are carried along unchanged, never zeroed behind a runtime bound: that indexing put the state into scratch.)
+#include "me_mbar.h"
+
+#pragma clang fp contract(off)
+
+namespace me {
+namespace mbar {
+namespace {
+
+constexpr int kObsTargets = 4;                  // targets per pass
+constexpr int kObsCols = 4;                     // observable columns per pass
+
+struct ObsSelection {
+  int q[ME_MAX_RECORDED_OBSERVABLES];
+};
+
+// ---- the store ----------------------------------------------------------------------------------------------------------
+template <typename R>
+__global__ void __launch_bounds__(kThreads) k_observable_record(const R *__restrict__ x, const R *__restrict__ energy, long long n,
+                                                                 int nr, int nc, int n_terms, int tiled, ObsSelection sel,
+                                                                 int n_sel, double *dst) {
+  const long long c = (long long)blockIdx.x * kThreads + threadIdx.x;
+  if (c >= n) return;
+  const int d = nr + 2 * nc, nobs = 2 * nr + nc;
+  // element index of state row k of this chain (k_trace's two layouts)
+  const long long x0 = tiled ? (c >> 6) * (long long)d * 64 + (c & 63) : c;
+  const long long xs = tiled ? 64 : n;
+  for (int j = 0; j < n_sel; ++j) {
+    const int q = sel.q[j];                     // wave-uniform
+    double v;
+    if (q < d) {
+      v = (double)x[x0 + (long long)q * xs];
+    } else if (q < d + nobs) {
+      const int o = q - d;
+      if (o < nr) {
+        v = fabs((double)x[x0 + (long long)o * xs]);
+      } else if (o < nr + nc) {
+        const double re = (double)x[x0 + (long long)o * xs], im = (double)x[x0 + (long long)(o + nc) * xs];
+        v = __builtin_sqrt(__builtin_fma(re, re, im * im));
+      } else {
+        const double xr = (double)x[x0 + (long long)(o - nr - nc) * xs];
+        v = xr * xr;
+      }
+    } else {
+      v = (double)energy[(long long)(q - d - nobs) * n + c];
+    }
+    dst[(long long)j * n + c] = v;
+  }
+}
+
+// ---- reweighting --------------------------------------------------------------------------------------------------------
+// what a target's weights share, and what one observable column adds
+struct TargetState {
+  double M, W, Q2, mean_e;
+  double mean[kObsCols], M2[kObsCols], C[kObsCols];
+};
+static_assert(sizeof(TargetState) == 16 * sizeof(double), "partials are addressed as 16 doubles per state");
+
+__device__ __forceinline__ void clear(TargetState &s) {
+  s.M = -INFINITY;
+  s.W = s.Q2 = s.mean_e = 0.0;
+#pragma unroll
+  for (int q = 0; q < kObsCols; ++q) s.mean[q] = s.M2[q] = s.C[q] = 0.0;
+}
+
+// one more sample: log weight l, energy e, observable values a[0 .. nq); one exponential, no branch on the data
+__device__ __forceinline__ void add_sample(TargetState &s, double l, double e, const double (&a)[kObsCols], int nq) {
+  const bool higher = l > s.M;
+  const double x = math64::exp_nonpos(higher ? s.M - l : l - s.M);
+  const double scale = higher ? x : 1.0, w = higher ? 1.0 : x;
+  const double W = s.W * scale + w;
+  const double r = w / W;
+  const double mean_e = s.mean_e + (e - s.mean_e) * r;
+  const double we = w * (e - mean_e);           // w (E - mean_E_new)
+#pragma unroll
+  for (int q = 0; q < kObsCols; ++q)
+    if (q < nq) {
+      const double delta = a[q] - s.mean[q];
+      const double mean = s.mean[q] + delta * r;
+      s.M2[q] = s.M2[q] * scale + (w * delta) * (a[q] - mean);
+      s.C[q] = s.C[q] * scale + delta * we;
+      s.mean[q] = mean;
+    }
+  s.Q2 = s.Q2 * (scale * scale) + w * w;
+  s.mean_e = mean_e;
+  s.W = W;
+  s.M = higher ? l : s.M;
+}
+
+__device__ __forceinline__ double pick(bool first, double a, double b) { return first ? a : b; }
+
+// a (earlier in the fixed order) and b joined; an empty side (W = 0) returns the other one unchanged.  Branch-free: the
+// general formula is evaluated and then dropped by selects (what it makes of an empty side, NaN included, is never kept).
+__device__ __forceinline__ TargetState merge(const TargetState &a, const TargetState &b, int nq) {
+  const bool keep_a = !(b.W > 0.0), keep_b = !keep_a && !(a.W > 0.0);
+  TargetState r;
+  const double M = fmax(a.M, b.M);
+  const double sa = math64::exp_nonpos(a.M - M), sb = math64::exp_nonpos(b.M - M);
+  const double Wa = a.W * sa, Wb = b.W * sb;
+  const double W = Wa + Wb;
+  const double fb = Wb / W, cross = Wa * fb;
+  const double delta_e = b.mean_e - a.mean_e;
+  r.M = pick(keep_a, a.M, pick(keep_b, b.M, M));
+  r.W = pick(keep_a, a.W, pick(keep_b, b.W, W));
+  r.mean_e = pick(keep_a, a.mean_e, pick(keep_b, b.mean_e, a.mean_e + delta_e * fb));
+  r.Q2 = pick(keep_a, a.Q2, pick(keep_b, b.Q2, a.Q2 * (sa * sa) + b.Q2 * (sb * sb)));
+#pragma unroll
+  for (int q = 0; q < kObsCols; ++q) {
+    if (q < nq) {
+      const double delta = b.mean[q] - a.mean[q];
+      r.mean[q] = pick(keep_a, a.mean[q], pick(keep_b, b.mean[q], a.mean[q] + delta * fb));
+      r.M2[q] = pick(keep_a, a.M2[q], pick(keep_b, b.M2[q], (a.M2[q] * sa + b.M2[q] * sb) + (delta * delta) * cross));
+      r.C[q] = pick(keep_a, a.C[q], pick(keep_b, b.C[q], (a.C[q] * sa + b.C[q] * sb) + (delta * delta_e) * cross));
+    } else {                                    // (unused columns stay what clear() made them)
+      r.mean[q] = a.mean[q], r.M2[q] = a.M2[q], r.C[q] = a.C[q];
+    }
+  }
+  return r;
+}
+
+// s and o with the lower lane's first
+__device__ __forceinline__ TargetState merge_ordered(bool o_first, const TargetState &s, const TargetState &o, int nq) {
+  TargetState a, b;
+  a.M = pick(o_first, o.M, s.M), b.M = pick(o_first, s.M, o.M);
+  a.W = pick(o_first, o.W, s.W), b.W = pick(o_first, s.W, o.W);
+  a.Q2 = pick(o_first, o.Q2, s.Q2), b.Q2 = pick(o_first, s.Q2, o.Q2);
+  a.mean_e = pick(o_first, o.mean_e, s.mean_e), b.mean_e = pick(o_first, s.mean_e, o.mean_e);
+#pragma unroll
+  for (int q = 0; q < kObsCols; ++q) {
+    a.mean[q] = pick(o_first, o.mean[q], s.mean[q]), b.mean[q] = pick(o_first, s.mean[q], o.mean[q]);
+    a.M2[q] = pick(o_first, o.M2[q], s.M2[q]), b.M2[q] = pick(o_first, s.M2[q], o.M2[q]);
+    a.C[q] = pick(o_first, o.C[q], s.C[q]), b.C[q] = pick(o_first, s.C[q], o.C[q]);
+  }
+  return merge(a, b, nq);
+}
+
+__device__ __forceinline__ TargetState shuffle_xor(const TargetState &s, int d, int nq) {
+  TargetState o;
+  o.M = __shfl_xor(s.M, d);
+  o.W = __shfl_xor(s.W, d);
+  o.Q2 = __shfl_xor(s.Q2, d);
+  o.mean_e = __shfl_xor(s.mean_e, d);
+#pragma unroll
+  for (int q = 0; q < kObsCols; ++q) {
+    if (q < nq) {
+      o.mean[q] = __shfl_xor(s.mean[q], d);
+      o.M2[q] = __shfl_xor(s.M2[q], d);
+      o.C[q] = __shfl_xor(s.C[q], d);
+    } else {
+      o.mean[q] = s.mean[q], o.M2[q] = s.M2[q], o.C[q] = s.C[q];
+    }
+  }
+  return o;
+}
+
+// butterfly over the wavefront; the lower lane's state is always the first operand, so every lane holds the same result
+__device__ __forceinline__ TargetState wave_merge(TargetState s, int nq) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const TargetState o = shuffle_xor(s, d, nq);
+    s = merge_ordered((lane & d) != 0, s, o, nq);
+  }
+  return s;
+}
+
+// the block's wavefront results in order (thread 0 returns the block's state)
+__device__ __forceinline__ TargetState block_merge(const TargetState &w, TargetState *waves, int nq) {
+  if ((threadIdx.x & 63) == 0) waves[threadIdx.x >> 6] = w;
+  __syncthreads();
+  TargetState b = waves[0];
+  if (threadIdx.x == 0)
+    for (int k = 1; k < kWaves; ++k) b = merge(b, waves[k], nq);
+  __syncthreads();
+  return b;
+}
+
+// d_n = m_n + ln s_n of every sample of the padded range [0, n_padded); NaN when the energy is not finite or n <= i
+__global__ void __launch_bounds__(kThreads) k_mbar_log_denominator(const double *__restrict__ energies, long long n, long long n_padded,
+                                                                    int n_rungs, const double *__restrict__ table, double *d) {
+  for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n_padded; i += (long long)gridDim.x * kThreads) {
+    const double e = i < n ? energies[i] : NAN;
+    double v = NAN;
+    if (isfinite(e)) {
+      double m, s;
+      sample_max_sum(table, n_rungs, e, m, s);
+      v = m + log(s);
+    }
+    d[i] = v;
+  }
+}
+
+// Sample i = record * n_chains + chain; column q of it sits at obs[record * record_stride + q * column_stride + chain] (the
+// engine's store: n_chains, Q n_chains, n_chains; host columns [Q][n]: n, 0, n).  `d` is padded to whole tiles.
+// Registers: 194 VGPRs, no AGPRs, no scratch, 2 wavefronts per SIMD (the running state alone is 128).
+__global__ void __launch_bounds__(kThreads) k_mbar_reweight_obs(const double *__restrict__ energies, const double *__restrict__ d,
+                                                                 const double *__restrict__ obs, long long n, long long n_chains,
+                                                                 long long record_stride, long long column_stride, int nq,
+                                                                 const double *__restrict__ inv_temps, int n_targets,
+                                                                 long long n_tiles, TargetState *partials) {
+  __shared__ TargetState waves[kWaves];
+  TargetState st[kObsTargets];
+#pragma unroll
+  for (int t = 0; t < kObsTargets; ++t) clear(st[t]);
+  for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    const long long base = tile * kTile + threadIdx.x;
+    long long record = base / n_chains, chain = base - record * n_chains;
+#pragma unroll 1
+    for (int r = 0; r < kItems; ++r) {
+      const long long i = base + (long long)r * kThreads;
+      const double dn = d[i];                   // (padded: in bounds; NaN beyond n)
+      if (dn == dn) {
+        const double e = energies[i];
+        const double *col = obs + record * record_stride + chain;
+        double a[kObsCols];
+#pragma unroll
+        for (int q = 0; q < kObsCols; ++q) a[q] = q < nq ? col[(long long)q * column_stride] : 0.0;
+#pragma unroll
+        for (int t = 0; t < kObsTargets; ++t)
+          if (t < n_targets) add_sample(st[t], __builtin_fma(-e, inv_temps[t], -dn), e, a, nq);
+      }
+      chain += kThreads;
+      while (chain >= n_chains) {
+        chain -= n_chains;
+        record += 1;
+      }
+    }
+  }
+#pragma unroll
+  for (int t = 0; t < kObsTargets; ++t) {
+    if (t >= n_targets) break;
+    const TargetState b = block_merge(wave_merge(st[t], nq), waves, nq);
+    if (threadIdx.x == 0) partials[(size_t)blockIdx.x * kObsTargets + t] = b;
+  }
+}
+
+// block t: the block partials of the pass's target t joined in a fixed order.  Row t of the [n][Q] outputs starts at
+// mean/var/cov + t * q_total (the host has offset the pointers to the pass's first target and column).
+__global__ void __launch_bounds__(kThreads) k_mbar_reweight_obs_finish(const TargetState *partials, int n_blocks, int nq, int q_total,
+                                                                        double n_used, int write_neff, double *mean, double *var,
+                                                                        double *cov, double *neff) {
+  __shared__ TargetState waves[kWaves];
+  const int t = blockIdx.x;
+  TargetState s;
+  clear(s);
+  for (int b = threadIdx.x; b < n_blocks; b += kThreads) s = merge(s, partials[(size_t)b * kObsTargets + t], nq);
+  const TargetState b = block_merge(wave_merge(s, nq), waves, nq);
+  if (threadIdx.x != 0) return;
+#pragma unroll
+  for (int q = 0; q < kObsCols; ++q)
+    if (q < nq) {
+      mean[(size_t)t * q_total + q] = b.mean[q];
+      var[(size_t)t * q_total + q] = b.M2[q] / b.W;
+      cov[(size_t)t * q_total + q] = b.C[q] / b.W;
+    }
+  if (write_neff) neff[t] = (b.W * b.W) / (n_used * b.Q2);
+}
+
+// where the observable columns of an MBAR problem are (device memory)
+struct ObsColumns {
+  const double *data;
+  int n_columns;
+  long long n_chains, record_stride, column_stride;
+};
+
+hipError_t reweight_observables(const MbarSamples &sm, const ObsColumns &oc, const double *ladder_temps, int n_rungs, const double *f,
+                                const double *temps, int n_temps, double *mean, double *var, double *cov, double *neff,
+                                int *empty_rung, hipStream_t stream) {
+  if (n_rungs < 1 || n_rungs > kK || sm.n_samples < 1 || n_temps < 1) return hipErrorInvalidValue;
+  Work w;
+  std::vector<unsigned long long> counts;
+  ME_MBAR_HIP(count_used(sm, n_rungs, w, counts, empty_rung, stream));
+  if (*empty_rung >= 0) return hipSuccess;
+  double n_used = 0.0;
+  for (int k = 0; k < n_rungs; ++k) n_used += (double)counts[k];
+  ME_MBAR_HIP(upload_table(w, ladder_temps, n_rungs, counts, f, stream));
+  const int n_blocks = blocks_of(sm.n_samples), nq_all = oc.n_columns;
+  const long long n_tiles = tiles_of(sm.n_samples), n_padded = n_tiles * kTile;
+  std::vector<double> inv((size_t)n_temps);
+  for (int t = 0; t < n_temps; ++t) inv[t] = 1.0 / temps[t];
+  const size_t cells = (size_t)n_temps * nq_all;
+  DeviceBuffer d, partials;
+  ME_MBAR_HIP(d.resize((size_t)n_padded * sizeof(double)));
+  ME_MBAR_HIP(partials.resize((size_t)n_blocks * kObsTargets * sizeof(TargetState)));
+  ME_MBAR_HIP(w.inv_temps.resize(inv.size() * sizeof(double)));
+  ME_MBAR_HIP(w.out.resize((3 * cells + (size_t)n_temps) * sizeof(double)));
+  ME_MBAR_HIP(hipMemcpyAsync(w.inv_temps.get(), inv.data(), inv.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+  double *o_mean = w.out.get<double>(), *o_var = o_mean + cells, *o_cov = o_var + cells, *o_neff = o_cov + cells;
+  hipLaunchKernelGGL(k_mbar_log_denominator, dim3(n_blocks), dim3(kThreads), 0, stream, sm.energies, sm.n_samples, n_padded, n_rungs,
+                     w.table.get<const double>(), d.get<double>());
+  for (int t0 = 0; t0 < n_temps; t0 += kObsTargets) {
+    const int nt = std::min(kObsTargets, n_temps - t0);
+    for (int q0 = 0; q0 < nq_all; q0 += kObsCols) {
+      const int nq = std::min(kObsCols, nq_all - q0);
+      const size_t cell = (size_t)t0 * nq_all + q0;
+      hipLaunchKernelGGL(k_mbar_reweight_obs, dim3(n_blocks), dim3(kThreads), 0, stream, sm.energies, d.get<const double>(),
+                         oc.data + (size_t)q0 * oc.column_stride, sm.n_samples, oc.n_chains, oc.record_stride, oc.column_stride, nq,
+                         w.inv_temps.get<const double>() + t0, nt, n_tiles, partials.get<TargetState>());
+      hipLaunchKernelGGL(k_mbar_reweight_obs_finish, dim3(nt), dim3(kThreads), 0, stream, partials.get<const TargetState>(), n_blocks, nq,
+                         nq_all, n_used, q0 == 0 ? 1 : 0, o_mean + cell, o_var + cell, o_cov + cell, o_neff + t0);
+    }
+  }
+  ME_MBAR_HIP(hipGetLastError());
+  std::vector<double> out(3 * cells + (size_t)n_temps);
+  ME_MBAR_HIP(hipMemcpyAsync(out.data(), w.out.get(), out.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+  ME_MBAR_HIP(hipStreamSynchronize(stream));      // (also: `inv`, `d` and `partials` leave scope)
+  if (mean) std::copy(out.begin(), out.begin() + cells, mean);
+  if (var) std::copy(out.begin() + cells, out.begin() + 2 * cells, var);
+  if (cov) std::copy(out.begin() + 2 * cells, out.begin() + 3 * cells, cov);
+  if (neff) std::copy(out.begin() + 3 * cells, out.end(), neff);
+  return hipSuccess;
+}
+
+int reweight_observables_common(me_engine *e, const MbarSamples &sm, const ObsColumns &oc, const double *ladder_temps, int n_rungs,
+                                const double *f, const double *temps, int n, double *mean, double *var, double *cov, double *neff,
+                                hipStream_t stream) {
+  if (!f || !temps || n < 1) return fail(e, ME_ERR_INVALID, "f and at least one target temperature are needed");
+  int rc = mbar_check_temps(e, temps, n, "target temperatures");
+  if (rc) return rc;
+  for (int k = 0; k < n_rungs; ++k)
+    if (!std::isfinite(f[k])) return fail(e, ME_ERR_INVALID, "f must be finite");
+  int empty = -1;
+  const hipError_t err = reweight_observables(sm, oc, ladder_temps, n_rungs, f, temps, n, mean, var, cov, neff, &empty, stream);
+  return mbar_check_common(e, n_rungs, empty, err);
+}
+
+int catalogue_size(const me_engine *e) { return e->d + e->nobs + e->n_terms; }
+
+}  // namespace
+
+// me_energy_samples_record's second kernel: row `row` of the observable store (the caller has checked that it exists)
+hipError_t observable_record_enqueue(me_engine *e, long long row) {
+  me_engine::Samples &s = e->samples;
+  ObsSelection sel;
+  for (int j = 0; j < ME_MAX_RECORDED_OBSERVABLES; ++j) sel.q[j] = j < s.n_obs ? s.obs_index[j] : 0;
+  double *dst = s.obs.get<double>() + (size_t)row * (size_t)s.n_obs * (size_t)e->n;
+  const dim3 grid((unsigned)((e->n + kThreads - 1) / kThreads));
+  if (e->dtype == ME_F32)
+    hipLaunchKernelGGL(k_observable_record<float>, grid, dim3(kThreads), 0, e->stream, e->x.get<const float>(), e->energy.get<const float>(),
+                       e->n, e->nr, e->nc, e->n_terms, e->x_tiled ? 1 : 0, sel, s.n_obs, dst);
+  else
+    hipLaunchKernelGGL(k_observable_record<double>, grid, dim3(kThreads), 0, e->stream, e->x.get<const double>(),
+                       e->energy.get<const double>(), e->n, e->nr, e->nc, e->n_terms, e->x_tiled ? 1 : 0, sel, s.n_obs, dst);
+  return hipGetLastError();
+}
+
+}  // namespace mbar
+}  // namespace me
+
+using namespace me;
+using namespace me::mbar;
+
+extern "C" {
+
+int me_observable_samples_enable(me_engine *e, const int32_t *indices, int32_t n_observables) {
+  if (!e) return ME_ERR_INVALID;
+  const int rc = refuse_stale_total(e, "observable samples are");
+  if (rc != ME_OK) return rc;
+  if (n_observables < 0 || n_observables > ME_MAX_RECORDED_OBSERVABLES)
+    return fail(e, ME_ERR_INVALID, "n_observables must lie in [0, " + std::to_string(ME_MAX_RECORDED_OBSERVABLES) + "]");
+  me_engine::Samples &s = e->samples;
+  ME_HIP(e, hipSetDevice(e->device));
+  if (n_observables == 0) {
+    ME_HIP(e, hipStreamSynchronize(e->stream));     // a record in flight writes the field
+    s.obs.reset();
+    s.n_obs = 0;
+    return ME_OK;
+  }
+  if (!s.data) return fail(e, ME_ERR_STATE, "observable samples need the energy store: call me_energy_samples_enable first");
+  if (!indices) return fail(e, ME_ERR_INVALID, "indices missing");
+  for (int j = 0; j < n_observables; ++j)
+    if (indices[j] < 0 || indices[j] >= catalogue_size(e))
+      return fail(e, ME_ERR_INVALID, "observable index " + std::to_string(indices[j]) + " outside the catalogue of " +
+                                         std::to_string(catalogue_size(e)) + " quantities");
+  ME_HIP(e, hipStreamSynchronize(e->stream));
+  s.obs.reset();
+  s.n_obs = 0;
+  s.rows = 0;
+  const size_t bytes = (size_t)s.capacity * (size_t)n_observables * (size_t)e->n * sizeof(double);
+  ME_HIP(e, s.obs.resize(bytes));
+  if (bytes) {
+    ME_HIP(e, hipMemsetAsync(s.obs.get(), 0, bytes, e->stream));
+    ME_HIP(e, hipStreamSynchronize(e->stream));
+  }
+  s.n_obs = n_observables;
+  for (int j = 0; j < n_observables; ++j) s.obs_index[j] = indices[j];
+  return ME_OK;
+}
+
+int me_observable_samples_info(me_engine *e, int32_t *n_observables, int32_t *indices) {
+  if (!e) return ME_ERR_INVALID;
+  if (n_observables) *n_observables = e->samples.n_obs;
+  if (indices)
+    for (int j = 0; j < e->samples.n_obs; ++j) indices[j] = e->samples.obs_index[j];
+  return ME_OK;
+}
+
+int me_observable_samples_get(me_engine *e, int64_t record_begin, int64_t n_records, double *dst) {
+  if (!e || (!dst && n_records > 0)) return ME_ERR_INVALID;
+  const me_engine::Samples &s = e->samples;
+  if (s.n_obs == 0) return fail(e, ME_ERR_STATE, "observable samples are not enabled: call me_observable_samples_enable first");
+  if (record_begin < 0 || n_records < 0 || record_begin + n_records > s.rows)
+    return fail(e, ME_ERR_INVALID, "record range outside the recorded samples");
+  if (n_records == 0) return ME_OK;
+  const size_t row = (size_t)s.n_obs * (size_t)e->n;
+  ME_HIP(e, hipSetDevice(e->device));
+  ME_HIP(e, hipMemcpyAsync(dst, s.obs.get<double>() + (size_t)record_begin * row, (size_t)n_records * row * sizeof(double),
+                           hipMemcpyDeviceToHost, e->stream));
+  ME_HIP(e, hipStreamSynchronize(e->stream));
+  return ME_OK;
+}
+
+int me_observable_samples_set(me_engine *e, int64_t n_records, const double *src) {
+  if (!e || (!src && n_records > 0)) return ME_ERR_INVALID;
+  const me_engine::Samples &s = e->samples;
+  if (s.n_obs == 0) return fail(e, ME_ERR_STATE, "observable samples are not enabled: call me_observable_samples_enable first");
+  if (n_records != s.rows)
+    return fail(e, ME_ERR_INVALID, "n_records must equal the energy record count (" + std::to_string(s.rows) +
+                                       "): call me_energy_samples_set first");
+  if (n_records == 0) return ME_OK;
+  ME_HIP(e, hipSetDevice(e->device));
+  ME_HIP(e, hipMemcpyAsync(s.obs.get(), src, (size_t)n_records * (size_t)s.n_obs * (size_t)e->n * sizeof(double), hipMemcpyHostToDevice,
+                           e->stream));
+  ME_HIP(e, hipStreamSynchronize(e->stream));
+  return ME_OK;
+}
+
+int me_mbar_reweight_observables(me_engine *e, const double *f, const double *temps, int32_t n, double *mean, double *var,
+                                 double *cov_energy, double *neff_fraction) {
+  if (!e) return ME_ERR_INVALID;
+  MbarSamples sm;
+  int rc = engine_samples(e, sm);
+  if (rc) return rc;
+  if (e->samples.n_obs == 0)
+    return fail(e, ME_ERR_STATE, "no recorded observables: me_observable_samples_enable, then me_energy_samples_record");
+  ME_HIP(e, hipSetDevice(e->device));
+  const ObsColumns oc{e->samples.obs.get<const double>(), e->samples.n_obs, e->n, (long long)e->samples.n_obs * e->n, e->n};
+  return reweight_observables_common(e, sm, oc, e->ladder.temps.data(), e->ladder.n_rungs, f, temps, n, mean, var, cov_energy,
+                                     neff_fraction, e->stream);
+}
+
+int me_mbar_reweight_observables_samples(int32_t device_id, const double *energies, const int32_t *rungs, int64_t n_samples,
+                                         const double *observables, int32_t n_observables, const double *ladder_temps, int32_t n_rungs,
+                                         const double *f, const double *temps, int32_t n, double *mean, double *var,
+                                         double *cov_energy, double *neff_fraction) {
+  if (!observables) return fail(nullptr, ME_ERR_INVALID, "null pointer");
+  if (n_observables < 1 || n_observables > ME_MAX_RECORDED_OBSERVABLES)
+    return fail(nullptr, ME_ERR_INVALID, "n_observables must lie in [1, " + std::to_string(ME_MAX_RECORDED_OBSERVABLES) + "]");
+  DeviceBuffer energies_dev, rungs_dev, obs_dev;
+  MbarSamples sm;
+  int rc = upload_samples(device_id, energies, rungs, n_samples, ladder_temps, n_rungs, energies_dev, rungs_dev, sm);
+  if (rc) return rc;
+  ME_HIP(nullptr, obs_dev.resize(sizeof(double) * (size_t)n_samples * (size_t)n_observables));
+  ME_HIP(nullptr, hipMemcpy(obs_dev.get(), observables, obs_dev.bytes(), hipMemcpyHostToDevice));
+  const ObsColumns oc{obs_dev.get<const double>(), n_observables, n_samples, 0, n_samples};
+  rc = reweight_observables_common(nullptr, sm, oc, ladder_temps, n_rungs, f, temps, n, mean, var, cov_energy, neff_fraction, nullptr);
+  (void)hipDeviceSynchronize();
+  return rc;
+}
+
+}  // extern "C"

@@ -727,6 +727,93 @@ class MetropolisEngine:
             self._check(self._lib.me_mbar_energy_shift(self._handle, ctypes.byref(shift)))
         return _uncertainty_result(gram, counts, k, targets, ln_z, mean_e, n_used.value, g, shift.value)
 
+    # ------------------------------------------------------------------ recorded observables and their reweighting
+    def observable_names(self):
+        """The catalogue of a chain's recordable quantities, in the order of the C ABI (``me_observable_samples_enable``):
+        the state rows ``real_i``, ``re_i``, ``im_i``; the observables ``abs_real_i``, ``abs_complex_i``, ``real_i_sq`` (the
+        order of :attr:`observables_mean`); the ledger rows ``energy_<term name>``."""
+        from .statistics import observable_catalogue
+        return observable_catalogue(self.num_real_params, self.num_complex_params, self.energy_term_names)
+
+    def record_observables(self, which):
+        """Record per-chain observables next to every energy record from now on (``me_observable_samples_enable``; call it
+        after :meth:`record_energies`, whose capacity it takes: float64, ``capacity * len(which) * n_chains * 8`` bytes on the
+        device).  ``which``: up to 16 names of :meth:`observable_names` or indices into it (duplicates allowed); ``None`` or
+        an empty sequence frees the store.  The records of BOTH stores so far are forgotten, so record ``r`` of
+        :meth:`energy_samples` and of :meth:`observable_samples` is always the same moment; :meth:`record_energies` frees the
+        observable store and :meth:`set_temperatures` empties both.  ``ValueError`` for unknown names, indices outside the
+        catalogue, more than 16 entries or no energy store; ``NotImplementedError`` with ``reference_energy_ledgers=True``.
+
+        Like the energy samples, the observable samples are NOT part of :meth:`state_dict`: a run is resumed with
+        :meth:`set_energy_samples` followed by :meth:`set_observable_samples`."""
+        from .statistics import validate_observable_selection
+        if which is None or len(which) == 0:
+            self._check(self._lib.me_observable_samples_enable(self._handle, None, 0))
+            return
+        idx = validate_observable_selection(which, self.observable_names())
+        status = self._lib.me_observable_samples_enable(self._handle, idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), idx.size)
+        if status == _capi.ME_ERR_STATE:         # no energy store
+            raise ValueError(_capi.last_error(self._handle))
+        self._check(status)
+
+    def _recorded_observable_indices(self):
+        n = ctypes.c_int32()
+        idx = np.zeros(16, dtype=np.int32)
+        self._check(self._lib.me_observable_samples_info(self._handle, ctypes.byref(n), idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+        return idx[:n.value]
+
+    @property
+    def recorded_observables(self):
+        """The names of the recorded columns, in column order (empty without an observable store)."""
+        names = self.observable_names()
+        return tuple(names[i] for i in self._recorded_observable_indices())
+
+    def observable_samples(self):
+        """The recorded observables, ``(records, Q, n_chains)`` float64, record ``r`` taken with energy record ``r``."""
+        q = self._recorded_observable_indices().size
+        if q == 0:
+            raise ValueError("no observable store: call record_observables first")
+        rows = self.n_energy_records
+        out = np.empty((rows, q, self.n_chains), dtype=np.float64)
+        if rows:
+            self._check(self._lib.me_observable_samples_get(self._handle, 0, rows, _as_double_ptr(out)))
+        return out
+
+    def set_observable_samples(self, samples):
+        """Replace the observable records by ``samples``, ``(records, Q, n_chains)`` with ``records`` equal to the current
+        number of energy records (call :meth:`set_energy_samples` first)."""
+        q = self._recorded_observable_indices().size
+        if q == 0:
+            raise ValueError("no observable store: call record_observables first")
+        a = np.ascontiguousarray(samples, dtype=np.float64)
+        if a.ndim != 3 or a.shape[1:] != (q, self.n_chains):
+            raise ValueError("samples must be (records, Q = %d, n_chains = %d)" % (q, self.n_chains))
+        self._check(self._lib.me_observable_samples_set(self._handle, a.shape[0], _as_double_ptr(a)))
+
+    def reweight_observables(self, temps, f=None):
+        """The recorded observables reweighted to each temperature of ``temps`` (``me_mbar_reweight_observables``, on the
+        device): ``{"temps", "names", "mean", "var", "cov_energy", "dmean_dT", "neff_fraction"}`` -- the MBAR estimates of
+        ``<A_q>``, of its variance and of its covariance with the energy at ``T``, all ``(T, Q)``, ``dmean_dT = cov_energy /
+        T^2`` (the temperature derivative of the mean) and the effective fraction of the samples, ``(T,)``.  ``f``: the free
+        energies of :meth:`ladder_free_energies` (solved with the defaults when ``None``).  Bitwise reproducible, and column
+        ``q`` at temperature ``t`` does not depend on what else is asked for.  ``ValueError`` for empty, non-finite or
+        non-positive ``temps``; raises without a ladder, without records or without an observable store."""
+        from .statistics import validate_mbar_temps, _observable_result
+        temps = validate_mbar_temps(temps)
+        names = self.recorded_observables
+        if not names:
+            raise ValueError("no observable store: call record_observables first")
+        if f is None:
+            f = self.ladder_free_energies()["f"]
+        f = np.ascontiguousarray(f, dtype=np.float64)
+        ladder = self.temperatures
+        if ladder is not None and f.shape != ladder.shape:
+            raise ValueError("f must hold one free energy per rung")
+        out = [np.zeros((temps.size, len(names))) for _ in range(3)] + [np.zeros(temps.size)]
+        self._check(self._lib.me_mbar_reweight_observables(self._handle, _as_double_ptr(f), _as_double_ptr(temps), temps.size,
+                                                           *[_as_double_ptr(o) for o in out]))
+        return _observable_result(temps, names, *out)
+
     # ------------------------------------------------------------------ scalar temperature and population annealing
     def set_temp(self, temp):
         """Change the scalar temperature of the running engine (``me_set_temperature``); the next step uses it, so a schedule

@@ -168,6 +168,87 @@ def mbar_reweight(energies, rungs, temps, f, targets, device=0):
     return _reweight_result(targets, *out)
 
 
+MBAR_MAX_OBSERVABLES = 16       # recorded / reweighted observable columns (ME_MAX_RECORDED_OBSERVABLES)
+
+
+def observable_catalogue(n_real, n_complex, term_names):
+    """The names of a chain's recordable quantities in the order of the C ABI: state rows (``real_i``, ``re_i``, ``im_i``),
+    observables (``abs_real_i``, ``abs_complex_i``, ``real_i_sq``), ledger rows (``energy_<term name>``)."""
+    nr, nc = int(n_real), int(n_complex)
+    return (["real_%d" % i for i in range(nr)] + ["re_%d" % i for i in range(nc)] + ["im_%d" % i for i in range(nc)] +
+            ["abs_real_%d" % i for i in range(nr)] + ["abs_complex_%d" % i for i in range(nc)] +
+            ["real_%d_sq" % i for i in range(nr)] + ["energy_%s" % name for name in term_names])
+
+
+def validate_observable_selection(which, catalogue):
+    """``which`` (names of ``catalogue`` or indices into it, 1 to 16 of them, duplicates allowed) as int32 indices;
+    ``ValueError`` otherwise."""
+    if isinstance(which, (str, bytes)):
+        which = [which]
+    which = list(which)
+    if not 1 <= len(which) <= MBAR_MAX_OBSERVABLES:
+        raise ValueError("between 1 and %d observables can be recorded, got %d" % (MBAR_MAX_OBSERVABLES, len(which)))
+    idx = []
+    for w in which:
+        if isinstance(w, str):
+            if w not in catalogue:
+                raise ValueError("unknown observable %r; this engine has %s" % (w, ", ".join(catalogue)))
+            idx.append(catalogue.index(w))
+        elif isinstance(w, (int, np.integer)) and not isinstance(w, bool):
+            if not 0 <= int(w) < len(catalogue):
+                raise ValueError("observable index %d outside the catalogue of %d quantities" % (int(w), len(catalogue)))
+            idx.append(int(w))
+        else:
+            raise ValueError("observables are named by str or int, got %r" % (w,))
+    return np.asarray(idx, dtype=np.int32)
+
+
+def validate_mbar_observables(observables, n_samples):
+    """``observables`` of the engine-less form as a contiguous float64 ``(Q, n_samples)`` array, ``1 <= Q <= 16`` (a 1-d
+    array of ``n_samples`` entries is one column).  Values may be non-finite.  ``ValueError`` otherwise."""
+    a = np.asarray(observables, dtype=np.float64)
+    if a.ndim == 1:
+        a = a[None, :]
+    if a.ndim < 2:
+        raise ValueError("observables must be (Q, n_samples)")
+    a = a.reshape(a.shape[0], -1)
+    if not 1 <= a.shape[0] <= MBAR_MAX_OBSERVABLES:
+        raise ValueError("between 1 and %d observable columns are supported" % MBAR_MAX_OBSERVABLES)
+    if a.shape[1] != n_samples:
+        raise ValueError("every observable column needs one value per sample (%d), got %d" % (n_samples, a.shape[1]))
+    return np.ascontiguousarray(a)
+
+
+def _observable_result(temps, names, mean, var, cov, neff):
+    return {"temps": temps, "names": tuple(names), "mean": mean, "var": var, "cov_energy": cov,
+            "dmean_dT": cov / (temps * temps)[:, None], "neff_fraction": neff}
+
+
+def mbar_reweight_observables(energies, rungs, temps, f, targets, observables, device=0):
+    """Reweight observables sampled along with the energies of a ladder (``temps``, free energies ``f`` of
+    :func:`mbar_free_energies`) to the temperatures ``targets`` (``me_mbar_reweight_observables_samples``; the engine form is
+    ``MetropolisEngine.reweight_observables``).  ``observables``: ``(Q, n_samples)``, ``Q <= 16``, column ``q`` holding
+    ``A_q`` of every sample in the order of ``energies``.  Returns ``{"temps", "names", "mean", "var", "cov_energy",
+    "dmean_dT", "neff_fraction"}``: the first four ``(T, Q)``, ``dmean_dT = cov_energy / T^2``; ``names`` are the column
+    numbers.  A sample counts when its ENERGY is finite; a non-finite value in column ``q`` of such a sample makes column
+    ``q``'s results non-finite and changes no other column."""
+    import ctypes
+    from . import _capi
+    e, r, t = validate_mbar_samples(energies, rungs, temps)
+    targets = validate_mbar_temps(targets, "targets")
+    f = np.ascontiguousarray(f, dtype=np.float64)
+    if f.shape != t.shape or not np.all(np.isfinite(f)):
+        raise ValueError("f must hold one finite free energy per rung")
+    a = validate_mbar_observables(observables, e.size)
+    q = a.shape[0]
+    out = [np.zeros((targets.size, q)) for _ in range(3)] + [np.zeros(targets.size)]
+    dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)
+    _capi.check(_capi.load().me_mbar_reweight_observables_samples(
+        int(device), e.ctypes.data_as(dp), r.ctypes.data_as(ip), e.size, a.ctypes.data_as(dp), q, t.ctypes.data_as(dp), t.size,
+        f.ctypes.data_as(dp), targets.ctypes.data_as(dp), targets.size, *[o.ctypes.data_as(dp) for o in out]))
+    return _observable_result(targets, tuple(range(q)), *out)
+
+
 MBAR_GRAM_MAX_COLUMNS = 128     # columns of the weight matrix per device pass (csrc/me_mbar_cov.hip)
 
 

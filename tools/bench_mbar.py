@@ -3,6 +3,7 @@
     python tools/bench_mbar.py [--log2-chains 15] [--records 1024] [--rungs 8 16 32] [--reference-log2 20]
     python tools/bench_mbar.py --one-solve 16       (a single solve, for a kernel trace around it)
     python tools/bench_mbar.py --gram               (the Gram pass of the asymptotic error bars, profiles/mbar_uncertainty.txt)
+    python tools/bench_mbar.py --observables        (reweighting of recorded observables: whole-call time beside the energy-only call)
 
 Per ladder size K: synthetic energies of a 16-dimensional quadratic form (E / T Gamma(8) distributed) on T_k = 0.5 r^k with
 r chosen so that the ladder spans the same range for every K, injected with set_energy_samples; one warm-up solve, then a
@@ -84,6 +85,47 @@ def time_gram(k, log2_chains, records, n_targets=8):
     print(line, flush=True)
 
 
+HBM_RATE = 6.3e12      # bytes per second a streaming kernel reaches on the MI355X (8 TB/s is the data-sheet figure)
+
+
+def time_observables(k, log2_chains, records, n_targets=8, columns=(1, 4, 16)):
+    """me_mbar_reweight_observables (csrc/me_mbar_obs.hip) for Q recorded columns at ``n_targets`` temperatures beside the
+    energy-only me_mbar_reweight on the same samples in the same run.  Both calls include their counting pass and the upload
+    of the table; the observables' call adds one pass that writes d_n and ceil(T / 4) ceil(Q / 4) passes of up to 4 targets x
+    4 columns that each read (1 + q) 8 + 8 bytes per sample.  The time is the wall time of the WHOLE call (counting pass,
+    table upload, allocation of d and of the partials, the d pass, two launches per pass, the copy back and the wait), so the
+    rate printed from it is a lower bound for what k_mbar_reweight_obs itself reaches, not its share."""
+    eng, _ = loaded_engine(k, log2_chains, records)
+    n = records << log2_chains
+    f = eng.ladder_free_energies(tol=1e-8)["f"]
+    targets = np.geomspace(0.5, 3.0, n_targets)
+
+    def best(call, repeats=3):
+        call()                                                  # warm-up: allocations, code objects
+        times = []
+        for _ in range(repeats):
+            t0 = time.perf_counter()
+            call()
+            times.append(time.perf_counter() - t0)
+        return 1e3 * min(times)
+
+    energy_ms = best(lambda: eng.reweight(targets, f))
+    print("K = %d, %d samples, %d targets: energy-only reweighting (me_mbar_reweight) %.3f ms" % (k, n, n_targets, energy_ms),
+          flush=True)
+    energies = eng.energy_samples()
+    for q in columns:
+        eng.record_observables([j % 4 for j in range(q)])       # (one real parameter: a catalogue of 4 entries, duplicates
+        eng.set_energy_samples(energies)                        # allowed; the values are set below)
+        scale = 1.0 + 0.125 * np.arange(q)
+        eng.set_observable_samples(energies[:, None, :] * scale[None, :, None])
+        ms = best(lambda: eng.reweight_observables(targets, f))
+        passes = [(min(4, n_targets - t0), min(4, q - q0)) for t0 in range(0, n_targets, 4) for q0 in range(0, q, 4)]
+        traffic = n * (16 + sum((1 + nq) * 8 + 8 for _, nq in passes))      # the d pass reads E and writes d
+        print("    Q = %2d: %.3f ms = %.2f x energy-only; %d passes, %.2f GB of sample traffic: whole call >= %.0f GB/s = %.0f %% "
+              "of the %.1f TB/s HBM rate (a lower bound for the passes)" % (q, ms, ms / energy_ms, len(passes), 1e-9 * traffic, 1e-9 * traffic / (1e-3 * ms),
+                                      100 * traffic / (1e-3 * ms) / HBM_RATE, 1e-12 * HBM_RATE), flush=True)
+
+
 def time_reference(k, log2_samples):
     n = 1 << log2_samples
     temps = ladder(k)
@@ -124,7 +166,11 @@ if __name__ == "__main__":
     ap.add_argument("--reference-log2", type=int, default=20)
     ap.add_argument("--one-solve", type=int, default=0)
     ap.add_argument("--gram", action="store_true")
+    ap.add_argument("--observables", action="store_true")
     cli = ap.parse_args()
+    if cli.observables:
+        time_observables(8, cli.log2_chains, cli.records)
+        sys.exit(0)
     if cli.gram:
         for k in cli.rungs:
             time_gram(k, cli.log2_chains, cli.records)
