@@ -1,11 +1,14 @@
 // Y = M X on the bf16 matrix cores with fp32-level accuracy: both operands are split into three bf16 pieces
-// (truncation splits: v = v1 + v2 + v3 exactly captures >= 22 mantissa bits) and the six products whose piece
-// indices sum to <= 4 are accumulated in fp32:
-//     M X ~ M1 X1 + (M1 X2 + M2 X1) + (M1 X3 + M3 X1 + M2 X2),   neglected terms <= 2^-24 |M| |X|.
-// bf16 x bf16 products are exact in fp32, so the only rounding is the fp32 accumulation -- the same as any fp32
-// summation order.  Unlike v_mfma_f32_32x32x2_f32 (which occupies the fp32 VALU lanes, me_dense_mfma.h), the bf16
-// MFMAs run on the matrix pipe beside VALU work, and 96 v_mfma_f32_32x32x16_bf16 (32 cycles each) replace
-// 128 fp32 MFMAs of 64 cycles.
+// (truncation splits, 8 significant bits each: v = v1 + v2 + v3 exactly, |v2| < 2^-7 |v|, |v3| < 2^-15 |v|) and
+// the six products whose piece indices sum to <= 4 are accumulated in fp32:
+//     M X ~ M1 X1 + (M1 X2 + M2 X1) + (M1 X3 + M3 X1 + M2 X2).
+// Neglected: |M2||X3| + |M3||X2| + |M3||X3| <= (2^-21 + 2^-30) |M| |X| in the worst case (operands
+// 1.0000000 1111...), about 2^-23 where every mantissa bit is set and less on random data; derived in
+// tests/dense_product_reference.py, which holds the kernel to it.  bf16 x bf16 products are exact in fp32, so
+// the only rounding is the fp32 accumulation -- the same as any fp32 summation order.  Unlike
+// v_mfma_f32_32x32x2_f32 (which occupies the fp32 VALU lanes, me_dense_mfma.h), the bf16 MFMAs run on the
+// matrix pipe beside VALU work, and 96 v_mfma_f32_32x32x16_bf16 (32 cycles each) replace 128 fp32 MFMAs of
+// 64 cycles.
 //
 // One wavefront = 64 chains, one chain per lane.  Operand maps (guide section 3): lane l (r = l & 31, h = l >> 5) holds
 // A[row r][k = 8h + j] and B[k = 8h + j][col r], j = 0..7, of a 32x32x16 product; C/D as for every 32x32 shape.
