@@ -24,6 +24,19 @@ COMM_ID_BYTES = 128
 _dp = ctypes.POINTER(ctypes.c_double)
 
 
+def double_ptr(arr):
+    """A contiguous float64 array as ``double *``."""
+    return arr.ctypes.data_as(_dp)
+
+
+def int32_ptr(arr):
+    return arr.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+
+
+def int64_ptr(arr):
+    return arr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
+
+
 class MeConfig(ctypes.Structure):
     """struct me_config (include/metropolis_engine.h)."""
     _fields_ = [

@@ -33,6 +33,15 @@ KERNEL_DIMS = [
     (0, 1, 0, 1), (0, 2, 0, 1), (0, 3, 0, 1), (0, 4, 0, 1),
     (1, 1, 0, 1), (1, 2, 0, 1), (2, 1, 0, 1), (2, 2, 1, 1), (4, 4, 0, 1), (2, 7, 0, 1),
 ]
+# the dimension-independent units, csrc/<name>.hip, with the hipcc flags of their own: every unit but me_kernels, in link order
+# (tools/build_variant.sh builds its variants from this list)
+HOST_UNITS = [
+    ("me_generic", []), ("me_statistics", []), ("me_runtime_dims", []), ("me_replica", []), ("me_mbar", []), ("me_mbar_cov", []),
+    ("me_mbar_obs", []), ("me_api", []),
+    # population annealing: the weights, sums and slot boundaries must round exactly as written (no fused multiply-adds), so
+    # that the scan pass reproduces the weight pass's sums bit for bit and tests/population_reference.py can restate them
+    ("me_population", ["-ffp-contract=off"]),
+]
 MAX_PACKED_IN_REGISTERS = 160     # per-chain covariance / factor kernels keep the packed matrix in registers
 MAX_REGISTER_DOF = 96             # largest n_real + 2 n_complex the register-resident kernels are built for BY DEFAULT: beyond
 #                                   it built-in energies run on the runtime-dimension set (no build, identity / shared shape)
@@ -99,11 +108,8 @@ def build(force=False, jobs=None, verbose=True):
             units.append((os.path.join(OBJ_DIR, "me_kernels_%d_%d_f%d.o" % (nr, nc, bits)), os.path.join(CSRC, "me_kernels.hip"),
                           ["-DME_NR=%d" % nr, "-DME_NC=%d" % nc, "-DME_DENSE=%d" % dense, "-DME_PER_CHAIN=%d" % per_chain,
                            "-DME_ONLY_DTYPE=%d" % bits]))
-    for name in ("me_generic", "me_statistics", "me_runtime_dims", "me_replica", "me_mbar", "me_mbar_cov", "me_mbar_obs", "me_api"):
-        units.append((os.path.join(OBJ_DIR, name + ".o"), os.path.join(CSRC, name + ".hip"), []))
-    # population annealing: the weights, sums and slot boundaries must round exactly as written (no fused multiply-adds),
-    # so that the scan pass reproduces the weight pass's sums bit for bit and tests/population_reference.py can restate them
-    units.append((os.path.join(OBJ_DIR, "me_population.o"), os.path.join(CSRC, "me_population.hip"), ["-ffp-contract=off"]))
+    for name, flags in HOST_UNITS:
+        units.append((os.path.join(OBJ_DIR, name + ".o"), os.path.join(CSRC, name + ".hip"), flags))
 
     todo = []
     for obj, src, flags in units:

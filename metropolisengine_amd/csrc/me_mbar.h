@@ -1,6 +1,7 @@
 // What the MBAR units share (me_mbar.hip: samples, solve, reweighting; me_mbar_cov.hip: the Gram matrix of the weight
 // matrix for the asymptotic covariance; me_mbar_obs.hip: recorded observables and their reweighting): the tile policy, the
-// device table of a ladder, the per-sample sums and the host helpers that me_mbar.hip defines.  Private to the host side,
+// device table of a ladder, the per-sample sums, and the host scaffolding of an entry point, which me_mbar.hip defines: where
+// the samples come from (Source), the prepared problem (Problem, prepare) and the argument checks.  Private to the host side,
 // like me_engine.h.
 #pragma once
 
@@ -11,6 +12,7 @@
 #include "me_device.h"
 #include "me_engine.h"
 #include "me_math64.h"
+#include "me_wave.h"
 
 #pragma GCC visibility push(hidden)
 
@@ -48,12 +50,22 @@ struct MbarSamples {
   long long n_samples, n_chains, rung_chains;
 };
 
-// device scratch of one solve / reweighting
+// Observable columns that go with the samples (device memory): column q of sample i = record * n_chains + chain sits at
+// data[record * record_stride + q * column_stride + chain] (an engine's store: strides Q n_chains, n_chains; host columns
+// [Q][n]: n_chains = n, strides 0, n)
+struct ObsColumns {
+  const double *data;
+  int n_columns;
+  long long n_chains, record_stride, column_stride;
+};
+
+// Device scratch of one problem.  Every operation: `counts` (unsigned long long [kK]) and `table` (double [kTableDoubles]),
+// both from prepare.  Operations with target temperatures: `inv_temps` (double, 1 / T_t) and `out` (double), both sized by
+// upload_targets; `out` holds 4 doubles per target behind reweight_enqueue (me_mbar.hip, me_mbar_cov.hip) and [mean | var |
+// cov][target][column], then neff[target], in me_mbar_obs.hip.  reweight_enqueue alone: `moments` (Moments [block][kTargets]).
+// The solve alone: `partials` (double [block][rung]) and `control` (MbarControl).
 struct Work {
-  DeviceBuffer table, partials, inv_temps, out;   // double
-  DeviceBuffer moments;                           // Moments
-  DeviceBuffer counts;                            // unsigned long long
-  DeviceBuffer control;                           // MbarControl
+  DeviceBuffer table, partials, inv_temps, out, moments, counts, control;
 };
 
 #define ME_MBAR_HIP(call)                 \
@@ -66,25 +78,55 @@ inline long long tiles_of(long long n) { return (n + kTile - 1) / kTile; }
 inline int blocks_of(long long n) { return (int)std::min<long long>(tiles_of(n), kMaxBlocks); }
 
 // ---- defined in me_mbar.hip ---------------------------------------------------------------------------------------------
-// N_k into host `counts` (kK entries); *empty_rung = the first rung without a finite sample or -1.  Waits for the stream.
-hipError_t count_used(const MbarSamples &sm, int n_rungs, Work &w, std::vector<unsigned long long> &counts, int *empty_rung,
-                      hipStream_t stream);
-// the device table (w.table) for free energies f (nullptr: zeros)
-hipError_t upload_table(Work &w, const double *ladder_temps, int n_rungs, const std::vector<unsigned long long> &counts,
-                        const double *f, hipStream_t stream);
-// Enqueues the reweighting of the samples to temps[0 .. n_temps): afterwards w.inv_temps[t] = 1 / T_t and w.out[4 t ..] =
-// (ln_z, mean_e, var_e, neff_fraction) of T_t on the device.  Needs w.table; does not wait: `inv`, the host copy of the
-// 1 / T_t that is on its way to the device, is the caller's to keep until the stream has been waited for.
-hipError_t reweight_enqueue(const MbarSamples &sm, int n_rungs, Work &w, const double *temps, int n_temps, double n_used,
-                            std::vector<double> &inv, hipStream_t stream);
-// hipError_t / an empty rung as the ME_* code of an entry point
-int mbar_check_common(me_engine *e, int n_rungs, int empty_rung, hipError_t err);
+// Where the samples of an entry point come from: the store of an engine (on its stream), or host arrays, which from_host puts
+// on the device for the length of the call (e == nullptr, the null stream; messages go to the calling thread).
+struct Source {
+  me_engine *e = nullptr;
+  MbarSamples sm{};
+  const double *ladder_temps = nullptr;
+  int n_rungs = 0;
+  hipStream_t stream = nullptr;
+  ObsColumns columns{};                           // n_columns = 0: none
+  DeviceBuffer energies_dev, rungs_dev, columns_dev;      // the host form's samples and columns
+  // the engine's stores and ladder (ME_ERR_STATE when there is nothing to solve); selects its device
+  int from_engine(me_engine *engine);
+  // checks the host arrays and uploads them to device `device_id`; the second form also takes columns [n_columns][n_samples]
+  int from_host(int device_id, const double *energies, const int32_t *rungs, int64_t n_samples, const double *temps, int n);
+  int from_host(int device_id, const double *energies, const int32_t *rungs, int64_t n_samples, const double *temps, int n,
+                const double *observables, int n_columns);
+  // the end of a host-form entry point: waits for the device before the buffers go, and passes `rc` on
+  int finish(int rc) const;
+};
+
+// One prepared problem: the samples with their N_k counted and the ladder's table on the device.
+struct Problem {
+  MbarSamples sm{};
+  int n_rungs = 0;
+  hipStream_t stream = nullptr;
+  Work w;
+  unsigned long long counts[kK] = {};             // N_k
+  int empty_rung = -1;                            // the first rung without a finite sample
+  double n_used = 0.0;                            // the sum of the N_k, added as double ...
+  long long n_used_ll = 0;                        // ... and as integers
+};
+// hipErrorInvalidValue unless 1 <= n_rungs <= kK and there is a sample.  Then the N_k (waits for the stream) and, unless a rung
+// is empty (p.empty_rung >= 0 with hipSuccess: nothing else is to be computed), n_used and the table for the free energies f
+// (nullptr: zeros; waits again).
+hipError_t prepare(Problem &p, const Source &src, const double *f);
+// 1 / T_t of temps[0 .. n) into `inv` and on its way to p.w.inv_temps; p.w.out sized to out_doubles.  Does not wait: `inv` is the
+// caller's to keep until the stream has been waited for.
+hipError_t upload_targets(Problem &p, const double *temps, int n, size_t out_doubles, std::vector<double> &inv);
+// Enqueues the reweighting of `sm` (the problem's samples, or the used ones of them packed) to temps[0 .. n_temps): afterwards
+// p.w.inv_temps[t] = 1 / T_t and p.w.out[4 t ..] = (ln_z, mean_e, var_e, neff_fraction) of T_t on the device.  Does not wait
+// (`inv`: see upload_targets).
+hipError_t reweight_enqueue(Problem &p, const MbarSamples &sm, const double *temps, int n_temps, std::vector<double> &inv);
+// the host copy `out` of such a p.w.out into those of the four arrays that are not nullptr
+void unpack_targets(const std::vector<double> &out, int n_temps, double *ln_z, double *mean_e, double *var_e, double *neff_fraction);
+// ME_ERR_INVALID unless f[0 .. n_rungs) is there and finite, n >= min_targets and temps[0 .. n) is there, finite and > 0
+int check_f_and_targets(me_engine *e, const double *f, int n_rungs, const double *temps, int n, int min_targets);
+// what an operation on `p` returned, or p's empty rung, as the ME_* code of an entry point
+int mbar_check_common(me_engine *e, const Problem &p, hipError_t err);
 int mbar_check_temps(me_engine *e, const double *temps, int n, const char *what);
-// the engine's store as an MBAR problem (ME_ERR_STATE when there is nothing to solve)
-int engine_samples(me_engine *e, MbarSamples &sm);
-// host samples of the engine-less forms on the device (`energies_dev`, `rungs_dev`: theirs for the length of the call)
-int upload_samples(int device_id, const double *energies, const int32_t *rungs, int64_t n_samples, const double *ladder_temps,
-                   int n_rungs, DeviceBuffer &energies_dev, DeviceBuffer &rungs_dev, MbarSamples &sm);
 
 // ---- defined in me_mbar_obs.hip -----------------------------------------------------------------------------------------
 // me_energy_samples_record's second kernel: row `row` of the engine's observable store (which exists) on the engine's stream

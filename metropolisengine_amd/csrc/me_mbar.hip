@@ -68,12 +68,6 @@ __global__ void __launch_bounds__(kThreads) k_mbar_count(const double *__restric
   if (threadIdx.x < n_rungs && local[threadIdx.x]) atomicAdd(&counts[threadIdx.x], (unsigned long long)local[threadIdx.x]);
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v = v + __shfl_xor(v, d);
-  return v;
-}
-
 // the block's sum of every lane's acc[0 .. kChunk) added to total[c0 ..): wavefront butterfly, then the wavefronts in order
 __device__ __forceinline__ void flush_chunk(double (&acc)[kChunk], int c0, int n_rungs, double (*red)[kChunk], double *total) {
 #pragma unroll
@@ -315,132 +309,82 @@ __global__ void __launch_bounds__(kThreads) k_mbar_reweight_finish(const Moments
 
 }  // namespace
 
-// ---- host side --------------------------------------------------------------------------------------------------------
-// N_k into host `counts`; *empty_rung = the first rung without a finite sample or -1
-hipError_t count_used(const MbarSamples &sm, int n_rungs, Work &w, std::vector<unsigned long long> &counts, int *empty_rung,
-                      hipStream_t stream) {
-  ME_MBAR_HIP(w.counts.resize(kK * sizeof(unsigned long long)));
-  ME_MBAR_HIP(hipMemsetAsync(w.counts.get(), 0, w.counts.bytes(), stream));
-  hipLaunchKernelGGL(k_mbar_count, dim3(blocks_of(sm.n_samples)), dim3(kThreads), 0, stream, sm.energies, sm.rungs, sm.n_samples,
-                     sm.n_chains, sm.rung_chains, n_rungs, w.counts.get<unsigned long long>());
-  ME_MBAR_HIP(hipGetLastError());
-  counts.assign(kK, 0);
-  ME_MBAR_HIP(hipMemcpyAsync(counts.data(), w.counts.get(), kK * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-  ME_MBAR_HIP(hipStreamSynchronize(stream));
-  *empty_rung = -1;
-  for (int k = n_rungs - 1; k >= 0; --k)
-    if (counts[k] == 0) *empty_rung = k;
-  return hipSuccess;
-}
 
-// the device table for free energies f
-hipError_t upload_table(Work &w, const double *ladder_temps, int n_rungs, const std::vector<unsigned long long> &counts,
-                        const double *f, hipStream_t stream) {
+// ---- host side --------------------------------------------------------------------------------------------------------
+hipError_t prepare(Problem &p, const Source &src, const double *f) {
+  p.sm = src.sm;
+  p.n_rungs = src.n_rungs;
+  p.stream = src.stream;
+  Work &w = p.w;
+  const int n_rungs = p.n_rungs;
+  if (n_rungs < 1 || n_rungs > kK || p.sm.n_samples < 1) return hipErrorInvalidValue;
+  // N_k: the finite samples of every rung
+  ME_MBAR_HIP(w.counts.resize(kK * sizeof(unsigned long long)));
+  ME_MBAR_HIP(hipMemsetAsync(w.counts.get(), 0, w.counts.bytes(), p.stream));
+  hipLaunchKernelGGL(k_mbar_count, dim3(blocks_of(p.sm.n_samples)), dim3(kThreads), 0, p.stream, p.sm.energies, p.sm.rungs,
+                     p.sm.n_samples, p.sm.n_chains, p.sm.rung_chains, n_rungs, w.counts.get<unsigned long long>());
+  ME_MBAR_HIP(hipGetLastError());
+  ME_MBAR_HIP(hipMemcpyAsync(p.counts, w.counts.get(), kK * sizeof(unsigned long long), hipMemcpyDeviceToHost, p.stream));
+  ME_MBAR_HIP(hipStreamSynchronize(p.stream));
+  p.empty_rung = -1;
+  for (int k = n_rungs - 1; k >= 0; --k)
+    if (p.counts[k] == 0) p.empty_rung = k;
+  if (p.empty_rung >= 0) return hipSuccess;
+  for (int k = 0; k < n_rungs; ++k) {
+    p.n_used += (double)p.counts[k];
+    p.n_used_ll += (long long)p.counts[k];
+  }
+  // the device table for the free energies f
   std::vector<double> table(kTableDoubles, 0.0);
   for (int k = 0; k < n_rungs; ++k) {
-    table[kBeta + k] = 1.0 / ladder_temps[k];
-    table[kN + k] = (double)counts[k];
-    table[kLnN + k] = std::log((double)counts[k]);
+    table[kBeta + k] = 1.0 / src.ladder_temps[k];
+    table[kN + k] = (double)p.counts[k];
+    table[kLnN + k] = std::log((double)p.counts[k]);
     table[kF + k] = f ? f[k] : 0.0;
     table[kC + k] = table[kLnN + k] + table[kF + k];
   }
   ME_MBAR_HIP(w.table.resize(kTableDoubles * sizeof(double)));
-  ME_MBAR_HIP(hipMemcpyAsync(w.table.get(), table.data(), kTableDoubles * sizeof(double), hipMemcpyHostToDevice, stream));
-  ME_MBAR_HIP(hipStreamSynchronize(stream));      // `table` leaves scope
-  return hipSuccess;
+  ME_MBAR_HIP(hipMemcpyAsync(w.table.get(), table.data(), kTableDoubles * sizeof(double), hipMemcpyHostToDevice, p.stream));
+  return hipStreamSynchronize(p.stream);          // `table` leaves scope
 }
 
-hipError_t reweight_enqueue(const MbarSamples &sm, int n_rungs, Work &w, const double *temps, int n_temps, double n_used,
-                            std::vector<double> &inv, hipStream_t stream) {
+hipError_t upload_targets(Problem &p, const double *temps, int n, size_t out_doubles, std::vector<double> &inv) {
+  inv.resize((size_t)n);
+  for (int t = 0; t < n; ++t) inv[t] = 1.0 / temps[t];
+  ME_MBAR_HIP(p.w.inv_temps.resize(inv.size() * sizeof(double)));
+  ME_MBAR_HIP(p.w.out.resize(out_doubles * sizeof(double)));
+  return hipMemcpyAsync(p.w.inv_temps.get(), inv.data(), inv.size() * sizeof(double), hipMemcpyHostToDevice, p.stream);
+}
+
+hipError_t reweight_enqueue(Problem &p, const MbarSamples &sm, const double *temps, int n_temps, std::vector<double> &inv) {
+  Work &w = p.w;
   const int n_blocks = blocks_of(sm.n_samples);
   const long long n_tiles = tiles_of(sm.n_samples);
-  inv.resize((size_t)n_temps);
-  for (int t = 0; t < n_temps; ++t) inv[t] = 1.0 / temps[t];
-  ME_MBAR_HIP(w.inv_temps.resize(inv.size() * sizeof(double)));
-  ME_MBAR_HIP(w.out.resize(4 * inv.size() * sizeof(double)));
   ME_MBAR_HIP(w.moments.resize((size_t)n_blocks * kTargets * sizeof(Moments)));
-  ME_MBAR_HIP(hipMemcpyAsync(w.inv_temps.get(), inv.data(), inv.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+  ME_MBAR_HIP(upload_targets(p, temps, n_temps, 4 * (size_t)n_temps, inv));
   for (int t0 = 0; t0 < n_temps; t0 += kTargets) {
     const int nt = std::min(kTargets, n_temps - t0);
-    hipLaunchKernelGGL(k_mbar_reweight, dim3(n_blocks), dim3(kThreads), 0, stream, sm.energies, sm.n_samples, n_rungs,
+    hipLaunchKernelGGL(k_mbar_reweight, dim3(n_blocks), dim3(kThreads), 0, p.stream, sm.energies, sm.n_samples, p.n_rungs,
                        w.table.get<const double>(), w.inv_temps.get<const double>() + t0, nt, n_tiles, w.moments.get<Moments>());
-    hipLaunchKernelGGL(k_mbar_reweight_finish, dim3(nt), dim3(kThreads), 0, stream, w.moments.get<const Moments>(), n_blocks, n_used,
-                       w.out.get<double>() + 4 * (size_t)t0);
+    hipLaunchKernelGGL(k_mbar_reweight_finish, dim3(nt), dim3(kThreads), 0, p.stream, w.moments.get<const Moments>(), n_blocks,
+                       p.n_used, w.out.get<double>() + 4 * (size_t)t0);
   }
   return hipGetLastError();
 }
 
-namespace {
-
-// Both wait for the stream and write host arrays.  *empty_rung = the first rung without a finite sample (nothing else is
-// computed then), or -1.  mbar_solve: f[K], n_used[K].  mbar_reweight: any of the four outputs may be nullptr.
-hipError_t mbar_solve(const MbarSamples &sm, const double *ladder_temps, int n_rungs, double tolerance, int max_iterations,
-                      double *f, int *iterations, double *residual, long long *n_used, int *empty_rung, hipStream_t stream) {
-  if (n_rungs < 1 || n_rungs > kK || sm.n_samples < 1) return hipErrorInvalidValue;
-  Work w;
-  std::vector<unsigned long long> counts;
-  ME_MBAR_HIP(count_used(sm, n_rungs, w, counts, empty_rung, stream));
-  for (int k = 0; k < n_rungs; ++k) n_used[k] = (long long)counts[k];
-  if (*empty_rung >= 0) return hipSuccess;
-  ME_MBAR_HIP(upload_table(w, ladder_temps, n_rungs, counts, nullptr, stream));
-  const int n_blocks = blocks_of(sm.n_samples);
-  const long long n_tiles = tiles_of(sm.n_samples);
-  ME_MBAR_HIP(w.partials.resize((size_t)n_blocks * n_rungs * sizeof(double)));
-  ME_MBAR_HIP(w.control.resize(sizeof(MbarControl)));
-  ME_MBAR_HIP(hipMemsetAsync(w.control.get(), 0, sizeof(MbarControl), stream));
-  MbarControl c{0.0, 0, 0};
-  while (c.iterations < max_iterations && !c.done) {
-    const int batch = std::min(kBatch, max_iterations - c.iterations);
-    for (int it = 0; it < batch; ++it) {
-      hipLaunchKernelGGL(k_mbar_weights, dim3(n_blocks), dim3(kThreads), 0, stream, sm.energies, sm.n_samples, n_rungs,
-                         w.table.get<const double>(), w.control.get<const MbarControl>(), n_tiles, w.partials.get<double>());
-      hipLaunchKernelGGL(k_mbar_update, dim3(1), dim3(kUpdateThreads), 0, stream, w.partials.get<const double>(), n_blocks, n_rungs,
-                         tolerance, w.table.get<double>(), w.control.get<MbarControl>());
-    }
-    ME_MBAR_HIP(hipGetLastError());
-    ME_MBAR_HIP(hipMemcpyAsync(&c, w.control.get(), sizeof(MbarControl), hipMemcpyDeviceToHost, stream));
-    ME_MBAR_HIP(hipStreamSynchronize(stream));
-  }
-  ME_MBAR_HIP(hipMemcpyAsync(f, w.table.get<double>() + kF, (size_t)n_rungs * sizeof(double), hipMemcpyDeviceToHost, stream));
-  ME_MBAR_HIP(hipStreamSynchronize(stream));
-  *iterations = c.iterations;
-  *residual = c.residual;
-  return hipSuccess;
+void unpack_targets(const std::vector<double> &out, int n_temps, double *ln_z, double *mean_e, double *var_e, double *neff_fraction) {
+  double *const dst[4] = {ln_z, mean_e, var_e, neff_fraction};
+  for (int j = 0; j < 4; ++j)
+    for (int t = 0; dst[j] && t < n_temps; ++t) dst[j][t] = out[4 * (size_t)t + j];
 }
 
-hipError_t mbar_reweight(const MbarSamples &sm, const double *ladder_temps, int n_rungs, const double *f, const double *temps,
-                         int n_temps, double *ln_z, double *mean_e, double *var_e, double *neff_fraction, int *empty_rung,
-                         hipStream_t stream) {
-  if (n_rungs < 1 || n_rungs > kK || sm.n_samples < 1 || n_temps < 1) return hipErrorInvalidValue;
-  Work w;
-  std::vector<unsigned long long> counts;
-  ME_MBAR_HIP(count_used(sm, n_rungs, w, counts, empty_rung, stream));
-  if (*empty_rung >= 0) return hipSuccess;
-  double n_used = 0.0;
-  for (int k = 0; k < n_rungs; ++k) n_used += (double)counts[k];
-  ME_MBAR_HIP(upload_table(w, ladder_temps, n_rungs, counts, f, stream));
-  std::vector<double> inv, out(4 * (size_t)n_temps);
-  ME_MBAR_HIP(reweight_enqueue(sm, n_rungs, w, temps, n_temps, n_used, inv, stream));
-  ME_MBAR_HIP(hipMemcpyAsync(out.data(), w.out.get(), out.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-  ME_MBAR_HIP(hipStreamSynchronize(stream));
-  for (int t = 0; t < n_temps; ++t) {
-    if (ln_z) ln_z[t] = out[4 * (size_t)t];
-    if (mean_e) mean_e[t] = out[4 * (size_t)t + 1];
-    if (var_e) var_e[t] = out[4 * (size_t)t + 2];
-    if (neff_fraction) neff_fraction[t] = out[4 * (size_t)t + 3];
-  }
-  return hipSuccess;
-}
-
-}  // namespace
-
-// ---- entry points: energy samples, MBAR free energies and reweighting --------------------------------------------------
-int mbar_check_common(me_engine *e, int n_rungs, int empty_rung, hipError_t err) {
+// ---- what the entry points share ----------------------------------------------------------------------------------------
+int mbar_check_common(me_engine *e, const Problem &p, hipError_t err) {
   if (err == hipErrorInvalidValue)
     return fail(e, ME_ERR_UNSUPPORTED, "MBAR supports 1 to " + std::to_string(kK) + " rungs and at least one sample");
   ME_HIP(e, err);
-  if (empty_rung >= 0)
-    return fail(e, ME_ERR_STATE, "rung " + std::to_string(empty_rung) + " of " + std::to_string(n_rungs) +
+  if (p.empty_rung >= 0)
+    return fail(e, ME_ERR_STATE, "rung " + std::to_string(p.empty_rung) + " of " + std::to_string(p.n_rungs) +
                                      " has no sample with a finite energy: MBAR needs every rung sampled");
   return ME_OK;
 }
@@ -449,66 +393,136 @@ int mbar_check_temps(me_engine *e, const double *temps, int n, const char *what)
     if (!(std::isfinite(temps[k]) && temps[k] > 0)) return fail(e, ME_ERR_INVALID, std::string(what) + " must be finite and > 0");
   return ME_OK;
 }
-// the engine's store as an MBAR problem (ME_ERR_STATE when there is nothing to solve)
-int engine_samples(me_engine *e, MbarSamples &sm) {
+int check_f_and_targets(me_engine *e, const double *f, int n_rungs, const double *temps, int n, int min_targets) {
+  if (!f || n < min_targets || (n > 0 && !temps))
+    return fail(e, ME_ERR_INVALID, min_targets > 0 ? "f and at least one target temperature are needed"
+                                                   : "f and n_targets >= 0 temperatures are needed");
+  const int rc = mbar_check_temps(e, temps, n, "target temperatures");
+  if (rc) return rc;
+  for (int k = 0; k < n_rungs; ++k)
+    if (!std::isfinite(f[k])) return fail(e, ME_ERR_INVALID, "f must be finite");
+  return ME_OK;
+}
+
+int Source::from_engine(me_engine *engine) {
+  if (!engine) return ME_ERR_INVALID;
+  e = engine;
   if (e->ladder.n_rungs == 0) return fail(e, ME_ERR_STATE, "no temperature ladder: MBAR combines the rungs of me_set_temperature_ladder");
   if (!e->samples.data || e->samples.rows == 0)
     return fail(e, ME_ERR_STATE, "no recorded energy samples: me_energy_samples_enable, then me_energy_samples_record");
-  sm.energies = e->samples.data.get<double>();
-  sm.rungs = nullptr;
-  sm.n_samples = e->samples.rows * e->n;
-  sm.n_chains = e->n;
-  sm.rung_chains = e->n / e->ladder.n_rungs;
+  sm = MbarSamples{e->samples.data.get<double>(), nullptr, e->samples.rows * e->n, e->n, e->n / e->ladder.n_rungs};
+  ladder_temps = e->ladder.temps.data();
+  n_rungs = e->ladder.n_rungs;
+  stream = e->stream;
+  columns = ObsColumns{e->samples.obs.get<const double>(), e->samples.n_obs, e->n, (long long)e->samples.n_obs * e->n, e->n};
+  ME_HIP(e, hipSetDevice(e->device));
   return ME_OK;
 }
-// host samples of the engine-less forms on the device (`energies_dev`, `rungs_dev`: theirs for the length of the call)
-int upload_samples(int device_id, const double *energies, const int32_t *rungs, int64_t n_samples, const double *ladder_temps,
-                   int n_rungs, DeviceBuffer &energies_dev, DeviceBuffer &rungs_dev, MbarSamples &sm) {
-  if (!energies || !rungs || !ladder_temps) return fail(nullptr, ME_ERR_INVALID, "null pointer");
-  if (n_samples < 1 || n_rungs < 1) return fail(nullptr, ME_ERR_INVALID, "need n_samples >= 1 and n_rungs >= 1");
-  int rc = mbar_check_temps(nullptr, ladder_temps, n_rungs, "ladder temperatures");
+int Source::from_host(int device_id, const double *energies, const int32_t *rungs, int64_t n_samples, const double *temps, int n) {
+  if (!energies || !rungs || !temps) return fail(nullptr, ME_ERR_INVALID, "null pointer");
+  if (n_samples < 1 || n < 1) return fail(nullptr, ME_ERR_INVALID, "need n_samples >= 1 and n_rungs >= 1");
+  const int rc = mbar_check_temps(nullptr, temps, n, "ladder temperatures");
   if (rc) return rc;
   for (int64_t i = 0; i < n_samples; ++i)
-    if (rungs[i] < 0 || rungs[i] >= n_rungs) return fail(nullptr, ME_ERR_INVALID, "rungs must lie in [0, n_rungs)");
+    if (rungs[i] < 0 || rungs[i] >= n) return fail(nullptr, ME_ERR_INVALID, "rungs must lie in [0, n_rungs)");
   ME_HIP(nullptr, hipSetDevice(device_id));
   ME_HIP(nullptr, energies_dev.resize(sizeof(double) * (size_t)n_samples));
   ME_HIP(nullptr, rungs_dev.resize(sizeof(int) * (size_t)n_samples));
   ME_HIP(nullptr, hipMemcpy(energies_dev.get(), energies, energies_dev.bytes(), hipMemcpyHostToDevice));
   ME_HIP(nullptr, hipMemcpy(rungs_dev.get(), rungs, rungs_dev.bytes(), hipMemcpyHostToDevice));
-  sm.energies = energies_dev.get<double>();
-  sm.rungs = rungs_dev.get<int>();
-  sm.n_samples = n_samples;
-  sm.n_chains = sm.rung_chains = 1;
+  sm = MbarSamples{energies_dev.get<double>(), rungs_dev.get<int>(), n_samples, 1, 1};
+  ladder_temps = temps;
+  n_rungs = n;
   return ME_OK;
 }
+int Source::from_host(int device_id, const double *energies, const int32_t *rungs, int64_t n_samples, const double *temps, int n,
+                      const double *observables, int n_columns) {
+  if (!observables) return fail(nullptr, ME_ERR_INVALID, "null pointer");
+  if (n_columns < 1 || n_columns > ME_MAX_RECORDED_OBSERVABLES)
+    return fail(nullptr, ME_ERR_INVALID, "n_observables must lie in [1, " + std::to_string(ME_MAX_RECORDED_OBSERVABLES) + "]");
+  const int rc = from_host(device_id, energies, rungs, n_samples, temps, n);
+  if (rc) return rc;
+  ME_HIP(nullptr, columns_dev.resize(sizeof(double) * (size_t)n_samples * (size_t)n_columns));
+  ME_HIP(nullptr, hipMemcpy(columns_dev.get(), observables, columns_dev.bytes(), hipMemcpyHostToDevice));
+  columns = ObsColumns{columns_dev.get<const double>(), n_columns, n_samples, 0, n_samples};
+  return ME_OK;
+}
+int Source::finish(int rc) const {
+  (void)hipDeviceSynchronize();
+  return rc;
+}
+
 namespace {
-int solve_common(me_engine *e, const MbarSamples &sm, const double *ladder_temps, int n_rungs, double tolerance, int max_iterations,
-                 double *f_out, int32_t *iterations, double *residual, int64_t *n_used_out, hipStream_t stream) {
-  if (!f_out) return fail(e, ME_ERR_INVALID, "f_out missing");
-  if (!(tolerance > 0) || max_iterations < 1) return fail(e, ME_ERR_INVALID, "need tolerance > 0 and max_iterations >= 1");
-  std::vector<long long> used((size_t)std::max(n_rungs, 1));
-  int its = 0, empty = -1;
+
+// Both wait for the stream and write host arrays; with an empty rung (p.empty_rung) nothing else is computed.
+// mbar_solve: f[K].  mbar_reweight: any of the four outputs may be nullptr.
+hipError_t mbar_solve(Problem &p, const Source &src, double tolerance, int max_iterations, double *f, int *iterations, double *residual) {
+  ME_MBAR_HIP(prepare(p, src, nullptr));
+  if (p.empty_rung >= 0) return hipSuccess;
+  Work &w = p.w;
+  const int n_rungs = p.n_rungs, n_blocks = blocks_of(p.sm.n_samples);
+  const long long n_tiles = tiles_of(p.sm.n_samples);
+  ME_MBAR_HIP(w.partials.resize((size_t)n_blocks * n_rungs * sizeof(double)));
+  ME_MBAR_HIP(w.control.resize(sizeof(MbarControl)));
+  ME_MBAR_HIP(hipMemsetAsync(w.control.get(), 0, sizeof(MbarControl), p.stream));
+  MbarControl c{0.0, 0, 0};
+  while (c.iterations < max_iterations && !c.done) {
+    const int batch = std::min(kBatch, max_iterations - c.iterations);
+    for (int it = 0; it < batch; ++it) {
+      hipLaunchKernelGGL(k_mbar_weights, dim3(n_blocks), dim3(kThreads), 0, p.stream, p.sm.energies, p.sm.n_samples, n_rungs,
+                         w.table.get<const double>(), w.control.get<const MbarControl>(), n_tiles, w.partials.get<double>());
+      hipLaunchKernelGGL(k_mbar_update, dim3(1), dim3(kUpdateThreads), 0, p.stream, w.partials.get<const double>(), n_blocks, n_rungs,
+                         tolerance, w.table.get<double>(), w.control.get<MbarControl>());
+    }
+    ME_MBAR_HIP(hipGetLastError());
+    ME_MBAR_HIP(hipMemcpyAsync(&c, w.control.get(), sizeof(MbarControl), hipMemcpyDeviceToHost, p.stream));
+    ME_MBAR_HIP(hipStreamSynchronize(p.stream));
+  }
+  ME_MBAR_HIP(hipMemcpyAsync(f, w.table.get<double>() + kF, (size_t)n_rungs * sizeof(double), hipMemcpyDeviceToHost, p.stream));
+  ME_MBAR_HIP(hipStreamSynchronize(p.stream));
+  *iterations = c.iterations;
+  *residual = c.residual;
+  return hipSuccess;
+}
+
+hipError_t mbar_reweight(Problem &p, const Source &src, const double *f, const double *temps, int n_temps, double *ln_z, double *mean_e,
+                         double *var_e, double *neff_fraction) {
+  ME_MBAR_HIP(prepare(p, src, f));
+  if (p.empty_rung >= 0) return hipSuccess;
+  std::vector<double> inv, out(4 * (size_t)n_temps);
+  ME_MBAR_HIP(reweight_enqueue(p, p.sm, temps, n_temps, inv));
+  ME_MBAR_HIP(hipMemcpyAsync(out.data(), p.w.out.get(), out.size() * sizeof(double), hipMemcpyDeviceToHost, p.stream));
+  ME_MBAR_HIP(hipStreamSynchronize(p.stream));
+  unpack_targets(out, n_temps, ln_z, mean_e, var_e, neff_fraction);
+  return hipSuccess;
+}
+
+// the two forms of me_mbar_solve and of me_mbar_reweight behind their Source
+int solve_common(const Source &src, double tolerance, int max_iterations, double *f_out, int32_t *iterations, double *residual,
+                 int64_t *n_used_out) {
+  if (!f_out) return fail(src.e, ME_ERR_INVALID, "f_out missing");
+  if (!(tolerance > 0) || max_iterations < 1) return fail(src.e, ME_ERR_INVALID, "need tolerance > 0 and max_iterations >= 1");
+  Problem p;
+  int its = 0;
   double res = 0.0;
-  const hipError_t err = mbar_solve(sm, ladder_temps, n_rungs, tolerance, max_iterations, f_out, &its, &res, used.data(), &empty, stream);
-  if (err == hipSuccess && n_used_out)
-    for (int k = 0; k < n_rungs; ++k) n_used_out[k] = used[k];
-  const int rc = mbar_check_common(e, n_rungs, empty, err);
+  const hipError_t err = mbar_solve(p, src, tolerance, max_iterations, f_out, &its, &res);
+  if (err == hipSuccess && n_used_out)            // (also when a rung is empty: the message names one, these show all)
+    for (int k = 0; k < p.n_rungs; ++k) n_used_out[k] = (int64_t)p.counts[k];
+  const int rc = mbar_check_common(src.e, p, err);
   if (rc) return rc;
   if (iterations) *iterations = its;
   if (residual) *residual = res;
   return ME_OK;
 }
-int reweight_common(me_engine *e, const MbarSamples &sm, const double *ladder_temps, int n_rungs, const double *f, const double *temps,
-                    int n, double *ln_z, double *mean_e, double *var_e, double *neff_fraction, hipStream_t stream) {
-  if (!f || !temps || n < 1) return fail(e, ME_ERR_INVALID, "f and at least one target temperature are needed");
-  int rc = mbar_check_temps(e, temps, n, "target temperatures");
+
+int reweight_common(const Source &src, const double *f, const double *temps, int n, double *ln_z, double *mean_e, double *var_e,
+                    double *neff_fraction) {
+  const int rc = check_f_and_targets(src.e, f, src.n_rungs, temps, n, 1);
   if (rc) return rc;
-  for (int k = 0; k < n_rungs; ++k)
-    if (!std::isfinite(f[k])) return fail(e, ME_ERR_INVALID, "f must be finite");
-  int empty = -1;
-  const hipError_t err = mbar_reweight(sm, ladder_temps, n_rungs, f, temps, n, ln_z, mean_e, var_e, neff_fraction, &empty, stream);
-  return mbar_check_common(e, n_rungs, empty, err);
+  Problem p;
+  return mbar_check_common(src.e, p, mbar_reweight(p, src, f, temps, n, ln_z, mean_e, var_e, neff_fraction));
 }
+
 }  // namespace
 }  // namespace mbar
 }  // namespace me
@@ -583,47 +597,32 @@ int me_energy_samples_set(me_engine *e, int64_t n_records, const double *src) {
 
 int me_mbar_solve(me_engine *e, double tolerance, int32_t max_iterations, double *f_out, int32_t *iterations, double *residual,
                   int64_t *n_used_out) {
-  if (!e) return ME_ERR_INVALID;
-  MbarSamples sm;
-  int rc = engine_samples(e, sm);
-  if (rc) return rc;
-  ME_HIP(e, hipSetDevice(e->device));
-  return solve_common(e, sm, e->ladder.temps.data(), e->ladder.n_rungs, tolerance, max_iterations, f_out, iterations, residual, n_used_out,
-                      e->stream);
+  Source src;
+  const int rc = src.from_engine(e);
+  return rc ? rc : solve_common(src, tolerance, max_iterations, f_out, iterations, residual, n_used_out);
 }
 
 int me_mbar_reweight(me_engine *e, const double *f, const double *temps, int32_t n, double *ln_z, double *mean_e, double *var_e,
                      double *neff_fraction) {
-  if (!e) return ME_ERR_INVALID;
-  MbarSamples sm;
-  int rc = engine_samples(e, sm);
-  if (rc) return rc;
-  ME_HIP(e, hipSetDevice(e->device));
-  return reweight_common(e, sm, e->ladder.temps.data(), e->ladder.n_rungs, f, temps, n, ln_z, mean_e, var_e, neff_fraction, e->stream);
+  Source src;
+  const int rc = src.from_engine(e);
+  return rc ? rc : reweight_common(src, f, temps, n, ln_z, mean_e, var_e, neff_fraction);
 }
 
 int me_mbar_solve_samples(int32_t device_id, const double *energies, const int32_t *rungs, int64_t n_samples,
                           const double *ladder_temps, int32_t n_rungs, double tolerance, int32_t max_iterations, double *f_out,
                           int32_t *iterations, double *residual, int64_t *n_used_out) {
-  DeviceBuffer energies_dev, rungs_dev;
-  MbarSamples sm;
-  int rc = upload_samples(device_id, energies, rungs, n_samples, ladder_temps, n_rungs, energies_dev, rungs_dev, sm);
-  if (rc) return rc;
-  rc = solve_common(nullptr, sm, ladder_temps, n_rungs, tolerance, max_iterations, f_out, iterations, residual, n_used_out, nullptr);
-  (void)hipDeviceSynchronize();
-  return rc;
+  Source src;
+  const int rc = src.from_host(device_id, energies, rungs, n_samples, ladder_temps, n_rungs);
+  return rc ? rc : src.finish(solve_common(src, tolerance, max_iterations, f_out, iterations, residual, n_used_out));
 }
 
 int me_mbar_reweight_samples(int32_t device_id, const double *energies, const int32_t *rungs, int64_t n_samples,
                              const double *ladder_temps, int32_t n_rungs, const double *f, const double *temps, int32_t n,
                              double *ln_z, double *mean_e, double *var_e, double *neff_fraction) {
-  DeviceBuffer energies_dev, rungs_dev;
-  MbarSamples sm;
-  int rc = upload_samples(device_id, energies, rungs, n_samples, ladder_temps, n_rungs, energies_dev, rungs_dev, sm);
-  if (rc) return rc;
-  rc = reweight_common(nullptr, sm, ladder_temps, n_rungs, f, temps, n, ln_z, mean_e, var_e, neff_fraction, nullptr);
-  (void)hipDeviceSynchronize();
-  return rc;
+  Source src;
+  const int rc = src.from_host(device_id, energies, rungs, n_samples, ladder_temps, n_rungs);
+  return rc ? rc : src.finish(reweight_common(src, f, temps, n, ln_z, mean_e, var_e, neff_fraction));
 }
 
 }  // extern "C"

@@ -47,12 +47,6 @@ constexpr int kColB = 0, kColG = kMaxCols, kColMean = 2 * kMaxCols, kColShift = 
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v = fmin(v, __shfl_xor(v, d));
-  return v;
-}
-
 // counts[tile] = the finite energies of the tile
 __global__ void __launch_bounds__(kThreads) k_mbar_used_tiles(const double *__restrict__ energies, long long n, unsigned int *counts) {
   __shared__ unsigned int total;
@@ -268,29 +262,22 @@ int padded_row(int n_cols) {
 }
 
 // Waits for the stream and writes host arrays: gram[C][C] (C = n_rungs + 2 n_targets; the target-target blocks of targets
-// from different chunks are NaN), column_counts[C], ln_z / mean_e[n_targets] (may be nullptr), *n_used.  *empty_rung = the
-// first rung without a finite sample (nothing else is computed then), or -1.
-hipError_t mbar_gram(const MbarSamples &sm, const double *ladder_temps, int n_rungs, const double *f, const double *temps,
-                     int n_targets, double *gram, double *column_counts, double *ln_z, double *mean_e, long long *n_used,
-                     int *empty_rung, hipStream_t stream) {
-  if (n_rungs < 1 || n_rungs > kK || sm.n_samples < 1) return hipErrorInvalidValue;
-  Work w;
-  std::vector<unsigned long long> counts;
-  ME_MBAR_HIP(count_used(sm, n_rungs, w, counts, empty_rung, stream));
-  if (*empty_rung >= 0) return hipSuccess;
-  double used = 0.0;
-  long long used_ll = 0;
-  for (int k = 0; k < n_rungs; ++k) {
-    used += (double)counts[k];
-    used_ll += (long long)counts[k];
-  }
-  ME_MBAR_HIP(upload_table(w, ladder_temps, n_rungs, counts, f, stream));
+// from different chunks are NaN), column_counts[C], ln_z / mean_e[n_targets] (may be nullptr).  With an empty rung
+// (p.empty_rung) nothing else is computed.
+hipError_t mbar_gram(Problem &p, const Source &src, const double *f, const double *temps, int n_targets, double *gram,
+                     double *column_counts, double *ln_z, double *mean_e) {
+  ME_MBAR_HIP(prepare(p, src, f));
+  if (p.empty_rung >= 0) return hipSuccess;
+  Work &w = p.w;
+  const MbarSamples &sm = p.sm;
+  const int n_rungs = p.n_rungs;
+  hipStream_t stream = p.stream;
   // the used samples alone, in their order (the rungs are in the counts already)
-  MbarSamples packed_samples{sm.energies, nullptr, used_ll, 1, 1};
+  MbarSamples packed_samples{sm.energies, nullptr, p.n_used_ll, 1, 1};
   DeviceBuffer packed, tile_counts, tile_offsets;
-  if (used_ll != sm.n_samples) {
+  if (p.n_used_ll != sm.n_samples) {
     const long long all_tiles = tiles_of(sm.n_samples);
-    ME_MBAR_HIP(packed.resize((size_t)used_ll * sizeof(double)));
+    ME_MBAR_HIP(packed.resize((size_t)p.n_used_ll * sizeof(double)));
     ME_MBAR_HIP(tile_counts.resize((size_t)all_tiles * sizeof(unsigned int)));
     ME_MBAR_HIP(tile_offsets.resize((size_t)all_tiles * sizeof(long long)));
     hipLaunchKernelGGL(k_mbar_used_tiles, dim3((unsigned)all_tiles), dim3(kThreads), 0, stream, sm.energies, sm.n_samples,
@@ -304,7 +291,7 @@ hipError_t mbar_gram(const MbarSamples &sm, const double *ladder_temps, int n_ru
   }
   const MbarSamples &ps = packed_samples;
   std::vector<double> inv;                                        // (on its way to the device until the wait below)
-  if (n_targets > 0) ME_MBAR_HIP(reweight_enqueue(ps, n_rungs, w, temps, n_targets, used, inv, stream));
+  if (n_targets > 0) ME_MBAR_HIP(reweight_enqueue(p, ps, temps, n_targets, inv));
   const int n_blocks = blocks_of(ps.n_samples);
   const long long n_tiles = tiles_of(ps.n_samples);
   const int per_chunk = (kMaxCols - n_rungs) / 2;                 // targets of one pass: K + 2 per_chunk <= kMaxCols
@@ -336,17 +323,13 @@ hipError_t mbar_gram(const MbarSamples &sm, const double *ladder_temps, int n_ru
   std::fill(gram, gram + (size_t)n_all * n_all, (double)NAN);
   for (int c = 0; c < n_chunks; ++c) {
     const int t0 = c * per_chunk, nt = std::min(per_chunk, n_targets - t0), n_cols = n_rungs + 2 * nt;
-    const double *src = host.data() + (size_t)c * kMaxCols * kMaxCols;
+    const double *chunk = host.data() + (size_t)c * kMaxCols * kMaxCols;
     auto global = [&](int l) { return l < n_rungs ? l : l + 2 * t0; };
     for (int i = 0; i < n_cols; ++i)
-      for (int j = 0; j < n_cols; ++j) gram[(size_t)global(i) * n_all + global(j)] = src[i * n_cols + j];
+      for (int j = 0; j < n_cols; ++j) gram[(size_t)global(i) * n_all + global(j)] = chunk[i * n_cols + j];
   }
-  for (int k = 0; k < n_all; ++k) column_counts[k] = k < n_rungs ? (double)counts[k] : 0.0;
-  for (int t = 0; t < n_targets; ++t) {
-    if (ln_z) ln_z[t] = out[4 * (size_t)t];
-    if (mean_e) mean_e[t] = out[4 * (size_t)t + 1];
-  }
-  if (n_used) *n_used = used_ll;
+  for (int k = 0; k < n_all; ++k) column_counts[k] = k < n_rungs ? (double)p.counts[k] : 0.0;
+  unpack_targets(out, n_targets, ln_z, mean_e, nullptr, nullptr);
   return hipSuccess;
 }
 
@@ -365,20 +348,17 @@ hipError_t energy_shift(const MbarSamples &sm, double *shift, hipStream_t stream
   return hipStreamSynchronize(stream);
 }
 
-int gram_common(me_engine *e, const MbarSamples &sm, const double *ladder_temps, int n_rungs, const double *f, const double *temps,
-                int n_targets, double *gram, double *column_counts, double *ln_z, double *mean_e, int64_t *n_used, hipStream_t stream) {
-  if (!f || !gram || !column_counts || n_targets < 0 || (n_targets > 0 && !temps))
-    return fail(e, ME_ERR_INVALID, "f, gram, column_counts and n_targets >= 0 temperatures are needed");
-  int rc = mbar_check_temps(e, temps, n_targets, "target temperatures");
+// the two forms of me_mbar_gram behind their Source
+int gram_common(const Source &src, const double *f, const double *temps, int n_targets, double *gram, double *column_counts,
+                double *ln_z, double *mean_e, int64_t *n_used) {
+  if (!gram || !column_counts) return fail(src.e, ME_ERR_INVALID, "gram and column_counts are needed");
+  // (only the first kK entries of f are looked at before the number of rungs is refused)
+  int rc = check_f_and_targets(src.e, f, std::min(src.n_rungs, kK), temps, n_targets, 0);
   if (rc) return rc;
-  for (int k = 0; k < n_rungs && k < kK; ++k)
-    if (!std::isfinite(f[k])) return fail(e, ME_ERR_INVALID, "f must be finite");
-  int empty = -1;
-  long long used = 0;
-  const hipError_t err = mbar_gram(sm, ladder_temps, n_rungs, f, temps, n_targets, gram, column_counts, ln_z, mean_e, &used, &empty, stream);
-  rc = mbar_check_common(e, n_rungs, empty, err);
+  Problem p;
+  rc = mbar_check_common(src.e, p, mbar_gram(p, src, f, temps, n_targets, gram, column_counts, ln_z, mean_e));
   if (rc) return rc;
-  if (n_used) *n_used = used;
+  if (n_used) *n_used = p.n_used_ll;
   return ME_OK;
 }
 
@@ -393,23 +373,18 @@ extern "C" {
 
 int me_mbar_gram(me_engine *e, const double *f, const double *temps, int32_t n_targets, double *gram, double *column_counts,
                  double *ln_z, double *mean_e, int64_t *n_used) {
-  if (!e) return ME_ERR_INVALID;
-  MbarSamples sm;
-  int rc = engine_samples(e, sm);
-  if (rc) return rc;
-  ME_HIP(e, hipSetDevice(e->device));
-  return gram_common(e, sm, e->ladder.temps.data(), e->ladder.n_rungs, f, temps, n_targets, gram, column_counts, ln_z, mean_e, n_used,
-                     e->stream);
+  Source src;
+  const int rc = src.from_engine(e);
+  return rc ? rc : gram_common(src, f, temps, n_targets, gram, column_counts, ln_z, mean_e, n_used);
 }
 
 int me_mbar_energy_shift(me_engine *e, double *shift) {
   if (!e) return ME_ERR_INVALID;
   if (!shift) return fail(e, ME_ERR_INVALID, "shift missing");
-  MbarSamples sm;
-  int rc = engine_samples(e, sm);
+  Source src;
+  const int rc = src.from_engine(e);
   if (rc) return rc;
-  ME_HIP(e, hipSetDevice(e->device));
-  ME_HIP(e, energy_shift(sm, shift, e->stream));
+  ME_HIP(e, energy_shift(src.sm, shift, src.stream));
   if (!std::isfinite(*shift)) return fail(e, ME_ERR_STATE, "no recorded sample has a finite energy");
   return ME_OK;
 }
@@ -417,13 +392,9 @@ int me_mbar_energy_shift(me_engine *e, double *shift) {
 int me_mbar_gram_samples(int32_t device_id, const double *energies, const int32_t *rungs, int64_t n_samples,
                          const double *ladder_temps, int32_t n_rungs, const double *f, const double *temps, int32_t n_targets,
                          double *gram, double *column_counts, double *ln_z, double *mean_e, int64_t *n_used) {
-  DeviceBuffer energies_dev, rungs_dev;
-  MbarSamples sm;
-  int rc = upload_samples(device_id, energies, rungs, n_samples, ladder_temps, n_rungs, energies_dev, rungs_dev, sm);
-  if (rc) return rc;
-  rc = gram_common(nullptr, sm, ladder_temps, n_rungs, f, temps, n_targets, gram, column_counts, ln_z, mean_e, n_used, nullptr);
-  (void)hipDeviceSynchronize();
-  return rc;
+  Source src;
+  const int rc = src.from_host(device_id, energies, rungs, n_samples, ladder_temps, n_rungs);
+  return rc ? rc : src.finish(gram_common(src, f, temps, n_targets, gram, column_counts, ln_z, mean_e, n_used));
 }
 
 }  // extern "C"

@@ -308,35 +308,23 @@ __global__ void __launch_bounds__(kThreads) k_mbar_reweight_obs_finish(const Tar
   if (write_neff) neff[t] = (b.W * b.W) / (n_used * b.Q2);
 }
 
-// where the observable columns of an MBAR problem are (device memory)
-struct ObsColumns {
-  const double *data;
-  int n_columns;
-  long long n_chains, record_stride, column_stride;
-};
-
-hipError_t reweight_observables(const MbarSamples &sm, const ObsColumns &oc, const double *ladder_temps, int n_rungs, const double *f,
-                                const double *temps, int n_temps, double *mean, double *var, double *cov, double *neff,
-                                int *empty_rung, hipStream_t stream) {
-  if (n_rungs < 1 || n_rungs > kK || sm.n_samples < 1 || n_temps < 1) return hipErrorInvalidValue;
-  Work w;
-  std::vector<unsigned long long> counts;
-  ME_MBAR_HIP(count_used(sm, n_rungs, w, counts, empty_rung, stream));
-  if (*empty_rung >= 0) return hipSuccess;
-  double n_used = 0.0;
-  for (int k = 0; k < n_rungs; ++k) n_used += (double)counts[k];
-  ME_MBAR_HIP(upload_table(w, ladder_temps, n_rungs, counts, f, stream));
-  const int n_blocks = blocks_of(sm.n_samples), nq_all = oc.n_columns;
+hipError_t reweight_observables(Problem &p, const Source &src, const double *f, const double *temps, int n_temps, double *mean,
+                                double *var, double *cov, double *neff) {
+  ME_MBAR_HIP(prepare(p, src, f));
+  if (p.empty_rung >= 0) return hipSuccess;
+  const ObsColumns &oc = src.columns;
+  Work &w = p.w;
+  const MbarSamples &sm = p.sm;
+  hipStream_t stream = p.stream;
+  const double n_used = p.n_used;
+  const int n_rungs = p.n_rungs, n_blocks = blocks_of(sm.n_samples), nq_all = oc.n_columns;
   const long long n_tiles = tiles_of(sm.n_samples), n_padded = n_tiles * kTile;
-  std::vector<double> inv((size_t)n_temps);
-  for (int t = 0; t < n_temps; ++t) inv[t] = 1.0 / temps[t];
   const size_t cells = (size_t)n_temps * nq_all;
+  std::vector<double> inv;
   DeviceBuffer d, partials;
   ME_MBAR_HIP(d.resize((size_t)n_padded * sizeof(double)));
   ME_MBAR_HIP(partials.resize((size_t)n_blocks * kObsTargets * sizeof(TargetState)));
-  ME_MBAR_HIP(w.inv_temps.resize(inv.size() * sizeof(double)));
-  ME_MBAR_HIP(w.out.resize((3 * cells + (size_t)n_temps) * sizeof(double)));
-  ME_MBAR_HIP(hipMemcpyAsync(w.inv_temps.get(), inv.data(), inv.size() * sizeof(double), hipMemcpyHostToDevice, stream));
+  ME_MBAR_HIP(upload_targets(p, temps, n_temps, 3 * cells + (size_t)n_temps, inv));
   double *o_mean = w.out.get<double>(), *o_var = o_mean + cells, *o_cov = o_var + cells, *o_neff = o_cov + cells;
   hipLaunchKernelGGL(k_mbar_log_denominator, dim3(n_blocks), dim3(kThreads), 0, stream, sm.energies, sm.n_samples, n_padded, n_rungs,
                      w.table.get<const double>(), d.get<double>());
@@ -363,17 +351,13 @@ hipError_t reweight_observables(const MbarSamples &sm, const ObsColumns &oc, con
   return hipSuccess;
 }
 
-int reweight_observables_common(me_engine *e, const MbarSamples &sm, const ObsColumns &oc, const double *ladder_temps, int n_rungs,
-                                const double *f, const double *temps, int n, double *mean, double *var, double *cov, double *neff,
-                                hipStream_t stream) {
-  if (!f || !temps || n < 1) return fail(e, ME_ERR_INVALID, "f and at least one target temperature are needed");
-  int rc = mbar_check_temps(e, temps, n, "target temperatures");
+// the two forms of me_mbar_reweight_observables behind their Source
+int reweight_observables_common(const Source &src, const double *f, const double *temps, int n, double *mean, double *var, double *cov,
+                                double *neff) {
+  const int rc = check_f_and_targets(src.e, f, src.n_rungs, temps, n, 1);
   if (rc) return rc;
-  for (int k = 0; k < n_rungs; ++k)
-    if (!std::isfinite(f[k])) return fail(e, ME_ERR_INVALID, "f must be finite");
-  int empty = -1;
-  const hipError_t err = reweight_observables(sm, oc, ladder_temps, n_rungs, f, temps, n, mean, var, cov, neff, &empty, stream);
-  return mbar_check_common(e, n_rungs, empty, err);
+  Problem p;
+  return mbar_check_common(src.e, p, reweight_observables(p, src, f, temps, n, mean, var, cov, neff));
 }
 
 int catalogue_size(const me_engine *e) { return e->d + e->nobs + e->n_terms; }
@@ -479,35 +463,21 @@ int me_observable_samples_set(me_engine *e, int64_t n_records, const double *src
 
 int me_mbar_reweight_observables(me_engine *e, const double *f, const double *temps, int32_t n, double *mean, double *var,
                                  double *cov_energy, double *neff_fraction) {
-  if (!e) return ME_ERR_INVALID;
-  MbarSamples sm;
-  int rc = engine_samples(e, sm);
+  Source src;
+  const int rc = src.from_engine(e);
   if (rc) return rc;
-  if (e->samples.n_obs == 0)
+  if (src.columns.n_columns == 0)
     return fail(e, ME_ERR_STATE, "no recorded observables: me_observable_samples_enable, then me_energy_samples_record");
-  ME_HIP(e, hipSetDevice(e->device));
-  const ObsColumns oc{e->samples.obs.get<const double>(), e->samples.n_obs, e->n, (long long)e->samples.n_obs * e->n, e->n};
-  return reweight_observables_common(e, sm, oc, e->ladder.temps.data(), e->ladder.n_rungs, f, temps, n, mean, var, cov_energy,
-                                     neff_fraction, e->stream);
+  return reweight_observables_common(src, f, temps, n, mean, var, cov_energy, neff_fraction);
 }
 
 int me_mbar_reweight_observables_samples(int32_t device_id, const double *energies, const int32_t *rungs, int64_t n_samples,
                                          const double *observables, int32_t n_observables, const double *ladder_temps, int32_t n_rungs,
                                          const double *f, const double *temps, int32_t n, double *mean, double *var,
                                          double *cov_energy, double *neff_fraction) {
-  if (!observables) return fail(nullptr, ME_ERR_INVALID, "null pointer");
-  if (n_observables < 1 || n_observables > ME_MAX_RECORDED_OBSERVABLES)
-    return fail(nullptr, ME_ERR_INVALID, "n_observables must lie in [1, " + std::to_string(ME_MAX_RECORDED_OBSERVABLES) + "]");
-  DeviceBuffer energies_dev, rungs_dev, obs_dev;
-  MbarSamples sm;
-  int rc = upload_samples(device_id, energies, rungs, n_samples, ladder_temps, n_rungs, energies_dev, rungs_dev, sm);
-  if (rc) return rc;
-  ME_HIP(nullptr, obs_dev.resize(sizeof(double) * (size_t)n_samples * (size_t)n_observables));
-  ME_HIP(nullptr, hipMemcpy(obs_dev.get(), observables, obs_dev.bytes(), hipMemcpyHostToDevice));
-  const ObsColumns oc{obs_dev.get<const double>(), n_observables, n_samples, 0, n_samples};
-  rc = reweight_observables_common(nullptr, sm, oc, ladder_temps, n_rungs, f, temps, n, mean, var, cov_energy, neff_fraction, nullptr);
-  (void)hipDeviceSynchronize();
-  return rc;
+  Source src;
+  const int rc = src.from_host(device_id, energies, rungs, n_samples, ladder_temps, n_rungs, observables, n_observables);
+  return rc ? rc : src.finish(reweight_observables_common(src, f, temps, n, mean, var, cov_energy, neff_fraction));
 }
 
 }  // extern "C"

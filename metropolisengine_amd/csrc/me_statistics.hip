@@ -11,15 +11,10 @@
 #include <string>
 
 #include "me_engine.h"
+#include "me_wave.h"
 
 namespace me {
 namespace {
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int w = 32; w > 0; w >>= 1) v += __shfl_xor(v, w, 64);
-  return v;
-}
 
 __global__ void __launch_bounds__(kBlockThreads) k_inefficiency(const double *series, long long n_series, long long length,
                                                                 int fast, int nskip, int mintime, double *g_out,

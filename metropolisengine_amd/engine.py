@@ -39,8 +39,7 @@ _DTYPES = {"f32": _capi.ME_F32, "float32": _capi.ME_F32, "f64": _capi.ME_F64, "f
 _COV_MODES = {"reference": _capi.COV_REFERENCE, "fixed": _capi.COV_FIXED, "pooled": _capi.COV_POOLED}
 
 
-def _as_double_ptr(arr):
-    return arr.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+_as_double_ptr = _capi.double_ptr
 
 
 def _initial_state(initial_real_params, initial_complex_params):
@@ -667,16 +666,17 @@ class MetropolisEngine:
         iterations taken, the last largest change of an ``f[k]``, whether it met ``tol``, and the finite samples of every
         rung (non-finite energies are skipped).  Bitwise reproducible.  ``ValueError`` unless ``tol > 0`` and ``max_iter >=
         1``; raises without a ladder, without records, or when a rung has no finite sample."""
-        from .statistics import validate_mbar_solve, _solve_result
-        tol, max_iter = validate_mbar_solve(tol, max_iter)
+        from . import statistics
+        tol, max_iter = statistics.validate_mbar_solve(tol, max_iter)
         k = ctypes.c_int32()
         self._check(self._lib.me_temperature_ladder(self._handle, None, 0, ctypes.byref(k)))
-        f = np.zeros(max(k.value, 1))
-        n_used = np.zeros(max(k.value, 1), dtype=np.int64)
-        its, res = ctypes.c_int32(), ctypes.c_double()
-        self._check(self._lib.me_mbar_solve(self._handle, tol, max_iter, _as_double_ptr(f), ctypes.byref(its), ctypes.byref(res),
-                                            n_used.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
-        return _solve_result(f, its.value, res.value, n_used, tol)
+        return statistics._solve(self._lib.me_mbar_solve, (self._handle,), max(k.value, 1), tol, max_iter)
+
+    def _ladder_f(self, f, finite):
+        """``f`` checked against the ladder, if there is one (``statistics.validate_mbar_f``)."""
+        from . import statistics
+        ladder = self.temperatures
+        return statistics.validate_mbar_f(f, None if ladder is None else ladder.size, finite)
 
     def reweight(self, temps, f=None):
         """The ladder's samples reweighted to each temperature of ``temps`` (``me_mbar_reweight``): ``{"temps", "ln_z",
@@ -684,18 +684,12 @@ class MetropolisEngine:
         the energy at ``T``, ``energy_var / T^2`` and the effective fraction of the samples behind the estimate.  ``f``: the
         free energies of :meth:`ladder_free_energies` (solved with the defaults when ``None``).  ``ValueError`` for empty,
         non-finite or non-positive ``temps``."""
-        from .statistics import validate_mbar_temps, _reweight_result
-        temps = validate_mbar_temps(temps)
+        from . import statistics
+        temps = statistics.validate_mbar_temps(temps)
         if f is None:
             f = self.ladder_free_energies()["f"]
-        f = np.ascontiguousarray(f, dtype=np.float64)
-        ladder = self.temperatures
-        if ladder is not None and f.shape != ladder.shape:
-            raise ValueError("f must hold one free energy per rung")
-        out = [np.zeros(temps.size) for _ in range(4)]
-        self._check(self._lib.me_mbar_reweight(self._handle, _as_double_ptr(f), _as_double_ptr(temps), temps.size,
-                                               *[_as_double_ptr(o) for o in out]))
-        return _reweight_result(temps, *out)
+        f = self._ladder_f(f, finite=False)      # (whether it is finite is the library's to say)
+        return statistics._reweight(self._lib.me_mbar_reweight, (self._handle,), f, temps)
 
     def ladder_free_energy_uncertainties(self, f, targets=None, inefficiency=1.0):
         """Asymptotic standard errors of the ladder's MBAR free energies ``f`` (of :meth:`ladder_free_energies`) and, with
@@ -705,27 +699,18 @@ class MetropolisEngine:
         (:func:`metropolisengine_amd.statistics.statistical_inefficiency`) as ``inefficiency`` (finite, ``>= 1``) and every
         variance is multiplied by it.  ``ValueError`` for invalid ``targets`` or ``inefficiency``; raises like
         :meth:`ladder_free_energies` without a ladder or without records."""
-        from .statistics import validate_mbar_temps, validate_mbar_inefficiency, _uncertainty_result
-        g = validate_mbar_inefficiency(inefficiency)
+        from . import statistics
+        g = statistics.validate_mbar_inefficiency(inefficiency)
         if targets is not None:
-            targets = validate_mbar_temps(targets, "targets")
-        f = np.ascontiguousarray(f, dtype=np.float64)
-        ladder = self.temperatures
-        if ladder is not None and (f.shape != ladder.shape or not np.all(np.isfinite(f))):
-            raise ValueError("f must hold one finite free energy per rung")
-        k = f.size if ladder is not None else 1
-        n_targets = 0 if targets is None else targets.size
-        c = k + 2 * n_targets
-        gram, counts = np.zeros((c, c)), np.zeros(c)
-        ln_z, mean_e = np.zeros(n_targets), np.zeros(n_targets)
-        n_used = ctypes.c_int64()
-        self._check(self._lib.me_mbar_gram(self._handle, _as_double_ptr(f), _as_double_ptr(targets) if n_targets else None, n_targets,
-                                           _as_double_ptr(gram), _as_double_ptr(counts), _as_double_ptr(ln_z), _as_double_ptr(mean_e),
-                                           ctypes.byref(n_used)))
-        shift = ctypes.c_double(0.0)
-        if n_targets:       # the shift of the energy columns, from the device: the samples stay there
+            targets = statistics.validate_mbar_temps(targets, "targets")
+        f = self._ladder_f(f, finite=True)
+        k = max(f.size, 1)      # (the ladder's rungs; without a ladder the library refuses before it writes)
+
+        def energy_shift():     # of the energy columns, from the device: the samples stay there
+            shift = ctypes.c_double(0.0)
             self._check(self._lib.me_mbar_energy_shift(self._handle, ctypes.byref(shift)))
-        return _uncertainty_result(gram, counts, k, targets, ln_z, mean_e, n_used.value, g, shift.value)
+            return shift.value
+        return statistics._uncertainties(self._lib.me_mbar_gram, (self._handle,), k, f, targets, g, energy_shift)
 
     # ------------------------------------------------------------------ recorded observables and their reweighting
     def observable_names(self):
@@ -798,21 +783,15 @@ class MetropolisEngine:
         energies of :meth:`ladder_free_energies` (solved with the defaults when ``None``).  Bitwise reproducible, and column
         ``q`` at temperature ``t`` does not depend on what else is asked for.  ``ValueError`` for empty, non-finite or
         non-positive ``temps``; raises without a ladder, without records or without an observable store."""
-        from .statistics import validate_mbar_temps, _observable_result
-        temps = validate_mbar_temps(temps)
+        from . import statistics
+        temps = statistics.validate_mbar_temps(temps)
         names = self.recorded_observables
         if not names:
             raise ValueError("no observable store: call record_observables first")
         if f is None:
             f = self.ladder_free_energies()["f"]
-        f = np.ascontiguousarray(f, dtype=np.float64)
-        ladder = self.temperatures
-        if ladder is not None and f.shape != ladder.shape:
-            raise ValueError("f must hold one free energy per rung")
-        out = [np.zeros((temps.size, len(names))) for _ in range(3)] + [np.zeros(temps.size)]
-        self._check(self._lib.me_mbar_reweight_observables(self._handle, _as_double_ptr(f), _as_double_ptr(temps), temps.size,
-                                                           *[_as_double_ptr(o) for o in out]))
-        return _observable_result(temps, names, *out)
+        f = self._ladder_f(f, finite=False)
+        return statistics._reweight_observables(self._lib.me_mbar_reweight_observables, (self._handle,), f, temps, names)
 
     # ------------------------------------------------------------------ scalar temperature and population annealing
     def set_temp(self, temp):

@@ -11,7 +11,11 @@ simulations", JCTC 12:1799, 2016; statistical inefficiency after Chodera et al.,
 pymbar 3.x ``timeseries.statisticalInefficiency`` / ``detectEquilibration``) and are tested against analytic
 AR(1) autocorrelation times only.
 """
+import ctypes
+
 import numpy as np
+
+from . import _capi
 
 
 def statistical_inefficiency(series, mintime=3, fast=False):
@@ -60,8 +64,6 @@ def detect_equilibration_batch(series, fast=True, nskip=1, device=0):
     """``detect_equilibration`` for every row of ``series[n_series, T]`` in one call on the GPU
     (``me_detect_equilibration``: one wavefront per (series, start)); returns ``(t0, g, Neff_max)`` arrays.  An
     ensemble run records thousands of chains x columns, each an O(T^2) scan on the host."""
-    import ctypes
-    from . import _capi
     a = np.ascontiguousarray(series, dtype=np.float64)
     if a.ndim != 2:
         raise ValueError("series must be [n_series, length]")
@@ -69,10 +71,9 @@ def detect_equilibration_batch(series, fast=True, nskip=1, device=0):
     t0 = np.zeros(n, dtype=np.int64)
     g = np.ones(n)
     neff = np.ones(n)
-    dp = ctypes.POINTER(ctypes.c_double)
     _capi.check(_capi.load().me_detect_equilibration(
-        int(device), a.ctypes.data_as(dp), n, length, int(bool(fast)), int(nskip),
-        t0.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), g.ctypes.data_as(dp), neff.ctypes.data_as(dp)))
+        int(device), _capi.double_ptr(a), n, length, int(bool(fast)), int(nskip), _capi.int64_ptr(t0), _capi.double_ptr(g),
+        _capi.double_ptr(neff)))
     return t0, g, neff
 
 
@@ -119,14 +120,47 @@ def validate_mbar_samples(energies, rungs, temps):
     return e, np.ascontiguousarray(r, dtype=np.int32), t
 
 
+def validate_mbar_f(f, n_rungs, finite=True):
+    """``f`` as a contiguous float64 array; ``ValueError`` unless it holds one free energy per rung, all of them finite when
+    ``finite``.  ``n_rungs`` ``None`` (an engine without a ladder, which the library refuses): nothing to compare with."""
+    f = np.ascontiguousarray(f, dtype=np.float64)
+    if n_rungs is not None and (f.shape != (n_rungs,) or (finite and not np.all(np.isfinite(f)))):
+        raise ValueError("f must hold one %sfree energy per rung" % ("finite " if finite else ""))
+    return f
+
+
+# One implementation per operation, below its result dictionary.  ``fn`` is the C function of either form and ``lead`` its
+# leading arguments: ``(handle,)`` of an engine (``MetropolisEngine``), or the samples on the host (``_host_samples``).
+def _call(fn, lead, *args):
+    _capi.check(fn(*lead, *args), lead[0] if len(lead) == 1 else None)
+
+
+def _host_samples(device, e, r, t, observables=None):
+    columns = () if observables is None else (_capi.double_ptr(observables), observables.shape[0])
+    return (int(device), _capi.double_ptr(e), _capi.int32_ptr(r), e.size) + columns + (_capi.double_ptr(t), t.size)
+
+
 def _solve_result(f, iterations, residual, n_used, tol):
     return {"f": f, "ln_z": -f, "iterations": int(iterations), "residual": float(residual),
             "converged": bool(residual <= tol), "n_samples": n_used}
 
 
+def _solve(fn, lead, n_rungs, tol, max_iter):
+    f, n_used = np.zeros(n_rungs), np.zeros(n_rungs, dtype=np.int64)
+    its, res = ctypes.c_int32(), ctypes.c_double()
+    _call(fn, lead, tol, max_iter, _capi.double_ptr(f), ctypes.byref(its), ctypes.byref(res), _capi.int64_ptr(n_used))
+    return _solve_result(f, its.value, res.value, n_used, tol)
+
+
 def _reweight_result(temps, ln_z, mean, var, neff):
     return {"temps": temps, "ln_z": ln_z, "energy_mean": mean, "energy_var": var, "heat_capacity": var / (temps * temps),
             "neff_fraction": neff}
+
+
+def _reweight(fn, lead, f, targets):
+    out = [np.zeros(targets.size) for _ in range(4)]
+    _call(fn, lead, _capi.double_ptr(f), _capi.double_ptr(targets), targets.size, *map(_capi.double_ptr, out))
+    return _reweight_result(targets, *out)
 
 
 def mbar_free_energies(energies, rungs, temps, tol=1e-10, max_iter=10000, device=0):
@@ -135,37 +169,19 @@ def mbar_free_energies(energies, rungs, temps, tol=1e-10, max_iter=10000, device
     ``{"f", "ln_z", "iterations", "residual", "converged", "n_samples"}``: ``f[k] = -ln Z(T_k) / Z(T_0)``, ``ln_z = -f``,
     ``n_samples[k]`` the finite energies of rung ``k`` (the others are skipped).  For samples gathered from several GPU
     shards and for subsets of a run; a rung without a finite sample raises."""
-    import ctypes
-    from . import _capi
     tol, max_iter = validate_mbar_solve(tol, max_iter)
     e, r, t = validate_mbar_samples(energies, rungs, temps)
-    f = np.zeros(t.size)
-    n_used = np.zeros(t.size, dtype=np.int64)
-    its, res = ctypes.c_int32(), ctypes.c_double()
-    dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)
-    _capi.check(_capi.load().me_mbar_solve_samples(
-        int(device), e.ctypes.data_as(dp), r.ctypes.data_as(ip), e.size, t.ctypes.data_as(dp), t.size, tol, max_iter,
-        f.ctypes.data_as(dp), ctypes.byref(its), ctypes.byref(res), n_used.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
-    return _solve_result(f, its.value, res.value, n_used, tol)
+    return _solve(_capi.load().me_mbar_solve_samples, _host_samples(device, e, r, t), t.size, tol, max_iter)
 
 
 def mbar_reweight(energies, rungs, temps, f, targets, device=0):
     """Reweight the samples of a ladder (``temps``, free energies ``f`` of :func:`mbar_free_energies`) to the temperatures
     ``targets`` (``me_mbar_reweight_samples``).  Returns ``{"temps", "ln_z", "energy_mean", "energy_var", "heat_capacity",
     "neff_fraction"}``: ``ln_z = ln Z(T) / Z(T_0)``, ``heat_capacity = energy_var / T^2``."""
-    import ctypes
-    from . import _capi
     e, r, t = validate_mbar_samples(energies, rungs, temps)
     targets = validate_mbar_temps(targets, "targets")
-    f = np.ascontiguousarray(f, dtype=np.float64)
-    if f.shape != t.shape or not np.all(np.isfinite(f)):
-        raise ValueError("f must hold one finite free energy per rung")
-    out = [np.zeros(targets.size) for _ in range(4)]
-    dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)
-    _capi.check(_capi.load().me_mbar_reweight_samples(
-        int(device), e.ctypes.data_as(dp), r.ctypes.data_as(ip), e.size, t.ctypes.data_as(dp), t.size, f.ctypes.data_as(dp),
-        targets.ctypes.data_as(dp), targets.size, *[o.ctypes.data_as(dp) for o in out]))
-    return _reweight_result(targets, *out)
+    f = validate_mbar_f(f, t.size)
+    return _reweight(_capi.load().me_mbar_reweight_samples, _host_samples(device, e, r, t), f, targets)
 
 
 MBAR_MAX_OBSERVABLES = 16       # recorded / reweighted observable columns (ME_MAX_RECORDED_OBSERVABLES)
@@ -224,6 +240,12 @@ def _observable_result(temps, names, mean, var, cov, neff):
             "dmean_dT": cov / (temps * temps)[:, None], "neff_fraction": neff}
 
 
+def _reweight_observables(fn, lead, f, targets, names):
+    out = [np.zeros((targets.size, len(names))) for _ in range(3)] + [np.zeros(targets.size)]
+    _call(fn, lead, _capi.double_ptr(f), _capi.double_ptr(targets), targets.size, *map(_capi.double_ptr, out))
+    return _observable_result(targets, names, *out)
+
+
 def mbar_reweight_observables(energies, rungs, temps, f, targets, observables, device=0):
     """Reweight observables sampled along with the energies of a ladder (``temps``, free energies ``f`` of
     :func:`mbar_free_energies`) to the temperatures ``targets`` (``me_mbar_reweight_observables_samples``; the engine form is
@@ -232,21 +254,12 @@ def mbar_reweight_observables(energies, rungs, temps, f, targets, observables, d
     "dmean_dT", "neff_fraction"}``: the first four ``(T, Q)``, ``dmean_dT = cov_energy / T^2``; ``names`` are the column
     numbers.  A sample counts when its ENERGY is finite; a non-finite value in column ``q`` of such a sample makes column
     ``q``'s results non-finite and changes no other column."""
-    import ctypes
-    from . import _capi
     e, r, t = validate_mbar_samples(energies, rungs, temps)
     targets = validate_mbar_temps(targets, "targets")
-    f = np.ascontiguousarray(f, dtype=np.float64)
-    if f.shape != t.shape or not np.all(np.isfinite(f)):
-        raise ValueError("f must hold one finite free energy per rung")
+    f = validate_mbar_f(f, t.size)
     a = validate_mbar_observables(observables, e.size)
-    q = a.shape[0]
-    out = [np.zeros((targets.size, q)) for _ in range(3)] + [np.zeros(targets.size)]
-    dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)
-    _capi.check(_capi.load().me_mbar_reweight_observables_samples(
-        int(device), e.ctypes.data_as(dp), r.ctypes.data_as(ip), e.size, a.ctypes.data_as(dp), q, t.ctypes.data_as(dp), t.size,
-        f.ctypes.data_as(dp), targets.ctypes.data_as(dp), targets.size, *[o.ctypes.data_as(dp) for o in out]))
-    return _observable_result(targets, tuple(range(q)), *out)
+    return _reweight_observables(_capi.load().me_mbar_reweight_observables_samples, _host_samples(device, e, r, t, a), f, targets,
+                                 tuple(range(a.shape[0])))
 
 
 MBAR_GRAM_MAX_COLUMNS = 128     # columns of the weight matrix per device pass (csrc/me_mbar_cov.hip)
@@ -306,6 +319,19 @@ def _uncertainty_result(gram, column_counts, n_rungs, targets, ln_z, mean_e, n_u
     return out
 
 
+def _uncertainties(fn, lead, n_rungs, f, targets, inefficiency, energy_shift):
+    """``energy_shift()``: the least finite energy - 1; asked for after the Gram matrix, and only with ``targets``."""
+    n_targets = 0 if targets is None else targets.size
+    c = n_rungs + 2 * n_targets
+    gram, counts = np.zeros((c, c)), np.zeros(c)
+    ln_z, mean_e = np.zeros(n_targets), np.zeros(n_targets)
+    n_used = ctypes.c_int64()
+    _call(fn, lead, _capi.double_ptr(f), _capi.double_ptr(targets) if n_targets else None, n_targets, _capi.double_ptr(gram),
+          _capi.double_ptr(counts), _capi.double_ptr(ln_z), _capi.double_ptr(mean_e), ctypes.byref(n_used))
+    shift = energy_shift() if n_targets else 0.0
+    return _uncertainty_result(gram, counts, n_rungs, targets, ln_z, mean_e, n_used.value, inefficiency, shift)
+
+
 def mbar_uncertainties(energies, rungs, temps, f, targets=None, inefficiency=1.0, device=0):
     """Asymptotic standard errors of MBAR free energies and of reweighted energies from samples on the host
     (``me_mbar_gram_samples``: one further pass over the samples builds the Gram matrix of the weight matrix on the matrix
@@ -319,26 +345,13 @@ def mbar_uncertainties(energies, rungs, temps, f, targets=None, inefficiency=1.0
     The asymptotic formula assumes INDEPENDENT samples.  For correlated samples pass their statistical inefficiency
     (:func:`statistical_inefficiency` of the energy series, ``>= 1``) as ``inefficiency``: every variance is multiplied by
     it, the customary correction.  ``ValueError`` for an ``inefficiency`` that is not a finite scalar ``>= 1``."""
-    import ctypes
-    from . import _capi
     g = validate_mbar_inefficiency(inefficiency)
     e, r, t = validate_mbar_samples(energies, rungs, temps)
     if targets is not None:
         targets = validate_mbar_temps(targets, "targets")
-    f = np.ascontiguousarray(f, dtype=np.float64)
-    if f.shape != t.shape or not np.all(np.isfinite(f)):
-        raise ValueError("f must hold one finite free energy per rung")
-    n_targets = 0 if targets is None else targets.size
-    c = t.size + 2 * n_targets
-    gram, counts = np.zeros((c, c)), np.zeros(c)
-    ln_z, mean_e = np.zeros(n_targets), np.zeros(n_targets)
-    n_used = ctypes.c_int64()
-    dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32)
-    _capi.check(_capi.load().me_mbar_gram_samples(
-        int(device), e.ctypes.data_as(dp), r.ctypes.data_as(ip), e.size, t.ctypes.data_as(dp), t.size, f.ctypes.data_as(dp),
-        targets.ctypes.data_as(dp) if n_targets else None, n_targets, gram.ctypes.data_as(dp), counts.ctypes.data_as(dp),
-        ln_z.ctypes.data_as(dp), mean_e.ctypes.data_as(dp), ctypes.byref(n_used)))
-    return _uncertainty_result(gram, counts, t.size, targets, ln_z, mean_e, n_used.value, g, e[np.isfinite(e)].min() - 1.0)
+    f = validate_mbar_f(f, t.size)
+    return _uncertainties(_capi.load().me_mbar_gram_samples, _host_samples(device, e, r, t), t.size, f, targets, g,
+                          lambda: e[np.isfinite(e)].min() - 1.0)
 
 
 def get_equilibration_points(df, device=None):

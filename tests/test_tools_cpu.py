@@ -51,3 +51,18 @@ def test_bench_side_measurements_need_full():
     assert (chosen.cpu_seconds, chosen.fused_sweeps, chosen.hbm_chains_log2, chosen.extras) == (0.0, 4, 22, 1)
     for args in (plain, full):
         assert (args.gpus, args.steps, args.warmup, args.dtype, args.sweeps, args.chains_log2) == (1, 7, 3, "f64", 1, 20)
+
+
+def test_host_units_are_named_once():
+    """build.HOST_UNITS names every csrc/*.hip but me_kernels.hip, and tools/build_variant.sh takes its units from that list: it
+    spells out none of them itself (a hand-kept second list once missed two new units and its variants stopped linking)."""
+    import re
+    from metropolisengine_amd import build
+    units = [name for name, _ in build.HOST_UNITS]
+    on_disk = sorted(f[:-len(".hip")] for f in os.listdir(build.CSRC) if f.endswith(".hip"))
+    assert sorted(units + ["me_kernels"]) == on_disk and len(set(units)) == len(units)
+    assert dict(build.HOST_UNITS)["me_population"] == ["-ffp-contract=off"]
+    with open(os.path.join(ROOT, "tools", "build_variant.sh")) as fh:
+        script = fh.read()
+    assert "build.HOST_UNITS" in script
+    assert set(re.findall(r"\bme_\w+", script)) == {"me_kernels"}
