@@ -47,6 +47,15 @@ __device__ __forceinline__ U4 philox4x32_10(U4 c, uint32_t k0, uint32_t k1) {
   }
   return c;
 }
+// Block b of chain gid's stream at one step (the counter layout of oracle/philox.py): outputs 4 b .. 4 b + 3 of the step's words
+__device__ __forceinline__ U4 philox_block(unsigned long long gid, unsigned long long step, int b, uint32_t seed_lo, uint32_t seed_hi) {
+  U4 ctr;
+  ctr.x = (uint32_t)gid;
+  ctr.y = (uint32_t)(gid >> 32);
+  ctr.z = (uint32_t)step;
+  ctr.w = ((uint32_t)(step >> 32) << 16) | (uint32_t)b;
+  return philox4x32_10(ctr, seed_lo, seed_hi);
+}
 
 // ------------------------------------------------------------------------------------------------ numerics
 // One explicit fused multiply-add.  hipcc contracts a * b + c by itself (-ffp-contract=fast), but for a * b + c * d it may
@@ -244,7 +253,7 @@ struct TiledField {
   __device__ __forceinline__ void store_nt(int k, unsigned int tile_off, R value) const { store_aux<ME_NT_AUX>(k, tile_off, value); }
 };
 
-// accesses of k_measure / k_factor to the packed covariance and factor fields; NT: streamed once per launch from / to
+// accesses of k_measure / the factor kernels to the packed covariance and factor fields; NT: streamed once per launch from / to
 // HBM (the launcher decides by working-set size, me_kernels.hip)
 template <bool NT, class F>
 __device__ __forceinline__ auto packed_load(const F &f, int row, unsigned int chain_off) {
@@ -587,6 +596,56 @@ struct StepArgs {
   int tiles_per_rung;
 };
 
+// the type-erased launch descriptor narrowed to the device dtype (the runtime-dimension kernels ignore ladder, stale_total, inj_*)
+template <typename R>
+StepArgs<R> typed(const StepLaunch &l) {
+  StepArgs<R> a;
+  a.x = (R *)l.x;
+  a.energy = (R *)l.energy;
+  a.width = (R *)l.width;
+  a.factor = (const R *)l.factor;
+  a.inj_normals = (const R *)l.inj_normals;
+  a.inj_uniforms = (const R *)l.inj_uniforms;
+  a.accept_slots = l.accept_slots;
+  a.status = l.status;
+  a.n = l.n;
+  a.chain_offset = l.chain_offset;
+  a.step_index = l.step_index;
+  a.seed_lo = (uint32_t)l.seed;
+  a.seed_hi = (uint32_t)(l.seed >> 32);
+  a.n_sweeps = l.n_sweeps;
+  a.reject_kind = l.reject_kind;
+  a.split_widths = l.split_widths;
+  a.stale_total = l.stale_total;
+  a.reject_bound = (R)l.reject_bound;
+  a.temp = (R)l.temp;
+  a.inv_temp = l.temp > 0 ? (R)(1.0 / l.temp) : (R)0;
+  a.inv_temp_log2e = l.temp > 0 ? (R)(1.4426950408889634 / l.temp) : (R)0;
+  a.ratio = (R)l.ratio;
+  a.p = (R)l.target_acceptance;
+  a.damping = (R)l.damping;
+  a.up = (R)(l.ratio * (1.0 - l.target_acceptance) / l.damping);
+  a.down = (R)(-l.ratio * l.target_acceptance / l.damping);
+  a.ladder = (const R *)l.ladder;
+  a.tiles_per_rung = l.tiles_per_rung;
+  return a;
+}
+
+// The end of every step kernel.  Acceptance tracking: ballot + popcount per sweep, then ONE plain read-modify-write of the
+// wavefront's own slot per launch (waves = wavefronts per block).  (Same-address atomics serialise at ~12 ns each at the
+// memory side: 2^14 wavefronts adding to one counter cost 0.4 ms per launch, 15x the whole state sweep.)  Slots are summed
+// on demand by k_sum_slots.  Then the launch's status bits, if any.
+template <typename R>
+__device__ __forceinline__ void publish_step(const StepArgs<R> &a, unsigned int waves, unsigned int wave_accepted, bool bad_energy,
+                                             bool bad_width, bool bad_pivot = false) {
+  if ((threadIdx.x & 63) == 0 && wave_accepted) {
+    unsigned long long *slot = a.accept_slots + (size_t)blockIdx.x * waves + (threadIdx.x >> 6);
+    *slot += (unsigned long long)wave_accepted;
+  }
+  const unsigned int bits = (bad_energy ? ST_NONFINITE_ENERGY : 0u) | (bad_width ? ST_BAD_WIDTH : 0u) | (bad_pivot ? ST_BAD_PIVOT : 0u);
+  if (bits) atomicOr(a.status, bits);
+}
+
 // The uphill test of chain c's accept rule (:329-335) at the chain's temperature.  LADDER = false: the scalar temp of the
 // kernel arguments, exactly as before ladders existed.  LADDER = true: the rung's constants from a.ladder.  A rung is a run
 // of whole 64-chain tiles, so the rung is wave-uniform: the tile index goes through readfirstlane and the two table words
@@ -656,12 +715,7 @@ __device__ __forceinline__ void draw_step(const StepArgs<R> &a, long long c, uns
     uint32_t words[4 * NBLK];
 #pragma unroll
     for (int b = 0; b < NBLK; ++b) {
-      U4 ctr;
-      ctr.x = (uint32_t)gid;
-      ctr.y = (uint32_t)(gid >> 32);
-      ctr.z = (uint32_t)step;
-      ctr.w = ((uint32_t)(step >> 32) << 16) | (uint32_t)b;
-      const U4 o = philox4x32_10(ctr, a.seed_lo, a.seed_hi);
+      const U4 o = philox_block(gid, step, b, a.seed_lo, a.seed_hi);
       words[4 * b + 0] = o.x;
       words[4 * b + 1] = o.y;
       words[4 * b + 2] = o.z;
@@ -912,12 +966,7 @@ __global__ void ME_STEP_BOUNDS k_step(StepArgs<R> a, Energy en) {
           uint32_t words[4 * NBLK];
 #pragma unroll
           for (int b = 0; b < NBLK; ++b) {
-            U4 ctr;
-            ctr.x = (uint32_t)gid;
-            ctr.y = (uint32_t)(gid >> 32);
-            ctr.z = (uint32_t)step;
-            ctr.w = ((uint32_t)(step >> 32) << 16) | (uint32_t)b;
-            const U4 o = philox4x32_10(ctr, a.seed_lo, a.seed_hi);
+            const U4 o = philox_block(gid, step, b, a.seed_lo, a.seed_hi);
             words[4 * b + 0] = o.x;
             words[4 * b + 1] = o.y;
             words[4 * b + 2] = o.z;
@@ -1036,15 +1085,7 @@ __global__ void ME_STEP_BOUNDS k_step(StepArgs<R> a, Energy en) {
     else ledger.store(fe, coff);
     fw.store(MIXED ? GROUP : 0, coff, w);   // after a mixed step_all rows 1, 2 are implied equal to row 0 (host flag)
   }
-  // acceptance tracking: ballot + popcount per sweep, then ONE plain read-modify-write of the wavefront's own
-  // slot per launch.  (Same-address atomics serialise at ~12 ns each at the memory side: 2^14 wavefronts adding
-  // to one counter cost 0.4 ms per launch, 15x the whole state sweep.)  Slots are summed on demand by k_sum_slots.
-  if ((threadIdx.x & 63) == 0 && wave_accepted) {
-    unsigned long long *slot = a.accept_slots + (size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    *slot += (unsigned long long)wave_accepted;
-  }
-  const unsigned int bits = (bad_energy ? ST_NONFINITE_ENERGY : 0u) | (bad_width ? ST_BAD_WIDTH : 0u);
-  if (bits) atomicOr(a.status, bits);
+  publish_step(a, blockDim.x >> 6, wave_accepted, bad_energy, bad_width);
 }
 
 template <typename R, int NR, int NC, class Energy>
@@ -1074,6 +1115,10 @@ __global__ void __launch_bounds__(kStepThreads) k_init_energy(const R *xs, R *en
   }
 }
 
+}  // namespace me
+#include "me_packed_walk.h"   // the streamed covariance / Cholesky walks, shared with me_runtime_dims.hip
+namespace me {
+
 // ------------------------------------------------------------------------------------------------ k_measure
 template <typename R>
 struct MeasureArgs {
@@ -1086,6 +1131,27 @@ struct MeasureArgs {
   R cov_keep;  // (i-2)/(i-1)
   int update_cov, write_factor, split_widths;
 };
+
+template <typename R>
+MeasureArgs<R> typed_measure(const MeasureLaunch &l) {
+  MeasureArgs<R> a;
+  a.x = (const R *)l.x;
+  a.width = (const R *)l.width;
+  a.mean = (R *)l.mean;
+  a.cov = (R *)l.cov;
+  a.obs_mean = (R *)l.obs_mean;
+  a.factor = (R *)l.factor;
+  a.status = l.status;
+  a.n = l.n;
+  const double i = (double)l.measure_count;
+  a.keep = (R)((i - 1.0) / i);
+  a.inv_i = (R)(1.0 / i);
+  a.cov_keep = (R)((i - 2.0) / (i - 1.0));
+  a.update_cov = l.update_cov;
+  a.split_widths = l.split_widths;
+  a.write_factor = l.write_factor;
+  return a;
+}
 
 // Running mean, Haario-type covariance recursion with the reference's undivided epsilon term (quirk Q1),
 // observables, and the refresh of the packed Cholesky factors the next proposals use.
@@ -1144,10 +1210,10 @@ __device__ __forceinline__ void cholesky_packed(R (&m)[NR * (NR + 1) / 2 + NC * 
     }
 }
 
-// FUSED = true refreshes the proposal factors in the same kernel (the updated covariance stays in registers).  With the
-// loads of every phase batched ahead of its stores this is the faster form for every per-chain kernel set, 16 real
-// parameters (136 entries, 253 VGPRs, two wavefronts per SIMD) included: 460 us against 570 us for the split form
-// (FUSED = false followed by k_factor), which is kept for experiments (-DME_MEASURE_FUSED_MAX_P).
+// FUSED = true refreshes the proposal factors in the same kernel (the updated covariance stays in registers): every
+// per-chain kernel set whose packed matrix fits in registers, 16 real parameters (136 entries, 253 VGPRs, two wavefronts per
+// SIMD) included -- with the loads of every phase batched ahead of its stores 460 us against 570 us for a factor kernel of
+// its own.  FUSED = false: sets that only track the covariance, and the streamed sizes (k_factor_tile / _stream / _mixed).
 #ifndef ME_MEASURE_WAVES
 #define ME_MEASURE_WAVES 1
 #endif
@@ -1156,37 +1222,13 @@ __device__ __forceinline__ void cholesky_packed(R (&m)[NR * (NR + 1) / 2 + NC * 
 // resident in the Infinity Cache between launches no longer fit together with it.  Measured at 2^20 x (16,0): packed
 // fields nt 468 -> 375 us, means nt on top of that 375 -> 410 us (x + means + observables = 256 MB still profit from the
 // cache); at 2^19 x (64,0), means only: 225 -> 190 us with nt (537 MB: keeping x resident for the next k_step wins).
-// Where measure_chain takes the running mean, the observable means and the packed covariance from: memory, when it asks
-// (k_measure), or registers that were loaded BEFORE the sweeps of a cycle (k_cycle: the loads travel while the sweeps run).
-template <typename R, bool NT, bool NTM>
-struct MeasureFromMemory {
-  const Field<R> &fmean, &fobs;
-  const TiledField<R> &fcov;
-  unsigned int coff, toff;
-  __device__ __forceinline__ R mean(int d) const { return packed_load<NTM>(fmean, d, coff); }
-  __device__ __forceinline__ R obs(int k) const { return packed_load<NTM>(fobs, k, coff); }
-  __device__ __forceinline__ R cov(int k) const { return packed_load<NT>(fcov, k, toff); }
-};
-// LEVEL 1: mean and observables preloaded, covariance from memory; LEVEL 2: everything preloaded
-template <typename R, int D, int NOBS, int P, int LEVEL, bool NT>
-struct MeasurePreloaded {
-  R mu[D], ob[NOBS], cv[LEVEL >= 2 ? P : 1];
-  const TiledField<R> &fcov;
-  unsigned int toff;
-  __device__ __forceinline__ R mean(int d) const { return mu[d]; }
-  __device__ __forceinline__ R obs(int k) const { return ob[k]; }
-  __device__ __forceinline__ R cov(int k) const {
-    if constexpr (LEVEL >= 2) return cv[k];
-    else return packed_load<NT>(fcov, k, toff);
-  }
-};
 
 // measure() of ONE chain whose state x is in registers: running mean (:404-410), observables (:458-463, :412-414),
 // covariance recursion (:416-427, one-pass form above) and the refresh of the chain's proposal factors.  Shared by
 // k_measure (loads x) and k_cycle (x comes straight out of the sweeps); forced inline.  widths(w_real, w_cplx) supplies
 // the group widths of the epsilon term (:418, :425) -- a field load in k_measure, registers in k_cycle.
-template <typename R, int NR, int NC, bool PER_CHAIN_COV, bool FUSED, bool NT, bool NTM, class Source, class WidthFn>
-__device__ __forceinline__ void measure_chain(const MeasureArgs<R> &a, long long c, const R (&x)[NR + 2 * NC], const Source &src,
+template <typename R, int NR, int NC, bool PER_CHAIN_COV, bool FUSED, bool NT, bool NTM, class WidthFn>
+__device__ __forceinline__ void measure_chain(const MeasureArgs<R> &a, long long c, const R (&x)[NR + 2 * NC],
                                               const Field<R> &fmean, const Field<R> &fobs, const TiledField<R> &fcov,
                                               const TiledField<R> &ffac, [[maybe_unused]] R (*s_delta)[kStepThreads],
                                               WidthFn &&widths, bool &bad_pivot) {
@@ -1205,7 +1247,7 @@ __device__ __forceinline__ void measure_chain(const MeasureArgs<R> &a, long long
   {
     R mu[D];
 #pragma unroll
-    for (int d = 0; d < D; ++d) mu[d] = src.mean(d);
+    for (int d = 0; d < D; ++d) mu[d] = packed_load<NTM>(fmean, d, coff);
 #pragma unroll
     for (int d = 0; d < D; ++d) {
       if constexpr (STREAM) s_delta[d][threadIdx.x] = x[d] - mu[d];   // parked in LDS, see the streaming path below
@@ -1220,7 +1262,7 @@ __device__ __forceinline__ void measure_chain(const MeasureArgs<R> &a, long long
     R m[kBatch];
 #pragma unroll
     for (int u = 0; u < kBatch; ++u)
-      if (k0 + u < NOBS) m[u] = src.obs(k0 + u);
+      if (k0 + u < NOBS) m[u] = packed_load<NTM>(fobs, k0 + u, coff);
 #pragma unroll
     for (int u = 0; u < kBatch; ++u) {
       const int k = k0 + u;
@@ -1242,70 +1284,15 @@ __device__ __forceinline__ void measure_chain(const MeasureArgs<R> &a, long long
       // the compiler may or may not fuse the product into the add, kernel by kernel
       const R w2_real = w_real * w_real, w2_cplx = w_cplx * w_cplx;
       if constexpr (STREAM) {
-        // delta is parked in LDS (lane-linear, conflict-free) so that the walk over the packed entries can be a
-        // ROLLED loop: unrolled, 2 080 entries are ~100 KB of code and the kernel becomes instruction-fetch bound.
-        // One 64-bit pointer per lane steps by whole rows (the packed order is exactly the loop order).
-        // tile-major: the chain's entries lie 64 values apart from the start of its tile
-        R *p = a.cov + (c >> 6) * (long long)P * 64 + (c & 63);
-        constexpr long long ts = 64;
-        for (int i = 0; i < NR; ++i) {
-          const R di = s_delta[i][threadIdx.x];
-          int j = 0;
-          // batches of 16 (then 4) entries: all loads first (a store to p[.] would otherwise fence the next load, the compiler
-          // cannot prove the rows distinct), then the updates
-          for (; j + 16 <= i; j += 16) {
-            R v[16];
-#pragma unroll
-            for (int u = 0; u < 16; ++u) v[u] = p[u * ts];
-#pragma unroll
-            for (int u = 0; u < 16; ++u) p[u * ts] = fma_(di * s_delta[j + u][threadIdx.x], a.inv_i, v[u] * a.cov_keep);
-            p += 16 * ts;
-          }
-          for (; j + 4 <= i; j += 4) {
-            R v[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) v[u] = p[u * ts];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) p[u * ts] = fma_(di * s_delta[j + u][threadIdx.x], a.inv_i, v[u] * a.cov_keep);
-            p += 4 * ts;
-          }
-          for (; j < i; ++j) {
-            *p = fma_(di * s_delta[j][threadIdx.x], a.inv_i, *p * a.cov_keep);
-            p += ts;
-          }
-          *p = fma_(w2_real, a.inv_i, fma_(di * di, a.inv_i, *p * a.cov_keep));
-          p += ts;
-        }
-        for (int i = 0; i < NC; ++i) {
-          const R ai = s_delta[NR + i][threadIdx.x], bi = s_delta[NR + NC + i][threadIdx.x];
-          int j = 0;
-          for (; j + 8 <= i; j += 8) {          // eight (Re, Im) pairs: sixteen loads, then the updates
-            R v[16];
-#pragma unroll
-            for (int u = 0; u < 16; ++u) v[u] = p[u * ts];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-              const R aj = s_delta[NR + j + u][threadIdx.x], bj = s_delta[NR + NC + j + u][threadIdx.x];
-              p[(2 * u) * ts] = fma_(fma_(ai, aj, bi * bj), a.inv_i, v[2 * u] * a.cov_keep);
-              p[(2 * u + 1) * ts] = fma_(fma_(bi, aj, -(ai * bj)), a.inv_i, v[2 * u + 1] * a.cov_keep);
-            }
-            p += 16 * ts;
-          }
-          for (; j < i; ++j) {
-            const R aj = s_delta[NR + j][threadIdx.x], bj = s_delta[NR + NC + j][threadIdx.x];
-            const R re = p[0], im = p[ts];
-            p[0] = fma_(fma_(ai, aj, bi * bj), a.inv_i, re * a.cov_keep);
-            p[ts] = fma_(fma_(bi, aj, -(ai * bj)), a.inv_i, im * a.cov_keep);
-            p += 2 * ts;
-          }
-          *p = fma_(w2_cplx, a.inv_i, fma_(fma_(ai, ai, bi * bi), a.inv_i, *p * a.cov_keep));
-          p += ts;
-        }
+        // delta is parked in LDS and the tile-major field walked in its own order (covariance_walk, me_packed_walk.h): the
+        // chain's entries lie 64 values apart from the start of its tile
+        covariance_walk(a.cov + (c >> 6) * (long long)P * 64 + (c & 63), s_delta, NR, NC, (int)threadIdx.x, a.inv_i, a.cov_keep,
+                        w2_real, w2_cplx);
       } else {
       // the packed matrix is read whole, then updated and written back (FUSED keeps it for the Cholesky anyway)
       R m[P];
 #pragma unroll
-      for (int k = 0; k < P; ++k) m[k] = src.cov(k);
+      for (int k = 0; k < P; ++k) m[k] = packed_load<NT>(fcov, k, toff);
 #pragma unroll
       for (int i = 0; i < NR; ++i)
 #pragma unroll
@@ -1368,8 +1355,7 @@ __global__ void __launch_bounds__(kStepThreads, ME_MEASURE_WAVES) k_measure(Meas
     R x[D];
 #pragma unroll
     for (int d = 0; d < D; ++d) x[d] = fx.load(d, xoff);
-    const MeasureFromMemory<R, NT, NTM> src{fmean, fobs, fcov, coff, tiled_offset<R>(c, P)};
-    measure_chain<R, NR, NC, PER_CHAIN_COV, FUSED, NT, NTM>(a, c, x, src, fmean, fobs, fcov, ffac, s_delta, [&](R &w_real, R &w_cplx) {
+    measure_chain<R, NR, NC, PER_CHAIN_COV, FUSED, NT, NTM>(a, c, x, fmean, fobs, fcov, ffac, s_delta, [&](R &w_real, R &w_cplx) {
       constexpr bool MIXED = NR > 0 && NC > 0;
       w_real = fw.load((MIXED && a.split_widths) ? 1 : 0, coff);
       w_cplx = fw.load((MIXED && a.split_widths) ? 2 : 0, coff);
@@ -1388,15 +1374,7 @@ __global__ void __launch_bounds__(kStepThreads, ME_MEASURE_WAVES) k_measure(Meas
 // CK: CK_IDENTITY / CK_SHARED (before the 50th measure, or cov_mode fixed / pooled) or CK_PER_CHAIN (each chain's own
 // factor, read once per launch).  NT / NTM: cache policy of the packed fields / the running means, as in k_measure; NT
 // also covers the factor read of the sweeps.  Packed matrices up to kMaxPackedInRegisters entries.
-// Measured (profiles/r03_cycle_prefetch_variants.txt, 10 sweeps per cycle, per-chain factors live): level 0 / 1 / 2 at (4,4) x
-// 2^20 chains 150 / 149 / 155 us (float32), 353 / 354 / 499 us (float64); at (2,7) x 2^18 chains 70 / 70 / 70 us, 185 / 192 /
-// 187 us -- with ten sweeps between the state loads and the measure half the launch is bound by the sweeps' instructions,
-// and the registers the preloaded values occupy cost more than their latency.  Default: off.
-#ifndef ME_CYCLE_PREFETCH
-#define ME_CYCLE_PREFETCH 0       // 0 / 1 / 2 (experiments)
-#endif
-constexpr int cycle_prefetch_level(int, int, int, int) { return ME_CYCLE_PREFETCH; }
-
+// (Requesting the measure half's loads before the sweeps did not pay: profiles/r03_cycle_prefetch_variants.txt.)
 template <typename R, int NR, int NC, class Energy, int CK, bool NT, bool NTM, bool LADDER = false>
 __global__ void ME_STEP_BOUNDS k_cycle(StepArgs<R> a, MeasureArgs<R> ma, Energy en) {
   constexpr int D = NR + 2 * NC;
@@ -1442,22 +1420,6 @@ __global__ void ME_STEP_BOUNDS k_cycle(StepArgs<R> a, MeasureArgs<R> ma, Energy 
       if constexpr (CK == CK_PER_CHAIN) return packed_load<NT>(ffac, k, toff);
       else return a.factor[k];
     };
-    // what the measure half needs from memory is requested BEFORE the sweeps (cycle_prefetch_level: 1 = mean and observables,
-    // 2 = the packed covariance too): the loads travel while the sweeps run instead of after them
-    constexpr int kPrefetch = cycle_prefetch_level(D, NOBS, P, (int)sizeof(R));
-    MeasurePreloaded<R, D, NOBS, P, kPrefetch, NT> pre{{}, {}, {}, fcov, toff};
-    if constexpr (kPrefetch >= 1) {
-#pragma unroll
-      for (int d = 0; d < D; ++d) pre.mu[d] = packed_load<NTM>(fmean, d, coff);
-#pragma unroll
-      for (int k = 0; k < NOBS; ++k) pre.ob[k] = packed_load<NTM>(fobs, k, coff);
-    }
-    if constexpr (kPrefetch >= 2) {
-      if (ma.update_cov) {
-#pragma unroll
-        for (int k = 0; k < P; ++k) pre.cv[k] = packed_load<NT>(fcov, k, toff);
-      }
-    }
     run_sweeps<R, NR, NC, Energy, CKX, false, GROUP_ALL, LADDER>(a, en, c, gid, stale_total, x, ledger, total_q5, w, w_r, w_c, fac,
                                                          wave_accepted, bad_energy);
     bad_width |= !(w > R(0));
@@ -1469,200 +1431,25 @@ __global__ void ME_STEP_BOUNDS k_cycle(StepArgs<R> a, MeasureArgs<R> ma, Energy 
     else ledger.store(fe, coff);
     fw.store(0, coff, w);
     // after a step_all both group widths equal the shared width (:436-437): that is what the epsilon terms use
-    if constexpr (kPrefetch >= 1) {
-      measure_chain<R, NR, NC, true, true, NT, NTM>(ma, c, x, pre, fmean, fobs, fcov, ffac, nullptr,
-                                                    [&](R &w_real, R &w_cplx) { w_real = w_cplx = w; }, bad_pivot);
-    } else {
-      const MeasureFromMemory<R, NT, NTM> src{fmean, fobs, fcov, coff, toff};
-      measure_chain<R, NR, NC, true, true, NT, NTM>(ma, c, x, src, fmean, fobs, fcov, ffac, nullptr,
-                                                    [&](R &w_real, R &w_cplx) { w_real = w_cplx = w; }, bad_pivot);
-    }
+    measure_chain<R, NR, NC, true, true, NT, NTM>(ma, c, x, fmean, fobs, fcov, ffac, nullptr,
+                                                  [&](R &w_real, R &w_cplx) { w_real = w_cplx = w; }, bad_pivot);
   }
-  if ((threadIdx.x & 63) == 0 && wave_accepted) {
-    unsigned long long *slot = a.accept_slots + (size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    *slot += (unsigned long long)wave_accepted;
-  }
-  const unsigned int bits = (bad_energy ? ST_NONFINITE_ENERGY : 0u) | (bad_width ? ST_BAD_WIDTH : 0u) | (bad_pivot ? ST_BAD_PIVOT : 0u);
-  if (bits) atomicOr(a.status, bits);
-}
-
-// Refresh the per-chain proposal factors from the per-chain covariance: factor = chol(C_r), chol(conj(K)).
-template <typename R, int NR, int NC, bool NT>
-__global__ void __launch_bounds__(kStepThreads) k_factor(const R *cov, R *factor, unsigned int *status, long long n) {
-  constexpr int PR = NR * (NR + 1) / 2;
-  constexpr int P = PR + NC * NC;
-  bool bad_pivot = false;
-  const long long stride = (long long)gridDim.x * kStepThreads;
-  const TiledField<R> fcov(cov, n, P), ffac(factor, n, P);
-  for (long long c = (long long)blockIdx.x * kStepThreads + threadIdx.x; c < n; c += stride) {
-    const unsigned int toff = tiled_offset<R>(c, P);
-    R m[P];
-#pragma unroll
-    for (int k = 0; k < P; ++k) m[k] = packed_load<NT>(fcov, k, toff);
-#pragma unroll
-    for (int i = 0; i < NC; ++i)
-#pragma unroll
-      for (int j = 0; j < i; ++j) m[cim(PR, i, j)] = -m[cim(PR, i, j)];   // conj(K) (quirk Q3, :292-298)
-    cholesky_packed<R, NR, NC>(m, bad_pivot);
-#pragma unroll
-    for (int k = 0; k < P; ++k) packed_store<NT>(ffac, k, toff, m[k]);
-  }
-  if (bad_pivot) atomicOr(status, (unsigned int)ST_BAD_PIVOT);
+  publish_step(a, blockDim.x >> 6, wave_accepted, bad_energy, bad_width, bad_pivot);
 }
 
 // Per-chain Cholesky factor of a covariance matrix too large for registers (more than 160 packed entries; pure real
-// spaces): factor = chol(C), row by row (Cholesky-Banachiewicz), each lane its own chain, everything through global
-// memory in the tile-major layout -- L_ij = (C_ij - sum_{k<j} L_ik L_jk) / L_jj.  The row being built lives in LDS
-// ([NR][64 lanes], lane-linear); the finished rows are re-read from the factor field itself, four rows at a time in
-// batches of 4 x 16 loads issued ahead of their multiply-adds.  ROWS rows are built together so that every finished L_jk that is loaded serves
-// ROWS dot products: the traffic is NR^3 / (6 ROWS) loads per chain (64 parameters, ROWS = 4: 11 k loads = 44 KB in
-// float32).  Slow by construction -- an order of magnitude above a measure() with the pooled shape -- and there only
-// so that cov_mode="reference" keeps the reference's semantics (metropolis_engine.py:416-421 feeding :268-270) at any
-// size.  The fields may pass 4 GiB: 64-bit pointers.
+// spaces): factor = chol(C), each lane its own chain, everything through global memory in the tile-major layout, the
+// block of rows being built in LDS (factor_real_rows, me_packed_walk.h).  The fields may pass 4 GiB: 64-bit pointers.
 template <typename R, int NR, bool NT>
 __global__ void __launch_bounds__(kStepThreads) k_factor_stream(const R *cov, R *factor, unsigned int *status, long long n) {
   constexpr int P = NR * (NR + 1) / 2;
   constexpr int ROWS = sizeof(R) == 4 ? 4 : 2;                  // LDS: ROWS x NR x 64 values (64 KiB at NR = 64)
-  using N_ = Num<R>;
-  __shared__ R rows[ROWS][NR][kStepThreads];
+  __shared__ R rows[ROWS * NR][kStepThreads];
   bool bad_pivot = false;
   const long long stride = (long long)gridDim.x * kStepThreads;
-  const int lane = threadIdx.x;
   for (long long c = (long long)blockIdx.x * kStepThreads + threadIdx.x; c < n; c += stride) {
     const long long base = (c >> 6) * (long long)P * 64 + (c & 63);
-    const R *cv = cov + base;
-    R *fc = factor + base;
-    for (int i0 = 0; i0 < NR; i0 += ROWS) {
-      const int nrows = NR - i0 < ROWS ? NR - i0 : ROWS;
-      // the covariance rows of the block into LDS
-      for (int r = 0; r < nrows; ++r) {
-        const R *src = cv + (long long)tri(i0 + r, 0) * 64;
-        int j = 0;
-        for (; j + 16 <= i0 + r + 1; j += 16) {
-          R v[16];
-#pragma unroll
-          for (int u = 0; u < 16; ++u) v[u] = NT ? __builtin_nontemporal_load(src + (j + u) * 64) : src[(j + u) * 64];
-#pragma unroll
-          for (int u = 0; u < 16; ++u) rows[r][j + u][lane] = v[u];
-        }
-        for (; j <= i0 + r; ++j) rows[r][j][lane] = NT ? __builtin_nontemporal_load(src + j * 64) : src[j * 64];
-      }
-      // Columns left of the block: every finished row j < i0 serves all rows of the block.  The walk is bound by memory
-      // LATENCY (every batch of loads a round trip, and column j needs column j - 1 of the block's rows): FOUR finished rows
-      // are fetched together -- their first j entries in batches of 4 x 16 loads, then the ten entries of the little triangle
-      // between them -- and the four columns are finished one after the other from registers (round 3; one row per visit
-      // with two or three dependent round trips each took twice as long: 8.0 -> 4.5 ms per measure at 100 parameters x 2^14
-      // chains in float64, tools/dev/time_compiled_vs_runtime.py).
-      int j = 0;
-      for (; j + 4 <= i0; j += 4) {
-        const R *lj[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) lj[q] = fc + (long long)tri(j + q, 0) * 64;
-        R s[4][ROWS];
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-          for (int r = 0; r < ROWS; ++r) s[q][r] = R(0);
-        int k = 0;
-        for (; k + 16 <= j; k += 16) {
-          R f[4][16];
-#pragma unroll
-          for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int u = 0; u < 16; ++u) f[q][u] = lj[q][(k + u) * 64];
-#pragma unroll
-          for (int u = 0; u < 16; ++u) {
-            R v[ROWS];
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r) v[r] = rows[r][k + u][lane];
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-#pragma unroll
-              for (int r = 0; r < ROWS; ++r) s[q][r] += v[r] * f[q][u];
-          }
-        }
-        for (; k < j; k += 4) {                             // (j is a multiple of 4)
-          R f[4][4];
-#pragma unroll
-          for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int u = 0; u < 4; ++u) f[q][u] = lj[q][(k + u) * 64];
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            R v[ROWS];
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r) v[r] = rows[r][k + u][lane];
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-#pragma unroll
-              for (int r = 0; r < ROWS; ++r) s[q][r] += v[r] * f[q][u];
-          }
-        }
-        R t[4][4];                                          // L[j + q][j + p], p <= q
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-          for (int p = 0; p <= q; ++p) t[q][p] = lj[q][(j + p) * 64];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const R inv = R(1) / t[q][q];
-#pragma unroll
-          for (int r = 0; r < ROWS; ++r) {
-            R acc = s[q][r];
-#pragma unroll
-            for (int p = 0; p < q; ++p) acc += rows[r][j + p][lane] * t[q][p];
-            rows[r][j + q][lane] = (rows[r][j + q][lane] - acc) * inv;
-          }
-        }
-      }
-      for (; j < i0; ++j) {                                 // (at most three rows left)
-        const R *lj = fc + (long long)tri(j, 0) * 64;
-        R s[ROWS];
-#pragma unroll
-        for (int r = 0; r < ROWS; ++r) s[r] = R(0);
-        int k = 0;
-        for (; k + 8 <= j; k += 8) {
-          R f[8];
-#pragma unroll
-          for (int u = 0; u < 8; ++u) f[u] = lj[(k + u) * 64];
-#pragma unroll
-          for (int u = 0; u < 8; ++u)
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r) s[r] += rows[r][k + u][lane] * f[u];
-        }
-        for (; k < j; ++k) {
-          const R f = lj[k * 64];
-#pragma unroll
-          for (int r = 0; r < ROWS; ++r) s[r] += rows[r][k][lane] * f;
-        }
-        const R inv = R(1) / lj[j * 64];
-#pragma unroll
-        for (int r = 0; r < ROWS; ++r) rows[r][j][lane] = (rows[r][j][lane] - s[r]) * inv;
-      }
-      // the triangle inside the block: rows depend on each other here, everything is in LDS
-      for (int r = 0; r < nrows; ++r) {
-        const int i = i0 + r;
-        for (int j = i0; j < i; ++j) {
-          const int rj = j - i0;
-          R s = R(0);
-          for (int k = 0; k < j; ++k) s += rows[r][k][lane] * rows[rj][k][lane];
-          rows[r][j][lane] = (rows[r][j][lane] - s) / rows[rj][j][lane];
-        }
-        R s = rows[r][i][lane];
-        for (int k = 0; k < i; ++k) s -= rows[r][k][lane] * rows[r][k][lane];
-        if (!(s > R(0))) { bad_pivot = true; s = R(1e-30); }
-        rows[r][i][lane] = N_::sqrt_(s);
-      }
-      // finished rows out
-      for (int r = 0; r < nrows; ++r) {
-        R *dst = fc + (long long)tri(i0 + r, 0) * 64;
-        for (int j = 0; j <= i0 + r; ++j) {
-          if constexpr (NT) __builtin_nontemporal_store(rows[r][j][lane], dst + j * 64);
-          else dst[j * 64] = rows[r][j][lane];
-        }
-      }
-      // the next block reads these rows back through global memory from this same lane: program order suffices
-    }
+    factor_real_rows<R, ROWS, NT>(cov + base, factor + base, NR, rows, (int)threadIdx.x, bad_pivot);
   }
   if (bad_pivot) atomicOr(status, (unsigned int)ST_BAD_PIVOT);
 }
@@ -1671,7 +1458,8 @@ __global__ void __launch_bounds__(kStepThreads) k_factor_stream(const R *cov, R 
 // spaces beyond 160 packed entries, e.g. 1 real + 13 complex = 170): factor = [chol(C_r) | chol(conj K)] (quirk Q3,
 // metropolis_engine.py:292-298), row by row (Cholesky-Banachiewicz), each lane its own chain, every operand through global
 // memory in the tile-major layout -- a finished L_ik is re-read from the factor field the lane itself wrote (program order
-// suffices).  Written for correctness, not speed (a dependent load per multiply-add): it exists so that
+// suffices; the complex half is factor_complex_rows, me_packed_walk.h).  Written for correctness, not speed (a dependent
+// load per multiply-add): it exists so that
 // cov_mode="reference" keeps the reference's semantics (:416-427 feeding :274-302) for such spaces at all; the pure real
 // sizes have k_factor_tile / k_factor_stream.
 template <typename R, int NR, int NC, bool NT>
@@ -1696,25 +1484,7 @@ __global__ void __launch_bounds__(kStepThreads) k_factor_mixed(const R *cov, R *
           fc[(long long)tri(i, i) * 64] = N_::sqrt_(s);
         }
       }
-    for (int i = 0; i < NC; ++i)
-      for (int j = 0; j <= i; ++j) {
-        R sr = j < i ? in(cre(PR, i, j)) : in(cdiag(PR, i));
-        R si = j < i ? -in(cim(PR, i, j)) : R(0);                 // conj(K)
-        for (int k = 0; k < j; ++k) {                              // s -= L_ik conj(L_jk)
-          const R ar = fc[(long long)cre(PR, i, k) * 64], ai = fc[(long long)cim(PR, i, k) * 64];
-          const R br = fc[(long long)cre(PR, j, k) * 64], bi = fc[(long long)cim(PR, j, k) * 64];
-          sr = fma_(-ai, bi, fma_(-ar, br, sr));
-          si = fma_(ar, bi, fma_(-ai, br, si));
-        }
-        if (j < i) {
-          const R d = fc[(long long)cdiag(PR, j) * 64];
-          fc[(long long)cre(PR, i, j) * 64] = sr / d;
-          fc[(long long)cim(PR, i, j) * 64] = si / d;
-        } else {
-          if (!(sr > R(0))) { bad_pivot = true; sr = R(1e-30); }
-          fc[(long long)cdiag(PR, i) * 64] = N_::sqrt_(sr);
-        }
-      }
+    factor_complex_rows<R, NT>(cv, fc, PR, NC, bad_pivot);
   }
   if (bad_pivot) atomicOr(status, (unsigned int)ST_BAD_PIVOT);
 }

@@ -33,9 +33,6 @@
 #ifndef ME_TRACK_COV
 #define ME_TRACK_COV 1   // k_measure can maintain the per-chain running covariance (streaming form when ME_PER_CHAIN=0)
 #endif
-#ifndef ME_MEASURE_FUSED_MAX_P
-#define ME_MEASURE_FUSED_MAX_P 160   // largest packed size whose Cholesky is fused into k_measure (all per-chain kernel sets; k_factor stays as the split form)
-#endif
 
 namespace me {
 namespace {
@@ -124,40 +121,6 @@ int energy_terms(int kind) {
   }
 }
 bool has_energy(int kind) { return energy_terms(kind) > 0; }
-
-template <typename R>
-StepArgs<R> typed(const StepLaunch &l) {
-  StepArgs<R> a;
-  a.x = (R *)l.x;
-  a.energy = (R *)l.energy;
-  a.width = (R *)l.width;
-  a.factor = (const R *)l.factor;
-  a.inj_normals = (const R *)l.inj_normals;
-  a.inj_uniforms = (const R *)l.inj_uniforms;
-  a.accept_slots = l.accept_slots;
-  a.status = l.status;
-  a.n = l.n;
-  a.chain_offset = l.chain_offset;
-  a.step_index = l.step_index;
-  a.seed_lo = (uint32_t)l.seed;
-  a.seed_hi = (uint32_t)(l.seed >> 32);
-  a.n_sweeps = l.n_sweeps;
-  a.reject_kind = l.reject_kind;
-  a.split_widths = l.split_widths;
-  a.stale_total = l.stale_total;
-  a.reject_bound = (R)l.reject_bound;
-  a.temp = (R)l.temp;
-  a.inv_temp = l.temp > 0 ? (R)(1.0 / l.temp) : (R)0;
-  a.inv_temp_log2e = l.temp > 0 ? (R)(1.4426950408889634 / l.temp) : (R)0;
-  a.ratio = (R)l.ratio;
-  a.p = (R)l.target_acceptance;
-  a.damping = (R)l.damping;
-  a.up = (R)(l.ratio * (1.0 - l.target_acceptance) / l.damping);
-  a.down = (R)(-l.ratio * l.target_acceptance / l.damping);
-  a.ladder = (const R *)l.ladder;
-  a.tiles_per_rung = l.tiles_per_rung;
-  return a;
-}
 
 template <typename R, class Energy, bool INJECT, int GROUP, bool LADDER>
 hipError_t launch_step_cov(const StepLaunch &l, const StepArgs<R> &a, const Energy &en, dim3 grid, dim3 block,
@@ -394,27 +357,6 @@ hipError_t init_energy(const EnergyLaunch &l, hipStream_t stream) {
   });
 }
 
-template <typename R>
-MeasureArgs<R> typed_measure(const MeasureLaunch &l) {
-  MeasureArgs<R> a;
-  a.x = (const R *)l.x;
-  a.width = (const R *)l.width;
-  a.mean = (R *)l.mean;
-  a.cov = (R *)l.cov;
-  a.obs_mean = (R *)l.obs_mean;
-  a.factor = (R *)l.factor;
-  a.status = l.status;
-  a.n = l.n;
-  const double i = (double)l.measure_count;
-  a.keep = (R)((i - 1.0) / i);
-  a.inv_i = (R)(1.0 / i);
-  a.cov_keep = (R)((i - 2.0) / (i - 1.0));
-  a.update_cov = l.update_cov;
-  a.split_widths = l.split_widths;
-  a.write_factor = l.write_factor;
-  return a;
-}
-
 // n_sweeps x step_all + measure in one launch (k_cycle, me_device.h) for the kernel sets whose packed matrix lives in
 // registers; anything else -- group steps, injected streams, a shared factor, engines that keep no per-chain covariance,
 // the matrix-core kernels of the dense 64-parameter form -- answers hipErrorNotSupported and me_cycle issues two launches.
@@ -467,7 +409,8 @@ hipError_t measure(const MeasureLaunch &l, hipStream_t stream) {
   const MeasureArgs<R> a = typed_measure<R>(l);
   // small packed matrices: one fused launch; large ones: streaming update, then the factor kernel (see k_measure)
   constexpr int P = NR * (NR + 1) / 2 + NC * NC;
-  constexpr bool kFused = ME_PER_CHAIN == 1 && P <= ME_MEASURE_FUSED_MAX_P;
+  constexpr bool kFused = ME_PER_CHAIN == 1;     // packed matrices that fit in registers: the Cholesky is fused into k_measure
+  static_assert(ME_PER_CHAIN != 1 || P <= kMaxPackedInRegisters, "ME_PER_CHAIN=1 keeps the packed matrix in registers");
   const dim3 grid(grid_for(l.n, l.grid_blocks)), block(kStepThreads);
   // Cache policy by size (k_measure's comment in me_device.h): the packed fields go non-temporal when the whole working
   // set (x, means, observables, covariance, factor) exceeds the Infinity Cache; the means and observables too when even
@@ -484,14 +427,7 @@ hipError_t measure(const MeasureLaunch &l, hipStream_t stream) {
     if (ntm) hipLaunchKernelGGL((k_measure<R, NR, NC, false, false, false, true>), grid, block, 0, stream, a);
     else hipLaunchKernelGGL((k_measure<R, NR, NC, false, false, false, false>), grid, block, 0, stream, a);
   }
-#if ME_PER_CHAIN == 1
-  if constexpr (!kFused) {
-    if (l.update_cov && l.write_factor) {
-      if (nt) hipLaunchKernelGGL((k_factor<R, NR, NC, true>), grid, block, 0, stream, (const R *)l.cov, (R *)l.factor, l.status, l.n);
-      else hipLaunchKernelGGL((k_factor<R, NR, NC, false>), grid, block, 0, stream, (const R *)l.cov, (R *)l.factor, l.status, l.n);
-    }
-  }
-#elif ME_PER_CHAIN == 2
+#if ME_PER_CHAIN == 2
   static_assert(P > kMaxPackedInRegisters, "ME_PER_CHAIN=2 is for spaces with more than 160 packed entries");
   if (l.cov && l.update_cov && l.write_factor) {
     if constexpr (NC > 0) {       // a complex block: the plain one-lane-per-chain form (k_factor_mixed, me_device.h)

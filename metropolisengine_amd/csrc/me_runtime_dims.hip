@@ -90,14 +90,7 @@ __global__ void __launch_bounds__(kBlockThreads) k_step_runtime(StepArgs<R> a, R
     const unsigned long long gid = a.chain_offset + (unsigned long long)c;
     for (int s = 0; s < a.n_sweeps; ++s) {
       const unsigned long long step = a.step_index + (unsigned long long)s;
-      auto block_of = [&](int b) {
-        U4 ctr;
-        ctr.x = (uint32_t)gid;
-        ctr.y = (uint32_t)(gid >> 32);
-        ctr.z = (uint32_t)step;
-        ctr.w = ((uint32_t)(step >> 32) << 16) | (uint32_t)b;
-        return philox4x32_10(ctr, a.seed_lo, a.seed_hi);
-      };
+      auto block_of = [&](int b) { return philox_block(gid, step, b, a.seed_lo, a.seed_hi); };
       const R s_r = w_r, s_c = w_c * R(0.70710678118654752440);
       // ---- pass 1: proposed energy (and the proposed x_0 for the wall)
       R e_new = R(0), xp0 = R(0);
@@ -154,74 +147,60 @@ __global__ void __launch_bounds__(kBlockThreads) k_step_runtime(StepArgs<R> a, R
     a.energy[c] = e;
     a.width[(long long)wrow * n + c] = w;
   }
-  if ((threadIdx.x & 63) == 0 && wave_accepted) {
-    unsigned long long *slot = a.accept_slots + (size_t)blockIdx.x * (kBlockThreads >> 6) + (threadIdx.x >> 6);
-    *slot += (unsigned long long)wave_accepted;
+  publish_step(a, kBlockThreads >> 6, wave_accepted, bad_energy, bad_width);
+}
+
+// Running means (:404-410) and observables [|x_r|, |z_c|, x_r^2] with their running means (:458-463, :412-414) of chain c,
+// the arithmetic spelled as in measure_chain (me_device.h).  delta: where x - mu_old is parked for the covariance walk
+// ([D][64], this lane's column), or nullptr.
+template <typename R>
+__device__ __forceinline__ void runtime_means_and_observables(const MeasureArgs<R> &a, int nr, int nc, long long c,
+                                                              R (*delta)[kStepThreads], int lane) {
+  using N_ = Num<R>;
+  const int D = nr + 2 * nc, nobs = 2 * nr + nc;
+  const long long n = a.n;
+  for (int d = 0; d < D; ++d) {
+    const long long i = (long long)d * n + c;
+    const R mu = a.mean[i], xd = a.x[i];
+    if (delta) delta[d][lane] = xd - mu;
+    a.mean[i] = fma_(xd, a.inv_i, mu * a.keep);
   }
-  const unsigned int bits = (bad_energy ? ST_NONFINITE_ENERGY : 0u) | (bad_width ? ST_BAD_WIDTH : 0u);
-  if (bits) atomicOr(a.status, bits);
+  for (int k = 0; k < nobs; ++k) {
+    R o;
+    if (k < nr) o = N_::abs_(a.x[(long long)k * n + c]);
+    else if (k < nr + nc) {
+      const R re = a.x[(long long)k * n + c], im = a.x[(long long)(k + nc) * n + c];
+      o = N_::sqrt_(fma_(re, re, im * im));
+    } else {
+      const R v = a.x[(long long)(k - nr - nc) * n + c];
+      o = v * v;
+    }
+    const long long i = (long long)k * n + c;
+    a.obs_mean[i] = fma_(o, a.inv_i, a.obs_mean[i] * a.keep);
+  }
 }
 
 template <typename R>
 __global__ void __launch_bounds__(kBlockThreads) k_measure_runtime(MeasureArgs<R> a, int nr, int nc) {
-  using N_ = Num<R>;
-  const int D = nr + 2 * nc, nobs = 2 * nr + nc;
-  const long long stride = (long long)gridDim.x * kBlockThreads, n = a.n;
-  for (long long c = (long long)blockIdx.x * kBlockThreads + threadIdx.x; c < n; c += stride) {
-    for (int d = 0; d < D; ++d) {                                                          // :404-410
-      const long long i = (long long)d * n + c;
-      a.mean[i] = a.mean[i] * a.keep + a.x[i] * a.inv_i;
-    }
-    for (int k = 0; k < nobs; ++k) {                                                       // :458-463, :412-414
-      R o;
-      if (k < nr) o = N_::abs_(a.x[(long long)k * n + c]);
-      else if (k < nr + nc) {
-        const R re = a.x[(long long)k * n + c], im = a.x[(long long)(k + nc) * n + c];
-        o = N_::sqrt_(re * re + im * im);
-      } else {
-        const R v = a.x[(long long)(k - nr - nc) * n + c];
-        o = v * v;
-      }
-      const long long i = (long long)k * n + c;
-      a.obs_mean[i] = a.obs_mean[i] * a.keep + o * a.inv_i;
-    }
-  }
+  const long long stride = (long long)gridDim.x * kBlockThreads;
+  for (long long c = (long long)blockIdx.x * kBlockThreads + threadIdx.x; c < a.n; c += stride)
+    runtime_means_and_observables<R>(a, nr, nc, c, nullptr, 0);
 }
 
-// measure() of an engine that keeps per-chain covariance matrices at runtime dimensions (cov_mode="reference" on pure real
-// spaces, or the tracking flag): means and observables as above, then the covariance recursion of k_measure's streaming
-// path (me_device.h: delta = x - mu_old parked in LDS, the packed entries of the tile-major field walked in their own
-// order, batches of loads ahead of their updates; :416-427 in the one-pass form).  One wavefront per block, one lane per
-// chain, dynamic LDS delta[D][64].
+// measure() of an engine that keeps per-chain covariance matrices at runtime dimensions (cov_mode="reference", or the
+// tracking flag): means and observables as above, then the covariance recursion of k_measure's streaming path
+// (covariance_walk, me_packed_walk.h: delta = x - mu_old parked in LDS, the packed entries of the tile-major field walked
+// in their own order; :416-427 in the one-pass form).  One wavefront per block, one lane per chain, dynamic LDS delta[D][64].
 template <typename R>
 __global__ void __launch_bounds__(kStepThreads) k_measure_runtime_cov(MeasureArgs<R> a, int nr, int nc) {
-  using N_ = Num<R>;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_rt[];
   R(*delta)[kStepThreads] = reinterpret_cast<R(*)[kStepThreads]>(smem_rt);
-  const int D = nr + 2 * nc, nobs = 2 * nr + nc, lane = threadIdx.x;
+  const int lane = threadIdx.x;
   const long long P = (long long)nr * (nr + 1) / 2 + (long long)nc * nc;
   const bool mixed = nr > 0 && nc > 0;
   const long long stride = (long long)gridDim.x * kStepThreads, n = a.n;
   for (long long c = (long long)blockIdx.x * kStepThreads + threadIdx.x; c < n; c += stride) {
-    for (int d = 0; d < D; ++d) {                                                          // :404-410
-      const long long i = (long long)d * n + c;
-      const R mu = a.mean[i], xd = a.x[i];
-      delta[d][lane] = xd - mu;
-      a.mean[i] = mu * a.keep + xd * a.inv_i;
-    }
-    for (int k = 0; k < nobs; ++k) {                                                       // :458-463, :412-414
-      R o;
-      if (k < nr) o = N_::abs_(a.x[(long long)k * n + c]);
-      else if (k < nr + nc) {
-        const R re = a.x[(long long)k * n + c], im = a.x[(long long)(k + nc) * n + c];
-        o = N_::sqrt_(re * re + im * im);
-      } else {
-        const R v = a.x[(long long)(k - nr - nc) * n + c];
-        o = v * v;
-      }
-      const long long i = (long long)k * n + c;
-      a.obs_mean[i] = a.obs_mean[i] * a.keep + o * a.inv_i;
-    }
+    runtime_means_and_observables(a, nr, nc, c, delta, lane);
     if (!a.update_cov) continue;
     // :418, :425 -- each block uses its own group's width; they coincide unless group steps made them differ
     R w_real = a.width[c], w_cplx = w_real;
@@ -229,224 +208,38 @@ __global__ void __launch_bounds__(kStepThreads) k_measure_runtime_cov(MeasureArg
       w_real = a.width[(long long)GROUP_REAL * n + c];
       w_cplx = a.width[(long long)GROUP_COMPLEX * n + c];
     }
-    const R w2_real = w_real * w_real, w2_cplx = w_cplx * w_cplx;
-    R *q = a.cov + (c >> 6) * P * 64 + (c & 63);
-    constexpr long long ts = 64;
-    for (int i = 0; i < nr; ++i) {
-      const R di = delta[i][lane];
-      int j = 0;
-      for (; j + 16 <= i; j += 16) {       // all loads first: a store to q[.] would fence the next load
-        R v[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) v[u] = q[u * ts];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) q[u * ts] = fma_(di * delta[j + u][lane], a.inv_i, v[u] * a.cov_keep);
-        q += 16 * ts;
-      }
-      for (; j < i; ++j) {
-        *q = fma_(di * delta[j][lane], a.inv_i, *q * a.cov_keep);
-        q += ts;
-      }
-      *q = fma_(w2_real, a.inv_i, fma_(di * di, a.inv_i, *q * a.cov_keep));
-      q += ts;
-    }
-    for (int i = 0; i < nc; ++i) {         // the Hermitian block: (Re, Im) of the columns j < i, then the real diagonal
-      const R ai = delta[nr + i][lane], bi = delta[nr + nc + i][lane];
-      for (int j = 0; j < i; ++j) {
-        const R aj = delta[nr + j][lane], bj = delta[nr + nc + j][lane];
-        const R re = q[0], im = q[ts];
-        q[0] = fma_(fma_(ai, aj, bi * bj), a.inv_i, re * a.cov_keep);
-        q[ts] = fma_(fma_(bi, aj, -(ai * bj)), a.inv_i, im * a.cov_keep);
-        q += 2 * ts;
-      }
-      *q = fma_(w2_cplx, a.inv_i, fma_(fma_(ai, ai, bi * bi), a.inv_i, *q * a.cov_keep));
-      q += ts;
-    }
+    covariance_walk(a.cov + (c >> 6) * P * 64 + (c & 63), delta, nr, nc, lane, a.inv_i, a.cov_keep, w_real * w_real, w_cplx * w_cplx);
   }
 }
 
-// factor = chol(C) per chain at runtime dimensions (pure real spaces): k_factor_stream of me_device.h with the row block in
-// dynamic LDS (rows[ROWS][nr][64]) -- Cholesky-Banachiewicz, each lane its own chain, finished rows re-read from the
-// factor field itself, ROWS rows built together so that every finished L_jk that is loaded serves ROWS dot products.
+// factor = chol(C) per chain at runtime dimensions, the real block: factor_real_rows (me_packed_walk.h, what k_factor_stream
+// of me_device.h runs) with the row block in dynamic LDS (rows[ROWS][nr][64]).
 template <typename R, int ROWS>
 __global__ void __launch_bounds__(kStepThreads) k_factor_runtime(const R *cov, R *factor, unsigned int *status, long long n, int nr,
                                                                  long long P) {      // P: packed entries per chain (real + Hermitian block)
-  using N_ = Num<R>;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_rt[];
   R(*lds)[kStepThreads] = reinterpret_cast<R(*)[kStepThreads]>(smem_rt);
-  auto row_of = [&](int r) { return lds + (size_t)r * nr; };          // rows[r][k][lane] = row_of(r)[k][lane]
   bool bad_pivot = false;
   const long long stride = (long long)gridDim.x * kStepThreads;
-  const int lane = threadIdx.x;
   for (long long c = (long long)blockIdx.x * kStepThreads + threadIdx.x; c < n; c += stride) {
     const long long base = (c >> 6) * P * 64 + (c & 63);
-    const R *cv = cov + base;
-    R *fc = factor + base;
-    for (int i0 = 0; i0 < nr; i0 += ROWS) {
-      const int nrows = nr - i0 < ROWS ? nr - i0 : ROWS;
-      for (int r = 0; r < nrows; ++r) {                    // the covariance rows of the block into LDS
-        const R *src = cv + (long long)tri(i0 + r, 0) * 64;
-        int j = 0;
-        for (; j + 16 <= i0 + r + 1; j += 16) {
-          R v[16];
-#pragma unroll
-          for (int u = 0; u < 16; ++u) v[u] = src[(j + u) * 64];
-#pragma unroll
-          for (int u = 0; u < 16; ++u) row_of(r)[j + u][lane] = v[u];
-        }
-        for (; j <= i0 + r; ++j) row_of(r)[j][lane] = src[j * 64];
-      }
-      // Columns left of the block: finished row j serves all rows of the block.  The walk is bound by memory LATENCY (one
-      // wavefront per SIMD at most, every batch of loads a round trip), and column j needs column j - 1 of the block's rows:
-      // FOUR finished rows are therefore fetched together -- their first j entries in batches of 4 x 16 loads, then the ten
-      // entries of the little triangle between them -- and the four columns are finished one after the other from registers.
-      int j = 0;
-      for (; j + 4 <= i0; j += 4) {
-        const R *lj[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) lj[q] = fc + (long long)tri(j + q, 0) * 64;
-        R sum[4][ROWS];
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-          for (int r = 0; r < ROWS; ++r) sum[q][r] = R(0);
-        int k = 0;
-        for (; k + 16 <= j; k += 16) {
-          R f[4][16];
-#pragma unroll
-          for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int u = 0; u < 16; ++u) f[q][u] = lj[q][(k + u) * 64];
-#pragma unroll
-          for (int u = 0; u < 16; ++u) {
-            R v[ROWS];
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r) v[r] = r < nrows ? row_of(r)[k + u][lane] : R(0);
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-#pragma unroll
-              for (int r = 0; r < ROWS; ++r) sum[q][r] += v[r] * f[q][u];
-          }
-        }
-        for (; k < j; k += 4) {                             // (j is a multiple of 4)
-          R f[4][4];
-#pragma unroll
-          for (int q = 0; q < 4; ++q)
-#pragma unroll
-            for (int u = 0; u < 4; ++u) f[q][u] = lj[q][(k + u) * 64];
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            R v[ROWS];
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r) v[r] = r < nrows ? row_of(r)[k + u][lane] : R(0);
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-#pragma unroll
-              for (int r = 0; r < ROWS; ++r) sum[q][r] += v[r] * f[q][u];
-          }
-        }
-        R t[4][4];                                          // L[j + q][j + p], p <= q
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-#pragma unroll
-          for (int p = 0; p <= q; ++p) t[q][p] = lj[q][(j + p) * 64];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const R inv = R(1) / t[q][q];
-#pragma unroll
-          for (int r = 0; r < ROWS; ++r)
-            if (r < nrows) {
-              R acc = sum[q][r];
-#pragma unroll
-              for (int p = 0; p < q; ++p) acc += row_of(r)[j + p][lane] * t[q][p];
-              row_of(r)[j + q][lane] = (row_of(r)[j + q][lane] - acc) * inv;
-            }
-        }
-      }
-      for (; j < i0; ++j) {                                 // (at most three rows left)
-        const R *lj = fc + (long long)tri(j, 0) * 64;
-        R sum[ROWS];
-#pragma unroll
-        for (int r = 0; r < ROWS; ++r) sum[r] = R(0);
-        int k = 0;
-        for (; k + 16 <= j; k += 16) {
-          R f[16];
-#pragma unroll
-          for (int u = 0; u < 16; ++u) f[u] = lj[(k + u) * 64];
-#pragma unroll
-          for (int u = 0; u < 16; ++u)
-#pragma unroll
-            for (int r = 0; r < ROWS; ++r)
-              if (r < nrows) sum[r] += row_of(r)[k + u][lane] * f[u];
-        }
-        for (; k < j; ++k) {
-          const R f = lj[k * 64];
-#pragma unroll
-          for (int r = 0; r < ROWS; ++r)
-            if (r < nrows) sum[r] += row_of(r)[k][lane] * f;
-        }
-        const R inv = R(1) / lj[j * 64];
-#pragma unroll
-        for (int r = 0; r < ROWS; ++r)
-          if (r < nrows) row_of(r)[j][lane] = (row_of(r)[j][lane] - sum[r]) * inv;
-      }
-      for (int r = 0; r < nrows; ++r) {                    // the triangle inside the block: everything is in LDS
-        const int i = i0 + r;
-        for (int j = i0; j < i; ++j) {
-          const int rj = j - i0;
-          R t = R(0);
-          for (int k = 0; k < j; ++k) t += row_of(r)[k][lane] * row_of(rj)[k][lane];
-          row_of(r)[j][lane] = (row_of(r)[j][lane] - t) / row_of(rj)[j][lane];
-        }
-        R t = row_of(r)[i][lane];
-        for (int k = 0; k < i; ++k) t -= row_of(r)[k][lane] * row_of(r)[k][lane];
-        if (!(t > R(0))) { bad_pivot = true; t = R(1e-30); }
-        row_of(r)[i][lane] = N_::sqrt_(t);
-      }
-      for (int r = 0; r < nrows; ++r) {                    // finished rows out (re-read by this same lane: program order suffices)
-        R *dst = fc + (long long)tri(i0 + r, 0) * 64;
-        for (int j = 0; j <= i0 + r; ++j) dst[j * 64] = row_of(r)[j][lane];
-      }
-    }
+    factor_real_rows<R, ROWS, false>(cov + base, factor + base, nr, lds, (int)threadIdx.x, bad_pivot);
   }
   if (bad_pivot) atomicOr(status, (unsigned int)ST_BAD_PIVOT);
 }
 
-// The Hermitian block of the factor at runtime dimensions: L = chol(conj K) (quirk Q3, metropolis_engine.py:292-298), the
-// complex half of k_factor_mixed (me_device.h) with runtime sizes -- row by row, each lane its own chain, every operand
-// through global memory (a finished L_ik is re-read from the factor field the lane itself wrote).  Written for
-// correctness, not speed.
+// The Hermitian block of the factor at runtime dimensions: factor_complex_rows (me_packed_walk.h, the complex half of
+// k_factor_mixed) behind the nr (nr + 1) / 2 real entries.
 template <typename R>
 __global__ void __launch_bounds__(kStepThreads) k_factor_runtime_complex(const R *cov, R *factor, unsigned int *status, long long n, int nr,
                                                                          int nc) {
-  using N_ = Num<R>;
-  const long long PR = (long long)nr * (nr + 1) / 2, P = PR + (long long)nc * nc;
+  const int PR = nr * (nr + 1) / 2;
+  const long long P = PR + (long long)nc * nc;
   bool bad_pivot = false;
   const long long stride = (long long)gridDim.x * kStepThreads;
   for (long long c = (long long)blockIdx.x * kStepThreads + threadIdx.x; c < n; c += stride) {
     const long long base = (c >> 6) * P * 64 + (c & 63);
-    const R *cv = cov + base;
-    R *fc = factor + base;
-    auto re_at = [&](int i, int j) { return (PR + (long long)i * i + 2 * j) * 64; };      // cre; cim = + 64; cdiag = re_at(i, i)
-    for (int i = 0; i < nc; ++i)
-      for (int j = 0; j <= i; ++j) {
-        R sr = cv[re_at(i, j)];
-        R si = j < i ? -cv[re_at(i, j) + 64] : R(0);                // conj(K)
-        for (int k = 0; k < j; ++k) {                                // s -= L_ik conj(L_jk)
-          const R ar = fc[re_at(i, k)], ai = fc[re_at(i, k) + 64];
-          const R br = fc[re_at(j, k)], bi = fc[re_at(j, k) + 64];
-          sr = fma_(-ai, bi, fma_(-ar, br, sr));
-          si = fma_(ar, bi, fma_(-ai, br, si));
-        }
-        if (j < i) {
-          const R d = fc[re_at(j, j)];
-          fc[re_at(i, j)] = sr / d;
-          fc[re_at(i, j) + 64] = si / d;
-        } else {
-          if (!(sr > R(0))) { bad_pivot = true; sr = R(1e-30); }
-          fc[re_at(i, i)] = N_::sqrt_(sr);
-        }
-      }
+    factor_complex_rows<R, false>(cov + base, factor + base, PR, nc, bad_pivot);
   }
   if (bad_pivot) atomicOr(status, (unsigned int)ST_BAD_PIVOT);
 }
@@ -650,14 +443,7 @@ __global__ void __launch_bounds__(kStepThreads) k_step_runtime_lds(StepArgs<R> a
     const unsigned long long gid = a.chain_offset + (unsigned long long)c;
     for (int s = 0; s < a.n_sweeps; ++s) {
       const unsigned long long step = a.step_index + (unsigned long long)s;
-      auto block_of = [&](int b) {
-        U4 ctr;
-        ctr.x = (uint32_t)gid;
-        ctr.y = (uint32_t)(gid >> 32);
-        ctr.z = (uint32_t)step;
-        ctr.w = ((uint32_t)(step >> 32) << 16) | (uint32_t)b;
-        return philox4x32_10(ctr, a.seed_lo, a.seed_hi);
-      };
+      auto block_of = [&](int b) { return philox_block(gid, step, b, a.seed_lo, a.seed_hi); };
       const R s_r = w_r, s_c = w_c * R(0.70710678118654752440);
       // ---- the state into x' first, sixteen loads in flight at a time (issued one by one where they are used, every
       // load would expose the whole memory latency: one wavefront per SIMD has nothing else to run)
@@ -828,12 +614,7 @@ __global__ void __launch_bounds__(kStepThreads) k_step_runtime_lds(StepArgs<R> a
       a.width[(long long)wrow * n + c] = w;
     }
   }
-  if ((threadIdx.x & 63) == 0 && wave_accepted) {
-    unsigned long long *slot = a.accept_slots + (size_t)blockIdx.x * (kStepThreads >> 6) + (threadIdx.x >> 6);
-    *slot += (unsigned long long)wave_accepted;
-  }
-  const unsigned int bits = (bad_energy ? ST_NONFINITE_ENERGY : 0u) | (bad_width ? ST_BAD_WIDTH : 0u);
-  if (bits) atomicOr(a.status, bits);
+  publish_step(a, kStepThreads >> 6, wave_accepted, bad_energy, bad_width);
 }
 
 template <typename R>
@@ -896,35 +677,12 @@ hipError_t step(const StepLaunch &l, hipStream_t stream) {
   if (l.group != GROUP_ALL && !mixed) return hipErrorInvalidValue;
   RuntimeStep<R> p;
   if (!fill(p, l.n_real, l.n_complex, l.group, l.energy_kind, l.coef_host, l.n_coef, l.coef_device)) return hipErrorInvalidValue;
-  StepArgs<R> a{};
-  a.x = (R *)l.x;
-  a.energy = (R *)l.energy;
-  a.width = (R *)l.width;
-  a.accept_slots = l.accept_slots;
-  a.status = l.status;
-  a.n = l.n;
-  a.chain_offset = l.chain_offset;
-  a.step_index = l.step_index;
-  a.seed_lo = (uint32_t)l.seed;
-  a.seed_hi = (uint32_t)(l.seed >> 32);
-  a.n_sweeps = l.n_sweeps;
-  a.reject_kind = l.reject_kind;
-  a.split_widths = l.split_widths;
-  a.reject_bound = (R)l.reject_bound;
-  a.temp = (R)l.temp;
-  a.inv_temp = l.temp > 0 ? (R)(1.0 / l.temp) : (R)0;
-  a.inv_temp_log2e = l.temp > 0 ? (R)(1.4426950408889634 / l.temp) : (R)0;
-  a.ratio = (R)l.ratio;
-  a.p = (R)l.target_acceptance;
-  a.damping = (R)l.damping;
-  a.up = (R)(l.ratio * (1.0 - l.target_acceptance) / l.damping);
-  a.down = (R)(-l.ratio * l.target_acceptance / l.damping);
+  const StepArgs<R> a = typed<R>(l);
   if (l.energy_kind == ME_ENERGY_DENSE_QUAD || l.cov_kind != CK_IDENTITY) {
     // the LDS form: one wavefront per block, x' (and, with a shared factor, g) parked per lane
     const bool shared = l.cov_kind == CK_SHARED;
     const size_t lds = (size_t)(l.n_real + 2 * l.n_complex) * kStepThreads * sizeof(R) * (shared ? 2 : 1);
     if (lds > kRuntimeLdsLimit) return hipErrorNotSupported;
-    a.factor = (const R *)l.factor;
     long long blocks = (l.n + kStepThreads - 1) / kStepThreads;
     if (l.grid_blocks > 0 && blocks > l.grid_blocks) blocks = l.grid_blocks;
     const R *folded = l.energy_kind == ME_ENERGY_DENSE_QUAD ? (const R *)l.coef_device : nullptr;
@@ -951,22 +709,7 @@ hipError_t step(const StepLaunch &l, hipStream_t stream) {
 
 template <typename R>
 hipError_t measure(const MeasureLaunch &l, hipStream_t stream) {
-  MeasureArgs<R> a{};
-  a.x = (const R *)l.x;
-  a.width = (const R *)l.width;
-  a.mean = (R *)l.mean;
-  a.cov = (R *)l.cov;
-  a.obs_mean = (R *)l.obs_mean;
-  a.factor = (R *)l.factor;
-  a.status = l.status;
-  a.n = l.n;
-  const double i = (double)l.measure_count;
-  a.keep = (R)((i - 1.0) / i);
-  a.inv_i = (R)(1.0 / i);
-  a.cov_keep = (R)((i - 2.0) / (i - 1.0));
-  a.update_cov = l.update_cov;
-  a.split_widths = l.split_widths;
-  a.write_factor = l.write_factor;
+  const MeasureArgs<R> a = typed_measure<R>(l);
   if (!l.cov) {
     hipLaunchKernelGGL(k_measure_runtime<R>, dim3(grid_of(l.n, l.grid_blocks)), dim3(kBlockThreads), 0, stream, a, l.n_real,
                        l.n_complex);

@@ -11,8 +11,7 @@ store, so (covariance read back, factor read back) is exactly (input, output) of
 Case -> kernel (dispatch: csrc/me_kernels.hip ``measure`` / ``cycle``, csrc/me_runtime_dims.hip ``measure``):
 
     (1,0) (16,0) (17,0) (4,4) (2,7) (0,12)   cholesky_packed in registers, fused into k_measure (<= 160 packed entries; (17,0)
-                                             with 153 and (0,12) with 144 are the largest real / complex ones).  The split
-                                             k_factor runs the same cholesky_packed and is not dispatched by any built set.
+                                             with 153 and (0,12) with 144 are the largest real / complex ones)
     (4,4) (16,0) through cycle(1)            cholesky_packed fused into k_cycle
     18 31 32                                 k_factor_tile, 32 lanes per chain, two chains per wavefront (18: 171 entries, the
                                              smallest streamed size; 31, 32: the full lane group)

@@ -2,9 +2,14 @@
 of freedom of the register-resident kernels.  The reference has no limit on the number of parameters
 (metropolis_engine.py:41-60).  float64 follows the many-chain oracle on the same Philox streams (1e-9): step_all, fused
 sweeps, group-wise steps of a mixed engine, the hard wall, T = 0, measure(); float32 is checked on stationary moments."""
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 
+import cholesky_reference as cr
 import metropolisengine_amd as me
 from metropolisengine_amd import build
 from oracle import energies
@@ -402,3 +407,71 @@ def test_cycle_on_the_runtime_dimension_set_is_step_all_plus_measure():
     for field in range(7):
         assert np.array_equal(a._get(field), b._get(field)), field
     assert a.accept_stats() == b.accept_stats()
+
+
+SHARED_WALK_FIELDS = ("mean", "obs_mean", "cov", "factor")
+
+
+def measure_crafted_checkpoint(dtype):
+    """One measure() of a 100-parameter cov_mode="reference" engine from a crafted checkpoint (the method of
+    tests/test_gpu_cholesky_conformance.py): "spd" matrices, a different one per chain, 10^4 measures behind it, identity
+    factors, width 1e-3, and running means 0.01 off the parameters so that the rank-one term of the recursion is exercised.
+    Returns what that measure refreshed."""
+    nr, n = 100, 64 + 7
+    eng = me.MetropolisEngine(me.IsoQuadratic(1.0), None, [0.1] * nr, None, temp=1.0, n_chains=n, seed=7, dtype=dtype,
+                              sampling_width=1e-3)
+    assert eng.cov_mode == "reference"
+    state = eng.state_dict()
+    state["cov"] = cr.pack(cr.make_class("spd", n, nr, dtype, seed=500), None)
+    state["mean"] = state["params"] + 0.01
+    state["factor"] = cr.packed_identity(n, nr, 0)
+    state["measure_step_counter"] = 10 ** 4
+    state["uses_per_chain_factors"] = True
+    eng.load_state_dict(state)
+    eng.measure()
+    eng.sync()
+    after = eng.state_dict()
+    return {name: after[name] for name in SHARED_WALK_FIELDS}
+
+
+RUNTIME_SET_CHILD = """
+import sys
+import numpy as np
+sys.path[:0] = [%r, %r]
+from metropolisengine_amd import build
+build.MAX_COMPILED_DOF = build.MAX_REGISTER_DOF        # per-chain shapes beyond 96 parameters: the runtime-dimension set
+def no_plugin(*args, **kwargs):
+    raise AssertionError("the runtime-dimension set needs no compiled kernel set")
+build.build_dims = no_plugin
+import test_gpu_runtime_dims as tests
+np.savez(sys.argv[2], **tests.measure_crafted_checkpoint(sys.argv[1]))
+"""
+
+
+@pytest.mark.parametrize("dtype", ["f32", "f64"])
+def test_compiled_and_runtime_sets_refresh_the_same_numbers(dtype, tmp_path):
+    """The compile-time kernel set of a streamed space and the runtime-dimension set run the SAME walks
+    (csrc/me_packed_walk.h), so one measure() from the same checkpoint must leave the same bits: running means, observable
+    means, packed covariance, packed factor.  100 real parameters: the (100,0) set is prebuilt (build_examples), and at 100
+    both sets build ROWS = 4 (float32) / 2 (float64) rows of the factor together -- ROWS decides which columns are divided by
+    a pivot and which are multiplied by its reciprocal, so only equal ROWS can give equal bits.  64 + 7 chains: a ragged
+    second tile.  The runtime-dimension set runs in a fresh child process (a loaded plugin wins the kernel-set lookup for the
+    rest of a process) that lowers build.MAX_COMPILED_DOF before it constructs its engine."""
+    assert os.path.exists(build.dims_plugin_path(100, 0))
+    compiled = measure_crafted_checkpoint(dtype)
+    tests_dir = os.path.dirname(os.path.abspath(__file__))
+    out = str(tmp_path / "runtime_set.npz")
+    # A child that hangs or dies of a signal may have faulted the device: pytest.exit ends the whole session, so that nothing
+    # more is started on it (as the child-process tests of tests/test_gpu_dense_product_conformance.py do).
+    try:
+        res = subprocess.run([sys.executable, "-c", RUNTIME_SET_CHILD % (os.path.dirname(tests_dir), tests_dir), dtype, out],
+                             capture_output=True, text=True, timeout=120)
+    except subprocess.TimeoutExpired:
+        pytest.exit("the runtime-dimension child process hung: nothing more is started on this device", returncode=1)
+    if res.returncode < 0 or res.returncode in (124, 134, 137, 139):
+        pytest.exit("the runtime-dimension child process died with status %d:\n%s" % (res.returncode, res.stderr[-2000:]),
+                    returncode=1)
+    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-2000:]
+    runtime = np.load(out)
+    for name in SHARED_WALK_FIELDS:
+        assert np.array_equal(compiled[name], runtime[name]), name
