@@ -165,48 +165,19 @@ template <int CK, int THREADS>
 __global__ void __launch_bounds__(THREADS, 2) k_step_dense64_bf16x3(StepArgs<float> a,
                                                                              const unsigned int *__restrict__ afrag,
                                                                              const unsigned int *lfrag) {
-  constexpr int D = 64;
-  using N_ = Num<float>;
   using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
   extern __shared__ __attribute__((aligned(16))) unsigned int smem_u[];
   unsigned int *lds_a = smem_u;
   constexpr int FRAG_WORDS = dense64_lds_frag_words<THREADS>();
   const unsigned int *a_piece3 = THREADS == 512 ? lds_a : afrag;   // see dense64_bf16_lds_bytes
-  float *lds_xp = reinterpret_cast<float *>(smem_u + FRAG_WORDS) + threadIdx.x;   // this lane's column, stride THREADS
+  Dense64Tile<THREADS> tile(a, reinterpret_cast<float *>(smem_u + FRAG_WORDS));
 
   const int lane = threadIdx.x & 63;
   unsigned int wave_accepted = 0;
   bool bad_energy = false, bad_width = false;
   const long long stride = (long long)gridDim.x * THREADS;
-  const XField<float, D> fx(a.x, a.n);      // tile-major: a wavefront's 64 rows are one contiguous 16 KiB block
-  const Field<float> fe(a.energy, a.n, 1), fw(a.width, a.n, 1);
-
-  // every lane stays active (MFMA and permlane need the whole wavefront): tail lanes shadow the last chain
   long long base = (long long)blockIdx.x * THREADS + (threadIdx.x & ~63);
   bool have = base < a.n;
-  bool live = false;
-  unsigned int coff = 0, xoff = 0;
-  unsigned long long gid = 0;
-  float x[D], e = 0.0f, w = 0.0f;
-  // Loads are issued in the order the first sweep consumes them (width, then rows 0, 1, 2, ...): memory returns in
-  // order, so the s_waitcnt before the first use of row 4b can leave the later rows in flight behind the Philox
-  // work.  Left to the scheduler the rows were issued scrambled and the first use waited for (almost) all of them.
-  auto load_tile = [&]() {
-    const long long c_raw = base + lane;
-    live = c_raw < a.n;
-    const long long c = live ? c_raw : a.n - 1;
-    coff = (unsigned int)c * 4u;
-    xoff = fx.offset(c);
-    gid = a.chain_offset + (unsigned long long)c;
-    w = fw.load(0, coff);
-    e = fe.load(0, coff);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int d = 0; d < D; ++d) {
-      x[d] = fx.load(d, xoff);
-      if ((d & 7) == 7) __builtin_amdgcn_sched_barrier(0);
-    }
-  };
   // A's fragment image (24 KiB, prepared once per engine by k_dense64_bf16_fragments) is requested first and the first
   // tile's state right behind it: the image lands, goes to LDS and the block passes its barrier while the state rows
   // are still arriving
@@ -216,8 +187,8 @@ __global__ void __launch_bounds__(THREADS, 2) k_step_dense64_bf16x3(StepArgs<flo
 #pragma unroll
   for (int k = 0; k < PER_THREAD; ++k) image[k] = reinterpret_cast<const u32x4 *>(afrag)[k * THREADS + threadIdx.x];
   __builtin_amdgcn_sched_barrier(0);
-  load_tile();   // unconditional (a wave past the end shadows the last chain): a branch here would make the
-                 // s_waitcnt in front of the LDS writes below wait for the tile as well
+  tile.load(a, base);   // unconditional (a wave past the end shadows the last chain): a branch here would make the
+                        // s_waitcnt in front of the LDS writes below wait for the tile as well
 #pragma unroll
   for (int k = 0; k < PER_THREAD; ++k) reinterpret_cast<u32x4 *>(lds_a)[k * THREADS + threadIdx.x] = image[k];
   __syncthreads();
@@ -225,76 +196,43 @@ __global__ void __launch_bounds__(THREADS, 2) k_step_dense64_bf16x3(StepArgs<flo
   while (have) {
     for (int s = 0; s < a.n_sweeps; ++s) {
       const unsigned long long step = a.step_index + (unsigned long long)s;
-      U4 ctr;
-      ctr.x = (uint32_t)gid;
-      ctr.y = (uint32_t)(gid >> 32);
-      ctr.z = (uint32_t)step;
-      const uint32_t step_hi = (uint32_t)(step >> 32) << 16;
       if constexpr (CK == CK_SHARED) {
 #pragma unroll
         for (int b = 0; b < 16; ++b) {
-          ctr.w = step_hi | (uint32_t)b;
-          const U4 r = philox4x32_10(ctr, a.seed_lo, a.seed_hi);
           float g[4];
-          N_::normal_pair(r.x, r.y, g[0], g[1]);
-          N_::normal_pair(r.z, r.w, g[2], g[3]);
+          dense64_normals(a, tile.gid, step, b, g);
 #pragma unroll
-          for (int i = 0; i < 4; ++i) lds_xp[(4 * b + i) * THREADS] = g[i];
+          for (int i = 0; i < 4; ++i) tile.xp(4 * b + i) = g[i];
         }
         // x' = x + w L g; every lane has read all of g before the first row comes out.  The clobber keeps the
         // (loop-invariant) fragment loads of L inside the sweep: hoisted, they would pin 96 registers.
         asm volatile("" ::: "memory");
-        wave_matmul_64_bf16x3(lfrag, lfrag, [&](int k) { return lds_xp[k * THREADS]; },
-                              [&](int row, float v) { lds_xp[row * THREADS] = x[row] + w * v; }, lane);
+        wave_matmul_64_bf16x3(lfrag, lfrag, [&](int k) { return tile.xp(k); },
+                              [&](int row, float v) { tile.xp(row) = tile.x[row] + tile.w * v; }, lane);
       } else {
 #pragma unroll
         for (int b = 0; b < 16; ++b) {
-          ctr.w = step_hi | (uint32_t)b;
-          const U4 r = philox4x32_10(ctr, a.seed_lo, a.seed_hi);
           float g[4];
-          N_::normal_pair(r.x, r.y, g[0], g[1]);
-          N_::normal_pair(r.z, r.w, g[2], g[3]);
+          dense64_normals(a, tile.gid, step, b, g);
 #pragma unroll
-          for (int i = 0; i < 4; ++i) lds_xp[(4 * b + i) * THREADS] = x[4 * b + i] + w * g[i];
+          for (int i = 0; i < 4; ++i) tile.xp(4 * b + i) = tile.x[4 * b + i] + tile.w * g[i];
         }
       }
       float e_new = 0.0f;                                   // E = x'^T (A x')
-      wave_matmul_64_bf16x3(lds_a, a_piece3, [&](int k) { return lds_xp[k * THREADS]; },
-                            [&](int row, float v) { e_new += lds_xp[row * THREADS] * v; }, lane);
-      ctr.w = step_hi | 16u;                                // word 64 = block 16, output 0
-      const float u = N_::unit(philox4x32_10(ctr, a.seed_lo, a.seed_hi).x);
-      bool rejected = false;
-      if (a.reject_kind == ME_REJECT_ABS_REAL0_GE) rejected = !(N_::abs_(lds_xp[0]) < a.reject_bound);
-      const float diff = e_new - e;
-      bool accept = diff <= 0.0f;
-      if (a.temp > 0.0f) accept = accept || N_::uphill(u, diff, a.inv_temp, a.inv_temp_log2e);
-      accept = accept && !rejected;
-      bad_energy |= (live && !rejected && !N_::finite(e_new));
-      if (accept) {
-#pragma unroll
-        for (int d = 0; d < D; ++d) x[d] = lds_xp[d * THREADS];
-      }
-      e = accept ? e_new : e;
-      w = N_::adapt(w, accept, a.ratio, a.p, a.damping, a.up, a.down);
-      wave_accepted += (unsigned int)__popcll(__ballot(accept && live));
+      wave_matmul_64_bf16x3(lds_a, a_piece3, [&](int k) { return tile.xp(k); },
+                            [&](int row, float v) { e_new += tile.xp(row) * v; }, lane);
+      const float u = dense64_accept_uniform(a, tile.gid, step);
+      const bool accept = dense64_decide(a, a.reject_kind == ME_REJECT_ABS_REAL0_GE, tile.xp(0), tile.e, e_new, u, tile.live, tile.w,
+                                         bad_energy, [&](bool take) { tile.commit(take); });
+      wave_accepted += (unsigned int)__popcll(__ballot(accept && tile.live));
     }
-    bad_width |= live && !(w > 0.0f);
-    if (live) {
-#pragma unroll
-      for (int d = 0; d < D; ++d) fx.store(d, xoff, x[d]);
-      fe.store(0, coff, e);
-      fw.store(0, coff, w);
-    }
+    bad_width |= tile.live && !(tile.w > 0.0f);
+    tile.store();
     base += stride;
     have = base < a.n;
-    if (have) load_tile();
+    if (have) tile.load(a, base);
   }
-  if (lane == 0 && wave_accepted) {
-    unsigned long long *slot = a.accept_slots + (size_t)blockIdx.x * (THREADS / 64) + (threadIdx.x >> 6);
-    *slot += (unsigned long long)wave_accepted;
-  }
-  const unsigned int bits = (bad_energy ? ST_NONFINITE_ENERGY : 0u) | (bad_width ? ST_BAD_WIDTH : 0u);
-  if (bits) atomicOr(a.status, bits);
+  publish_step(a, THREADS / 64, wave_accepted, bad_energy, bad_width);
 }
 
 // METROPOLIS_DENSE64_FP32_MFMA=1 selects the fp32 MFMA kernel instead (read once per process).
@@ -310,30 +248,15 @@ inline bool dense64_exact_fp32_mfma() {
 template <int CK, int THREADS>
 inline hipError_t launch_step_dense64_bf16x3_threads(const StepArgs<float> &a, const unsigned int *afrag,
                                                      const unsigned int *lfrag, int grid_blocks, hipStream_t stream) {
-  // per DEVICE of the process, not per process (me_per_device.h): the raised dynamic-LDS limit and the CU count
-  static PerDevice<hipError_t> attr_cache;
-  static PerDevice<int> cu_cache;
-  int device = 0;
-  hipError_t rc = hipGetDevice(&device);
-  if (rc != hipSuccess) return rc;
-  rc = attr_cache.get(device, [] {
-    return hipFuncSetAttribute((const void *)k_step_dense64_bf16x3<CK, THREADS>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)dense64_bf16_lds_bytes<CK, THREADS>());
-  });
-  if (rc != hipSuccess) return rc;
+  constexpr size_t lds = dense64_bf16_lds_bytes<CK, THREADS>();
+  if (hipError_t rc = raise_lds_limit<k_step_dense64_bf16x3<CK, THREADS>>(lds); rc != hipSuccess) return rc;
   // Persistent workgroups, four wavefront-slots' worth per SIMD pair (two 512-thread or four 256-thread groups per CU),
   // each striding over its tiles with the next tile's loads issued before the current one retires: beats one group per
   // tile by 12 % at one sweep per launch (start-up: image copy + barrier with nothing else resident) and ties when
   // sweeps are fused.  tools/dev/time_dense64_grid.py
-  const int cus = cu_cache.get(device, [device] {
-    int count = 0;
-    if (hipDeviceGetAttribute(&count, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || count <= 0) return 256;
-    return count;
-  });
   long long blocks = (a.n + THREADS - 1) / THREADS;
-  const long long cap = grid_blocks > 0 ? grid_blocks : (long long)cus * (1024 / THREADS);
+  const long long cap = grid_blocks > 0 ? grid_blocks : (long long)cu_count() * (1024 / THREADS);
   if (blocks > cap) blocks = cap;
-  constexpr size_t lds = dense64_bf16_lds_bytes<CK, THREADS>();
   hipLaunchKernelGGL((k_step_dense64_bf16x3<CK, THREADS>), dim3((unsigned)blocks), dim3(THREADS), lds, stream, a, afrag,
                      lfrag);
   return hipGetLastError();

@@ -43,11 +43,13 @@
 // the wavefronts of a workgroup start together or staggered; with any cache policy of the stores; from HBM or from a
 // 32 KiB region that never leaves the L2.  The SQ counters show the difference as issue stalls (SQ_WAIT_INST_ANY), not as
 // waits on memory; the shader clock stays at 2.33-2.40 GHz (1 360 W with the traffic, 1 000 W without).  The memory traffic
-// of the kernel on its own (-DME_DENSE64_F64_MEMORY_ONLY) takes 72 us.
+// of the kernel on its own takes 72 us.
+// (The variants those figures compare -- the prefetch forms, store policies, staggered starts, the memory-only kernel -- were
+// compile-time switches of this file up to commit 7b7fcf1, where they can still be built.)
 #pragma once
 
-#include "me_device.h"
-#include "me_per_device.h"
+#include "me_dense64.h"
+#include "me_launch.h"
 
 #include <type_traits>
 
@@ -55,25 +57,13 @@ namespace me {
 
 using f64x4 = __attribute__((ext_vector_type(4))) double;
 
-#ifndef ME_DENSE64_F64_PREFETCH
-#define ME_DENSE64_F64_PREFETCH 2       // the next tile's rows: 0 = loaded when this tile is done, 1 = into a second register set, 2 = into LDS by the load unit
-#endif
-#ifndef ME_DENSE64_F64_STORE_AUX
-#define ME_DENSE64_F64_STORE_AUX 0      // cache policy of the state stores: bit 0 = sc0, bit 1 = nt, bit 4 = sc1
-#endif
-#ifndef ME_DENSE64_F64_STAGGER
-#define ME_DENSE64_F64_STAGGER 0        // dev: wavefront w of a workgroup starts w x this many x 64 cycles late
-#endif
-#ifndef ME_DENSE64_F64_EXPERIMENT
-#define ME_DENSE64_F64_EXPERIMENT 0     // dev: bit 0 = no state stores, bit 1 = no state loads, bit 3 = every tile uses the first 32 KiB of the state
-#endif
 using f64x2 = __attribute__((ext_vector_type(2))) double;
 using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
 constexpr int kDense64F64Threads = 512;                  // 8 waves, two per SIMD
 constexpr int kDense64F64Frags = 40;                     // (mb, ks) pairs with 4 ks < 16 (mb + 1)
 constexpr int kDense64F64ImageDoubles = kDense64F64Frags * 64;
 // per wavefront: the 2 x 4 x 16 energy exchange, 2 x 16 wall values, and the slab the next tile's rows are prefetched into
-constexpr int kDense64F64WaveDoubles = 160 + (ME_DENSE64_F64_PREFETCH == 2 ? 64 * 32 : 0);
+constexpr int kDense64F64WaveDoubles = 160 + 64 * 32;
 constexpr size_t kDense64F64LdsBytes = sizeof(double) * (kDense64F64ImageDoubles + 8 * kDense64F64WaveDoubles);
 
 __host__ __device__ constexpr int dense64_f64_frag_index(int mb, int ks) { return 2 * mb * (mb + 1) + ks; }
@@ -201,7 +191,7 @@ __global__ void __launch_bounds__(kDense64F64Threads, 2)
   double *mine = smem64 + kDense64F64ImageDoubles + wave * kDense64F64WaveDoubles;
   double *exch = mine;                       // [chain block][h][j]: the four partial energies of a chain
   double *wall = mine + 128;                 // [chain block][j]: row 0 of the proposals, for the hard wall
-  [[maybe_unused]] double *slab = mine + 160;   // [slot][lane][chain block]: the next tile's rows
+  double *slab = mine + 160;                  // [slot][lane][chain block]: the next tile's rows
   const int j = lane & 15, h = lane >> 4;
   const int own = h >> 1;                    // the chain block whose accept decision, energy and width this lane carries
   unsigned int wave_accepted = 0;
@@ -215,16 +205,13 @@ __global__ void __launch_bounds__(kDense64F64Threads, 2)
   const long long tile_stride = (long long)gridDim.x * (kDense64F64Threads / 64);
   // byte offset of (row h, chain 2 j) of 32-chain tile t: t >> 1 is the 64-chain tile of the layout, t & 1 its half
   auto state_off = [&](long long t) {
-    if constexpr ((ME_DENSE64_F64_EXPERIMENT & 8) != 0) t &= 1;      // dev: every tile reads and writes the first 32 KiB
     return (unsigned int)(((t >> 1) * (long long)(D * 64) + (t & 1) * 32 + 2 * j) * 8) + (unsigned int)h * TiledField<double>::kEntryBytes;
   };
   auto load_rows = [&](long long t, f64x2 (&dst)[S]) {
     const unsigned int off = state_off(t);
 #pragma unroll
-    for (int ks = 0; ks < S; ++ks) {
-      if constexpr ((ME_DENSE64_F64_EXPERIMENT & 2) != 0) dst[ks] = f64x2{(double)off, 0.0};
-      else dst[ks] = __builtin_bit_cast(f64x2, __builtin_amdgcn_raw_buffer_load_b128(fx.rsrc, off, (unsigned int)ks * kSlotBytes, 0));
-    }
+    for (int ks = 0; ks < S; ++ks)
+      dst[ks] = __builtin_bit_cast(f64x2, __builtin_amdgcn_raw_buffer_load_b128(fx.rsrc, off, (unsigned int)ks * kSlotBytes, 0));
   };
 
   long long tile = (long long)blockIdx.x * (kDense64F64Threads / 64) + wave;
@@ -249,11 +236,6 @@ __global__ void __launch_bounds__(kDense64F64Threads, 2)
   }
   N_::prepare();    // the log table of the float64 Box-Muller; ends with the block barrier that also covers lds_t
   __builtin_amdgcn_s_waitcnt(0x0F70);        // enter the loop with nothing pending
-#if ME_DENSE64_F64_STAGGER > 0
-  // every wavefront of the workgroup starts a little later than the one before it
-#pragma unroll 1
-  for (int k = 0; k < wave; ++k) __builtin_amdgcn_s_sleep(ME_DENSE64_F64_STAGGER);
-#endif
   while (tile < n_tiles) {
     const long long c_own = tile * kTileChains64 + 2 * j + own;
     const bool live = c_own < a.n;
@@ -262,24 +244,17 @@ __global__ void __launch_bounds__(kDense64F64Threads, 2)
     const long long next = tile + tile_stride;
     const bool have_next = next < n_tiles;        // wave-uniform
     double en = 0.0, wn = 0.0;
-#if ME_DENSE64_F64_PREFETCH == 1
-    f64x2 xn[S];
-#endif
     // the next tile's rows travel while this one computes
     auto prefetch = [&]() {
       if (have_next) {
         const unsigned int ncoff = (unsigned int)(next * kTileChains64 + 2 * j + own) * 8u;
         en = fe.load(0, ncoff);
         wn = fw.load(0, ncoff);
-#if ME_DENSE64_F64_PREFETCH == 1
-        load_rows(next, xn);
-#elif ME_DENSE64_F64_PREFETCH == 2
         const unsigned int off = state_off(next);
 #pragma unroll
         for (int ks = 0; ks < S; ++ks)     // 64 lanes x 16 bytes land at slab[ks][lane]
           __builtin_amdgcn_raw_ptr_buffer_load_lds(fx.rsrc, (__attribute__((address_space(3))) void *)(slab + ks * 128), 16, off,
                                                    (unsigned int)ks * kSlotBytes, 0, 0);
-#endif
       }
     };
     if constexpr (CK != CK_SHARED) prefetch();
@@ -296,16 +271,8 @@ __global__ void __launch_bounds__(kDense64F64Threads, 2)
       for (int q = 0; q < 4; ++q) {
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb) {
-          const unsigned long long gid = gid0 + (unsigned long long)nb;
-          U4 ctr;
-          ctr.x = (uint32_t)gid;
-          ctr.y = (uint32_t)(gid >> 32);
-          ctr.z = (uint32_t)step;
-          ctr.w = ((uint32_t)(step >> 32) << 16) | (uint32_t)(4 * q + h);
-          const U4 o = philox4x32_10(ctr, a.seed_lo, a.seed_hi);
           double g[4];
-          N_::normal_pair(o.x, o.y, g[0], g[1]);
-          N_::normal_pair(o.z, o.w, g[2], g[3]);
+          dense64_normals(a, gid0 + (unsigned long long)nb, step, 4 * q + h, g);
           transpose_rows_4x4(g);
 #pragma unroll
           for (int k = 0; k < 4; ++k) xp[4 * q + k][nb] = g[k];
@@ -350,16 +317,12 @@ __global__ void __launch_bounds__(kDense64F64Threads, 2)
       double e_new = 0.0;      // the four lanes of a chain block sum the same four values in the same order
 #pragma unroll
       for (int hh = 0; hh < 4; ++hh) e_new += exch[(own * 4 + hh) * 16 + j];
+      // The lines of dense64_decide (me_dense64.h) spelled out around the ballot commit: through the shared function, in any
+      // of three forms, the identity shape's fused sweep ran 0.5-1.4 us (0.5-1.5 %) slower than with these lines in place, which
+      // compile to the code the kernel had before (profiles/dense64_shared_skeleton.txt)
       bool rejected = false;
       if (walled) rejected = !(N_::abs_(wall[own * 16 + j]) < a.reject_bound);
-      // ---- accept uniform: word 64 = block 16, output 0
-      const unsigned long long gid = gid0 + (unsigned long long)own;
-      U4 ctr;
-      ctr.x = (uint32_t)gid;
-      ctr.y = (uint32_t)(gid >> 32);
-      ctr.z = (uint32_t)step;
-      ctr.w = ((uint32_t)(step >> 32) << 16) | 16u;
-      const double u = N_::unit(philox4x32_10(ctr, a.seed_lo, a.seed_hi).x);
+      const double u = dense64_accept_uniform(a, gid0 + (unsigned long long)own, step);
       const double diff = e_new - e;
       bool accept = diff <= 0.0;
       if (a.temp > 0.0) accept = accept || N_::uphill(u, diff, a.inv_temp, a.inv_temp_log2e);
@@ -378,10 +341,8 @@ __global__ void __launch_bounds__(kDense64F64Threads, 2)
       wave_accepted += (unsigned int)__popcll(__ballot(accept && live && (h & 1) == 0));
       __builtin_amdgcn_wave_barrier();      // the next sweep overwrites the exchange
     };
-#ifndef ME_DENSE64_F64_MEMORY_ONLY     // (defined: the kernel's memory traffic without its arithmetic)
     sweep(std::true_type{}, 0);
     for (int s = 1; s < a.n_sweeps; ++s) sweep(std::false_type{}, s);
-#endif
     bad_width |= live && !(w > 0.0);
     // The prefetch was issued a tile of arithmetic ago: wait for it BEFORE this tile's stores are queued behind it (vmcnt
     // counts in order; afterwards any wait on the prefetch would drain the stores as well).
@@ -392,61 +353,32 @@ __global__ void __launch_bounds__(kDense64F64Threads, 2)
       const unsigned int off = state_off(tile);
 #pragma unroll
       for (int ks = 0; ks < S; ++ks)
-        if ((ME_DENSE64_F64_EXPERIMENT & 1) == 0 || x[ks][0] == 1.2345)
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, x[ks]), fx.rsrc, off, (unsigned int)ks * kSlotBytes, ME_DENSE64_F64_STORE_AUX);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, x[ks]), fx.rsrc, off, (unsigned int)ks * kSlotBytes, 0);
       if (live && (h & 1) == 0) {
         fe.store(0, coff, e);
         fw.store(0, coff, w);
       }
     }
     if (have_next) {
-#if ME_DENSE64_F64_PREFETCH == 1
-#pragma unroll
-      for (int ks = 0; ks < S; ++ks) x[ks] = xn[ks];
-#elif ME_DENSE64_F64_PREFETCH == 2
 #pragma unroll
       for (int ks = 0; ks < S; ++ks) x[ks] = *reinterpret_cast<const f64x2 *>(slab + ks * 128 + lane * 2);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");    // the slab has been read: free for the next prefetch
-#else
-      load_rows(next, x);
-      __builtin_amdgcn_s_waitcnt(0x0F70);
-#endif
     }
     e = en;
     w = wn;
     tile = next;
   }
-  if (lane == 0 && wave_accepted) {
-    unsigned long long *slot = a.accept_slots + (size_t)blockIdx.x * (kDense64F64Threads / 64) + wave;
-    *slot += (unsigned long long)wave_accepted;
-  }
-  const unsigned int bits = (bad_energy ? ST_NONFINITE_ENERGY : 0u) | (bad_width ? ST_BAD_WIDTH : 0u);
-  if (bits) atomicOr(a.status, bits);
+  publish_step(a, kDense64F64Threads / 64, wave_accepted, bad_energy, bad_width);
 }
 
-// Host launcher: one persistent 512-thread workgroup per CU (8 wavefronts, two per SIMD; LDS admits no more).  Both
-// per-device properties -- the raised dynamic-LDS limit and the CU count -- are resolved per device of the process.
+// Host launcher: one persistent 512-thread workgroup per CU (8 wavefronts, two per SIMD; LDS admits no more).
 template <int CK>
 inline hipError_t launch_step_dense64_f64(const StepArgs<double> &a, const double *t_image, const double *l_image,
                                           int grid_blocks, hipStream_t stream) {
-  static PerDevice<hipError_t> attr_cache;
-  static PerDevice<int> cu_cache;
-  int device = 0;
-  hipError_t rc = hipGetDevice(&device);
-  if (rc != hipSuccess) return rc;
-  rc = attr_cache.get(device, [] {
-    return hipFuncSetAttribute((const void *)k_step_dense64_f64<CK>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)kDense64F64LdsBytes);
-  });
-  if (rc != hipSuccess) return rc;
-  const int cus = cu_cache.get(device, [device] {
-    int count = 0;
-    if (hipDeviceGetAttribute(&count, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || count <= 0) return 256;
-    return count;
-  });
+  if (hipError_t rc = raise_lds_limit<k_step_dense64_f64<CK>>(kDense64F64LdsBytes); rc != hipSuccess) return rc;
   constexpr int chains_per_block = kTileChains64 * (kDense64F64Threads / 64);
   long long blocks = (a.n + chains_per_block - 1) / chains_per_block;
-  const long long cap = grid_blocks > 0 ? grid_blocks : (long long)cus;
+  const long long cap = grid_blocks > 0 ? grid_blocks : (long long)cu_count();
   if (blocks > cap) blocks = cap;
   hipLaunchKernelGGL((k_step_dense64_f64<CK>), dim3((unsigned)blocks), dim3(kDense64F64Threads), kDense64F64LdsBytes, stream,
                      a, t_image, l_image);

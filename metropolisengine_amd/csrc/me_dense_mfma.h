@@ -20,8 +20,8 @@
 //     accumulator register pair brings both halves home, then E = sum_p x'_p y_p is 64 FMAs per lane.
 #pragma once
 
-#include "me_device.h"
-#include "me_per_device.h"
+#include "me_dense64.h"
+#include "me_launch.h"
 
 namespace me {
 
@@ -143,7 +143,7 @@ __global__ void __launch_bounds__(kDenseBlockThreads, 2) k_step_dense64_mfma(Ste
   extern __shared__ __attribute__((aligned(16))) float smem[];
   float *lds_a = smem;
   float *lds_l = smem + 4096;
-  float *lds_xp = smem + 4096 * (CK == CK_SHARED ? 2 : 1) + threadIdx.x;   // this lane's column, stride 512
+  Dense64Tile<kDenseBlockThreads> tile(a, smem + 4096 * (CK == CK_SHARED ? 2 : 1));
   stage_a_fragments(lds_a, amat);
   if constexpr (CK == CK_SHARED) stage_a_fragments(lds_l, lfull);
   __syncthreads();
@@ -152,21 +152,8 @@ __global__ void __launch_bounds__(kDenseBlockThreads, 2) k_step_dense64_mfma(Ste
   unsigned int wave_accepted = 0;
   bool bad_energy = false, bad_width = false;
   const long long stride = (long long)gridDim.x * kDenseBlockThreads;
-  const XField<float, D> fx(a.x, a.n);
-  const Field<float> fe(a.energy, a.n, 1), fw(a.width, a.n, 1);
-  // every lane stays active (MFMA and permlane need the whole wavefront): tail lanes shadow the last chain
   for (long long base = (long long)blockIdx.x * kDenseBlockThreads + (threadIdx.x & ~63); base < a.n; base += stride) {
-    const long long c_raw = base + lane;
-    const bool live = c_raw < a.n;
-    const long long c = live ? c_raw : a.n - 1;
-    const unsigned int coff = (unsigned int)c * 4u, xoff = fx.offset(c);
-    float x[D];
-#pragma unroll
-    for (int d = 0; d < D; ++d) x[d] = fx.load(d, xoff);
-    float e = fe.load(0, coff);
-    float w = fw.load(0, coff);
-    const unsigned long long gid = a.chain_offset + (unsigned long long)c;
-
+    tile.load(a, base);
     for (int s = 0; s < a.n_sweeps; ++s) {
       const unsigned long long step = a.step_index + (unsigned long long)s;
       // Philox block b yields the normals of parameters 4b..4b+3 (k pairs 2b and 2b+1 of the first product);
@@ -175,10 +162,7 @@ __global__ void __launch_bounds__(kDenseBlockThreads, 2) k_step_dense64_mfma(Ste
       uint32_t pk0 = 0, pk1 = 0;
       auto draw_slice = [&](int b, int t, float (&g)[4]) {
         if (t == 0) {
-          pc.x = (uint32_t)gid;
-          pc.y = (uint32_t)(gid >> 32);
-          pc.z = (uint32_t)step;
-          pc.w = ((uint32_t)(step >> 32) << 16) | (uint32_t)b;
+          pc = philox_counter(tile.gid, step, b);
           pk0 = a.seed_lo;
           pk1 = a.seed_hi;
         }
@@ -190,9 +174,9 @@ __global__ void __launch_bounds__(kDenseBlockThreads, 2) k_step_dense64_mfma(Ste
       if constexpr (CK == CK_SHARED) {
         wave_matmul_64(lds_l, draw_slice, y, lane, true);      // y = L g, normals drawn on the fly
 #pragma unroll
-        for (int d = 0; d < D; ++d) lds_xp[d * kDenseBlockThreads] = x[d] + w * y[d];
+        for (int d = 0; d < D; ++d) tile.xp(d) = tile.x[d] + tile.w * y[d];
         wave_matmul_64(lds_a, [&](int b, int t, float (&v)[4]) {
-          if (t < 4) v[t] = lds_xp[(4 * b + t) * kDenseBlockThreads];
+          if (t < 4) v[t] = tile.xp(4 * b + t);
         }, y, lane, false);
       } else {
         // identity shape: x' = x + w g is formed block by block and fed straight into y = A x'
@@ -201,68 +185,42 @@ __global__ void __launch_bounds__(kDenseBlockThreads, 2) k_step_dense64_mfma(Ste
           if (t == 7) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-              v[i] = x[4 * b + i] + w * v[i];
-              lds_xp[(4 * b + i) * kDenseBlockThreads] = v[i];
+              v[i] = tile.x[4 * b + i] + tile.w * v[i];
+              tile.xp(4 * b + i) = v[i];
             }
           }
         }, y, lane, false);
       }
-      float u;
-      {
-        U4 ctr;
-        ctr.x = (uint32_t)gid;
-        ctr.y = (uint32_t)(gid >> 32);
-        ctr.z = (uint32_t)step;
-        ctr.w = ((uint32_t)(step >> 32) << 16) | 16u;     // word 64 = block 16, output 0
-        u = N_::unit(philox4x32_10(ctr, a.seed_lo, a.seed_hi).x);
-      }
-      float e_new = 0.0f;
+      const float u = dense64_accept_uniform(a, tile.gid, step);
+      float e_new = 0.0f;      // fma_ holds the sum to 64 fused multiply-adds in this order, whatever the code around it
 #pragma unroll
-      for (int d = 0; d < D; ++d) e_new += lds_xp[d * kDenseBlockThreads] * y[d];
+      for (int d = 0; d < D; ++d) e_new = fma_(tile.xp(d), y[d], e_new);
+      // dense64_decide (me_dense64.h) spelled out, the one piece this kernel keeps to itself: through the shared function
+      // it compiles to 194 registers instead of 251 and its fused sweeps run 1.3-2 % slower, measured twice
+      // (profiles/dense64_shared_skeleton.txt)
       bool rejected = false;
-      if (a.reject_kind == ME_REJECT_ABS_REAL0_GE) rejected = !(N_::abs_(lds_xp[0]) < a.reject_bound);
-      const float diff = e_new - e;
+      if (a.reject_kind == ME_REJECT_ABS_REAL0_GE) rejected = !(N_::abs_(tile.xp(0)) < a.reject_bound);
+      const float diff = e_new - tile.e;
       bool accept = diff <= 0.0f;
       if (a.temp > 0.0f) accept = accept || N_::uphill(u, diff, a.inv_temp, a.inv_temp_log2e);
       accept = accept && !rejected;
-      bad_energy |= (live && !rejected && !N_::finite(e_new));
-      if (accept) {
-#pragma unroll
-        for (int d = 0; d < D; ++d) x[d] = lds_xp[d * kDenseBlockThreads];
-      }
-      e = accept ? e_new : e;
-      w = N_::adapt(w, accept, a.ratio, a.p, a.damping, a.up, a.down);
-      wave_accepted += (unsigned int)__popcll(__ballot(accept && live));
+      bad_energy |= (tile.live && !rejected && !N_::finite(e_new));
+      tile.commit(accept);
+      tile.e = accept ? e_new : tile.e;
+      tile.w = N_::adapt(tile.w, accept, a.ratio, a.p, a.damping, a.up, a.down);
+      wave_accepted += (unsigned int)__popcll(__ballot(accept && tile.live));
     }
-    bad_width |= live && !(w > 0.0f);
-    if (live) {
-#pragma unroll
-      for (int d = 0; d < D; ++d) fx.store(d, xoff, x[d]);
-      fe.store(0, coff, e);
-      fw.store(0, coff, w);
-    }
+    bad_width |= tile.live && !(tile.w > 0.0f);
+    tile.store();
   }
-  if (lane == 0 && wave_accepted) {
-    unsigned long long *slot = a.accept_slots + (size_t)blockIdx.x * (kDenseBlockThreads / 64) + (threadIdx.x >> 6);
-    *slot += (unsigned long long)wave_accepted;
-  }
-  const unsigned int bits = (bad_energy ? ST_NONFINITE_ENERGY : 0u) | (bad_width ? ST_BAD_WIDTH : 0u);
-  if (bits) atomicOr(a.status, bits);
+  publish_step(a, kDenseBlockThreads / 64, wave_accepted, bad_energy, bad_width);
 }
 
 // Host launcher: 512-thread blocks, dynamic LDS above 64 KiB needs the function attribute once.
 template <int CK>
 inline hipError_t launch_step_dense64_mfma(const StepArgs<float> &a, const float *amat, const float *lfull, int grid_blocks,
                                            hipStream_t stream) {
-  static PerDevice<hipError_t> attr_cache;      // per device of the process (me_per_device.h)
-  int device = 0;
-  hipError_t rc = hipGetDevice(&device);
-  if (rc != hipSuccess) return rc;
-  rc = attr_cache.get(device, [] {
-    return hipFuncSetAttribute((const void *)k_step_dense64_mfma<CK>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)dense64_lds_bytes<CK>());
-  });
-  if (rc != hipSuccess) return rc;
+  if (hipError_t rc = raise_lds_limit<k_step_dense64_mfma<CK>>(dense64_lds_bytes<CK>()); rc != hipSuccess) return rc;
   long long blocks = (a.n + kDenseBlockThreads - 1) / kDenseBlockThreads;
   if (grid_blocks > 0 && blocks > grid_blocks) blocks = grid_blocks;
   hipLaunchKernelGGL(k_step_dense64_mfma<CK>, dim3((unsigned)blocks), dim3(kDenseBlockThreads), dense64_lds_bytes<CK>(),

@@ -48,13 +48,16 @@ __device__ __forceinline__ U4 philox4x32_10(U4 c, uint32_t k0, uint32_t k1) {
   return c;
 }
 // Block b of chain gid's stream at one step (the counter layout of oracle/philox.py): outputs 4 b .. 4 b + 3 of the step's words
-__device__ __forceinline__ U4 philox_block(unsigned long long gid, unsigned long long step, int b, uint32_t seed_lo, uint32_t seed_hi) {
+__device__ __forceinline__ U4 philox_counter(unsigned long long gid, unsigned long long step, int b) {
   U4 ctr;
   ctr.x = (uint32_t)gid;
   ctr.y = (uint32_t)(gid >> 32);
   ctr.z = (uint32_t)step;
   ctr.w = ((uint32_t)(step >> 32) << 16) | (uint32_t)b;
-  return philox4x32_10(ctr, seed_lo, seed_hi);
+  return ctr;
+}
+__device__ __forceinline__ U4 philox_block(unsigned long long gid, unsigned long long step, int b, uint32_t seed_lo, uint32_t seed_hi) {
+  return philox4x32_10(philox_counter(gid, step, b), seed_lo, seed_hi);
 }
 
 // ------------------------------------------------------------------------------------------------ numerics

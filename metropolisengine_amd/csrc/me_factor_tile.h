@@ -40,7 +40,7 @@
 // pivot, sqrt_and_inverse 10 ms; XCD-aware order: -15 % where a run is half a sector (32 bytes).
 #pragma once
 #include "me_device.h"
-#include "me_per_device.h"
+#include "me_launch.h"
 
 namespace me {
 
@@ -312,20 +312,9 @@ k_factor_tile(const R *cov, R *factor, unsigned int *status, long long n) {
 template <typename R, int NR, bool NT>
 inline hipError_t launch_factor_tile(const R *cov, R *factor, unsigned int *status, long long n, hipStream_t stream) {
   using T = FactorTile<R, NR>;
-  static PerDevice<int> blocks_per_device;
-  int device = 0;
-  hipError_t err = hipGetDevice(&device);
-  if (err != hipSuccess) return err;
-  const int resident = blocks_per_device.get(device, [&]() -> int {
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(&k_factor_tile<R, NR, NT>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)T::kLdsBytes) != hipSuccess)
-      return -1;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return -1;
-    const int per_cu = (int)(160 * 1024 / T::kLdsBytes) > 0 ? (int)(160 * 1024 / T::kLdsBytes) : 1;
-    return (prop.multiProcessorCount * per_cu + 7) / 8 * 8;
-  });
-  if (resident <= 0) return hipErrorInvalidValue;
+  if (hipError_t err = raise_lds_limit<k_factor_tile<R, NR, NT>>(T::kLdsBytes); err != hipSuccess) return err;
+  constexpr int per_cu = (int)(160 * 1024 / T::kLdsBytes) > 0 ? (int)(160 * 1024 / T::kLdsBytes) : 1;
+  const int resident = (cu_count() * per_cu + 7) / 8 * 8;
   const long long units = ((n + 63) >> 6) * (64 / T::kChains);
   const long long cap = (long long)resident * 4;          // a few units per resident workgroup: tails stay short
   const long long padded = (units + 8 * (64 / T::kChains) - 1) / (8 * (64 / T::kChains)) * (8 * (64 / T::kChains));

@@ -1,6 +1,6 @@
 // Dimension-independent kernels: broadcast fill and the ensemble (pooled) moment reduction.
 #include "me_internal.h"
-#include "me_per_device.h"
+#include "me_launch.h"
 
 namespace me {
 namespace {
@@ -310,15 +310,8 @@ namespace {
 template <typename R, int TILE>
 hipError_t launch_pool_stage1(const void *x, long long n, int nr, int nc, int n_entries, int blocks, double *partials, hipStream_t stream, bool tiled) {
   const size_t lds = (size_t)(nr + 2 * nc + nr + nc) * (size_t)(TILE + 1) * sizeof(R);
-  if (lds > 64 * 1024) {
-    static PerDevice<hipError_t> attr;
-    int device = 0;
-    if (hipError_t rc = hipGetDevice(&device); rc != hipSuccess) return rc;
-    const hipError_t rc = attr.get(device, [] {
-      return hipFuncSetAttribute((const void *)k_pool_reduce<R, TILE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPoolLdsLimit);
-    });
-    if (rc != hipSuccess) return rc;
-  }
+  if (lds > 64 * 1024)
+    if (hipError_t rc = raise_lds_limit<k_pool_reduce<R, TILE>>(kPoolLdsLimit); rc != hipSuccess) return rc;
   for (int base = 0; base < n_entries; base += kMaxEntries * kBlockThreads)
     hipLaunchKernelGGL((k_pool_reduce<R, TILE>), dim3((unsigned)blocks), dim3(kBlockThreads), lds, stream, (const R *)x, n, nr, nc, base,
                        tiled ? 1 : 0, partials);

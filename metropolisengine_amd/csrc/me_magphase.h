@@ -105,12 +105,7 @@ __global__ void __launch_bounds__(kStepThreads) k_step_magphase(StepArgs<R> a, E
         uint32_t words[4 * NBLK];
 #pragma unroll
         for (int b = 0; b < NBLK; ++b) {
-          U4 ctr;
-          ctr.x = (uint32_t)gid;
-          ctr.y = (uint32_t)(gid >> 32);
-          ctr.z = (uint32_t)step;
-          ctr.w = ((uint32_t)(step >> 32) << 16) | (uint32_t)b;
-          const U4 o = philox4x32_10(ctr, a.seed_lo, a.seed_hi);
+          const U4 o = philox_block(gid, step, b, a.seed_lo, a.seed_hi);
           words[4 * b + 0] = o.x;
           words[4 * b + 1] = o.y;
           words[4 * b + 2] = o.z;

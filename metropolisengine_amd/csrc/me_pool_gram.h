@@ -12,7 +12,7 @@
 
 #include "me_dense_mfma.h"
 #include "me_dense_f64.h"
-#include "me_per_device.h"
+#include "me_launch.h"
 
 namespace me {
 
@@ -203,14 +203,7 @@ __global__ void __launch_bounds__(64 * kGramWaves) k_pool_gram64_f64(const doubl
 
 inline hipError_t launch_pool_gram64_f64(const void *x, long long n, double *partials, int n_rows, hipStream_t stream) {
   constexpr size_t lds = (size_t)kGramWaves * 64 * kGramPitchF64 * sizeof(double);      // 2 x 34 KB
-  static PerDevice<int> raised;
-  int device = 0;
-  hipError_t err = hipGetDevice(&device);
-  if (err != hipSuccess) return err;
-  if (raised.get(device, [&]() -> int {
-        return hipFuncSetAttribute((const void *)k_pool_gram64_f64<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess ? 1 : -1;
-      }) < 0)
-    return hipErrorInvalidValue;
+  if (hipError_t err = raise_lds_limit<k_pool_gram64_f64<0>>(lds); err != hipSuccess) return err;
   hipLaunchKernelGGL(k_pool_gram64_f64<0>, dim3((unsigned)((n_rows + kGramWaves - 1) / kGramWaves)), dim3(64 * kGramWaves), lds, stream,
                      (const double *)x, n, partials, n_rows);
   return hipGetLastError();
@@ -324,14 +317,7 @@ __global__ void __launch_bounds__(64 * kSmallWavesF32) k_pool_gram32(const float
 template <int NR, int NC>
 inline hipError_t launch_pool_gram32(const void *x, long long n, double *partials, int n_rows, hipStream_t stream) {
   constexpr size_t lds = (size_t)kSmallWavesF32 * kSmallSlabBytesF32;      // 138 KB: one workgroup per CU
-  static PerDevice<int> raised;
-  int device = 0;
-  hipError_t err = hipGetDevice(&device);
-  if (err != hipSuccess) return err;
-  if (raised.get(device, [&]() -> int {
-        return hipFuncSetAttribute((const void *)k_pool_gram32<NR, NC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess ? 1 : -1;
-      }) < 0)
-    return hipErrorInvalidValue;
+  if (hipError_t err = raise_lds_limit<k_pool_gram32<NR, NC>>(lds); err != hipSuccess) return err;
   hipLaunchKernelGGL((k_pool_gram32<NR, NC>), dim3((unsigned)n_rows), dim3(64 * kSmallWavesF32), lds, stream, (const float *)x, n, partials, n_rows);
   return hipGetLastError();
 }
@@ -436,14 +422,7 @@ __global__ void __launch_bounds__(64 * kSmallWavesF64) k_pool_gram32_f64(const d
 template <int NR, int NC>
 inline hipError_t launch_pool_gram32_f64(const void *x, long long n, double *partials, int n_rows, hipStream_t stream) {
   constexpr size_t lds = (size_t)kSmallWavesF64 * kSmallSlabBytesF64;      // 136 KB: one workgroup per CU
-  static PerDevice<int> raised;
-  int device = 0;
-  hipError_t err = hipGetDevice(&device);
-  if (err != hipSuccess) return err;
-  if (raised.get(device, [&]() -> int {
-        return hipFuncSetAttribute((const void *)k_pool_gram32_f64<NR, NC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess ? 1 : -1;
-      }) < 0)
-    return hipErrorInvalidValue;
+  if (hipError_t err = raise_lds_limit<k_pool_gram32_f64<NR, NC>>(lds); err != hipSuccess) return err;
   hipLaunchKernelGGL((k_pool_gram32_f64<NR, NC>), dim3((unsigned)n_rows), dim3(64 * kSmallWavesF64), lds, stream, (const double *)x, n, partials, n_rows);
   return hipGetLastError();
 }

@@ -36,7 +36,7 @@
 #include <type_traits>
 
 #include "me_device.h"
-#include "me_per_device.h"
+#include "me_launch.h"
 
 namespace me {
 namespace {
@@ -686,15 +686,9 @@ hipError_t step(const StepLaunch &l, hipStream_t stream) {
     long long blocks = (l.n + kStepThreads - 1) / kStepThreads;
     if (l.grid_blocks > 0 && blocks > l.grid_blocks) blocks = l.grid_blocks;
     const R *folded = l.energy_kind == ME_ENERGY_DENSE_QUAD ? (const R *)l.coef_device : nullptr;
-    int device = 0;
-    if (hipError_t rc = hipGetDevice(&device); rc != hipSuccess) return rc;
     auto launch = [&](auto ck) -> hipError_t {
       constexpr int CK = decltype(ck)::value;
-      static PerDevice<hipError_t> attr_cache;
-      const hipError_t rc = attr_cache.get(device, [] {
-        return hipFuncSetAttribute((const void *)k_step_runtime_lds<R, CK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRuntimeLdsLimit);
-      });
-      if (rc != hipSuccess) return rc;
+      if (hipError_t rc = raise_lds_limit<k_step_runtime_lds<R, CK>>(kRuntimeLdsLimit); rc != hipSuccess) return rc;
       hipLaunchKernelGGL((k_step_runtime_lds<R, CK>), dim3((unsigned)blocks), dim3(kStepThreads), lds, stream, a, p, folded);
       return hipGetLastError();
     };
@@ -718,13 +712,7 @@ hipError_t measure(const MeasureLaunch &l, hipStream_t stream) {
   // engines that keep per-chain covariance matrices: one wavefront per block, delta (and the factor kernel's row block) in LDS
   const size_t row_bytes = (size_t)(l.n_real + 2 * l.n_complex) * kStepThreads * sizeof(R);
   if (row_bytes > kRuntimeLdsLimit) return hipErrorNotSupported;
-  int device = 0;
-  if (hipError_t rc = hipGetDevice(&device); rc != hipSuccess) return rc;
-  static PerDevice<hipError_t> attr_measure;
-  hipError_t rc = attr_measure.get(device, [] {
-    return hipFuncSetAttribute((const void *)k_measure_runtime_cov<R>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRuntimeLdsLimit);
-  });
-  if (rc != hipSuccess) return rc;
+  if (hipError_t rc = raise_lds_limit<k_measure_runtime_cov<R>>(kRuntimeLdsLimit); rc != hipSuccess) return rc;
   const dim3 grid(grid_for(l.n, l.grid_blocks)), block(kStepThreads);
   hipLaunchKernelGGL(k_measure_runtime_cov<R>, grid, block, row_bytes, stream, a, l.n_real, l.n_complex);
   if (l.update_cov && l.write_factor) {
@@ -732,11 +720,7 @@ hipError_t measure(const MeasureLaunch &l, hipStream_t stream) {
     const size_t real_row_bytes = (size_t)l.n_real * kStepThreads * sizeof(R);
     auto launch = [&](auto rows_tag) -> hipError_t {
       constexpr int ROWS = decltype(rows_tag)::value;
-      static PerDevice<hipError_t> attr_factor;
-      const hipError_t err = attr_factor.get(device, [] {
-        return hipFuncSetAttribute((const void *)k_factor_runtime<R, ROWS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kRuntimeLdsLimit);
-      });
-      if (err != hipSuccess) return err;
+      if (hipError_t err = raise_lds_limit<k_factor_runtime<R, ROWS>>(kRuntimeLdsLimit); err != hipSuccess) return err;
       hipLaunchKernelGGL((k_factor_runtime<R, ROWS>), grid, block, ROWS * real_row_bytes, stream, (const R *)l.cov, (R *)l.factor, l.status,
                          l.n, l.n_real, p_total);
       return hipGetLastError();

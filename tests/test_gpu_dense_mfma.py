@@ -120,6 +120,31 @@ def test_mfma_matches_f64_kernel_statistics():
     assert np.all(np.abs(np.diag(a["covariance"]) - np.diag(b["covariance"])) < 8 * 0.5 * np.sqrt(2.0 / n))
 
 
+@pytest.mark.parametrize("n", [1, 63, 65, 130])
+def test_dense64_f32_ragged_tiles_are_shards_of_a_larger_engine(n):
+    """Chain counts that leave a wavefront's 64-chain tile almost empty or one lane short (1, 63) or start a second or third
+    wavefront whose tail lanes shadow the last chain (65, 130): every chain's column of the product is independent of its
+    neighbours, so the n chains are bit for bit the first n of a 192-chain engine, with the identity shape and with a shared
+    factor.  (The float32 twin of the test of the same name in test_gpu_dense_f64.py; it runs under both kernel selections.)"""
+    kw = dict(temp=1.0, seed=77, sampling_width=0.15)
+    x0 = list(np.linspace(-0.2, 0.4, 64))
+    factor = np.linalg.cholesky(0.5 * np.linalg.inv(AMAT))[np.tril_indices(64)]
+    for mode in ("fixed", "pooled"):
+        big = me.MetropolisEngine(me.DenseQuadratic(AMAT), None, x0, None, n_chains=192, cov_mode=mode, **kw)
+        small = me.MetropolisEngine(me.DenseQuadratic(AMAT), None, x0, None, n_chains=n, cov_mode=mode, **kw)
+        if mode == "pooled":
+            big.set_shared_factor(factor)
+            small.set_shared_factor(factor)
+        for fused in (1, 3, 1):
+            big.step_all(fused)
+            small.step_all(fused)
+        assert np.array_equal(big._get(0)[:n], small._get(0))
+        # (a one-chain engine reports scalars, as the reference does)
+        assert np.array_equal(big.energy_total[:n], np.atleast_1d(small.energy_total))
+        assert np.array_equal(big.real_group_sampling_width[:n], np.atleast_1d(small.real_group_sampling_width))
+        assert small.accept_stats()[1] == 5 * n
+
+
 def test_fp32_mfma_variant_in_child_process():
     """The kernel choice is read once per process: run the one-step and f64-statistics checks again under
     METROPOLIS_DENSE64_FP32_MFMA=1 (one child test process)."""
@@ -127,10 +152,10 @@ def test_fp32_mfma_variant_in_child_process():
         pytest.skip("already the fp32 MFMA variant")
     env = dict(os.environ, METROPOLIS_DENSE64_FP32_MFMA="1")
     res = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-x", "-m", "gpu", "-k",
-                          "one_step or f64_kernel or gram", "-p", "no:cacheprovider"], env=env, capture_output=True, text=True,
+                          "one_step or f64_kernel or gram or ragged_tiles", "-p", "no:cacheprovider"], env=env, capture_output=True, text=True,
                          timeout=600, cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-2000:]
-    assert "6 passed" in res.stdout
+    assert "10 passed" in res.stdout
 
 
 def test_pooled_moments_gram_kernel_matches_numpy():
