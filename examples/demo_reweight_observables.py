@@ -1,7 +1,8 @@
 """Observables of a temperature ladder on a fine temperature grid: the double well of demo_ladder_free_energy.py,
 E = 4 (x^2 - 1)^2, sampled by parallel tempering with |x| and x^2 of every chain recorded next to its energy.  MBAR
 (``reweight_observables``, on the GPU; the samples never leave it) turns the eight rungs into <|x|>(T), <x^2>(T) and their
-temperature derivatives Cov(A, E) / T^2, printed next to a numerical quadrature.
+temperature derivatives Cov(A, E) / T^2, printed next to a numerical quadrature; ``observable_uncertainties`` adds the
+asymptotic standard error of every mean, scaled by the statistical inefficiency of the recorded series.
 
     python examples/demo_reweight_observables.py        (needs an MI355X and the built library)
 """
@@ -13,6 +14,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import metropolisengine_amd as me  # noqa: E402
+from metropolisengine_amd import statistics  # noqa: E402
 from demo_parallel_tempering import BARRIER, LADDER, double_well  # noqa: E402
 
 WHICH = ("abs_real_0", "real_0_sq")
@@ -64,7 +66,18 @@ def main(grid=None, **kw):
         print("%6.3f   %12.5f  %10.5f   %12.5f  %10.5f   %15.5f  %10.5f   %15.5f  %10.5f   %6.4f"
               % (t, out["mean"][i, 0], exact[0, i], out["mean"][i, 1], exact[1, i], out["dmean_dT"][i, 0], exact[2, i],
                  out["dmean_dT"][i, 1], exact[3, i], out["neff_fraction"][i]))
-    return {"temps": grid, "result": out, "exact": exact, "engine": engine}
+    # error bars: the asymptotic MBAR covariance assumes independent samples, and the records of a slot are correlated in
+    # time, so every variance is scaled by the statistical inefficiency of the slot's series (the mean over 64 slots)
+    series = engine.observable_samples()[:, :, ::max(1, engine.n_chains // 64)]
+    g = [float(np.mean([statistics.statistical_inefficiency(series[:, q, c]) for c in range(series.shape[2])]))
+         for q in range(len(WHICH))]
+    bars = engine.observable_uncertainties(grid, f=None, inefficiency=g)
+    print("statistical inefficiency of the recorded series: |x| %.2f, x^2 %.2f" % tuple(g))
+    print("     T      <|x|>: MBAR +- error      quadrature     <x^2>: MBAR +- error      quadrature")
+    for i, t in enumerate(grid):
+        print("%6.3f   %12.5f ± %.5f  %10.5f   %12.5f ± %.5f  %10.5f"
+              % (t, bars["mean"][i, 0], bars["d_mean"][i, 0], exact[0, i], bars["mean"][i, 1], bars["d_mean"][i, 1], exact[1, i]))
+    return {"temps": grid, "result": out, "exact": exact, "engine": engine, "uncertainties": bars}
 
 
 if __name__ == "__main__":

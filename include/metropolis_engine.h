@@ -437,7 +437,26 @@ int me_mbar_energy_shift(me_engine *engine, double *shift);
  *                       whether it is asked for alone or among 16 columns and any number of targets.  Errors as for
  *                       me_mbar_reweight, plus ME_ERR_STATE without an observable store.
  *   me_mbar_reweight_observables_samples   the same kernels on host arrays, like me_mbar_reweight_samples; observables is
- *                       [n_observables][n_samples], 1 <= n_observables <= ME_MAX_RECORDED_OBSERVABLES. */
+ *                       [n_observables][n_samples], 1 <= n_observables <= ME_MAX_RECORDED_OBSERVABLES.
+ *   me_mbar_gram_observables   me_mbar_gram for the asymptotic covariance of the reweighted means of the Q recorded columns
+ *                       (csrc/me_mbar_cov.hip has the definition).  n_targets >= 1 target temperatures.  W has C = n_rungs +
+ *                       n_targets (1 + Q) columns: column k < n_rungs is rung k (column_counts[k] = its finite samples), column
+ *                       n_rungs + t (1 + Q) is the state of target t, W_na = exp(-E_n / T_t - d_n - ln_z_t), and column n_rungs +
+ *                       t (1 + Q) + 1 + q its observable q, W_na (A_qn - S_q) / (mean_tq - S_q) (counts 0).  S_q = (the least
+ *                       finite value of column q over the used samples) - 1, so every factor is >= 1; mean_tq is
+ *                       me_mbar_reweight_observables' mean.  gram is [C][C], full and bitwise symmetric; column_counts is [C];
+ *                       ln_z [n_targets], mean [n_targets][Q], shifts [Q] (= S_q) and *n_used may be NULL.  When some energy is
+ *                       not finite the used samples AND their columns are packed first, in their order: every result is bit for
+ *                       bit the result on the arrays with the other samples removed (so mean is me_mbar_reweight_observables'
+ *                       bit for bit when every energy is finite).  A column q whose mean at target t is not finite (a
+ *                       non-finite A_q in a used sample) gets NaN in the row and the column of gram of its columns, and no other
+ *                       entry changes.  Targets go through the device in chunks of (128 - n_rungs) / (1 + Q) (at least 3),
+ *                       every chunk with the ladder columns, and the blocks of gram that pair targets of different chunks are
+ *                       NaN.  The entries that pair ladder and state columns are me_mbar_gram's bit for bit.  All sums have a
+ *                       fixed order.  Errors as for me_mbar_gram, and ME_ERR_INVALID for n_targets < 1, ME_ERR_STATE without an
+ *                       observable store.
+ *   me_mbar_gram_observables_samples   the same on host arrays; observables is [n_columns][n_samples], 1 <= n_columns <=
+ *                       ME_MAX_RECORDED_OBSERVABLES (ME_ERR_INVALID otherwise). */
 #define ME_MAX_RECORDED_OBSERVABLES 16
 int me_observable_samples_enable(me_engine *engine, const int32_t *indices, int32_t n_observables);
 int me_observable_samples_info(me_engine *engine, int32_t *n_observables, int32_t *indices);
@@ -449,6 +468,12 @@ int me_mbar_reweight_observables_samples(int32_t device_id, const double *energi
                                          const double *observables, int32_t n_observables, const double *ladder_temps,
                                          int32_t n_rungs, const double *f, const double *temps, int32_t n, double *mean,
                                          double *var, double *cov_energy, double *neff_fraction);
+int me_mbar_gram_observables(me_engine *engine, const double *f, const double *temps, int32_t n_targets, double *gram,
+                             double *column_counts, double *ln_z, double *mean, double *shifts, int64_t *n_used);
+int me_mbar_gram_observables_samples(int32_t device_id, const double *energies, const int32_t *rungs, int64_t n_samples,
+                                     const double *ladder_temps, int32_t n_rungs, const double *observables, int32_t n_columns,
+                                     const double *f, const double *temps, int32_t n_targets, double *gram,
+                                     double *column_counts, double *ln_z, double *mean, double *shifts, int64_t *n_used);
 
 /* Text of the last error on this engine (or of the last failed me_create when engine is NULL). */
 int me_last_error(me_engine *engine, char *buf, size_t buf_bytes);

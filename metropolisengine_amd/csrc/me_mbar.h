@@ -58,6 +58,11 @@ struct ObsColumns {
   int n_columns;
   long long n_chains, record_stride, column_stride;
 };
+// where column 0 of sample i sits in such columns
+__device__ __forceinline__ long long obs_offset(const ObsColumns &oc, long long i) {
+  const long long record = i / oc.n_chains;
+  return record * oc.record_stride + (i - record * oc.n_chains);
+}
 
 // Device scratch of one problem.  Every operation: `counts` (unsigned long long [kK]) and `table` (double [kTableDoubles]),
 // both from prepare.  Operations with target temperatures: `inv_temps` (double, 1 / T_t) and `out` (double), both sized by
@@ -129,6 +134,16 @@ int mbar_check_common(me_engine *e, const Problem &p, hipError_t err);
 int mbar_check_temps(me_engine *e, const double *temps, int n, const char *what);
 
 // ---- defined in me_mbar_obs.hip -----------------------------------------------------------------------------------------
+// Device scratch of one observable reweighting: d_n of every sample and the block partials
+struct ObsScratch {
+  DeviceBuffer d, partials;
+};
+// Enqueues the reweighting of the columns `oc` of `sm` (the problem's samples, or the used ones of them packed) to the n_temps
+// temperatures whose 1 / T_t are on the device at inv_temps: afterwards out = [mean | var | cov_energy][target][column], then
+// neff_fraction[target], 3 n_temps Q + n_temps doubles of device memory.  Does not wait: `scratch` is the caller's to keep until
+// the stream has been waited for.
+hipError_t reweight_observables_enqueue(Problem &p, const MbarSamples &sm, const ObsColumns &oc, const double *inv_temps, int n_temps,
+                                        ObsScratch &scratch, double *out);
 // me_energy_samples_record's second kernel: row `row` of the engine's observable store (which exists) on the engine's stream
 hipError_t observable_record_enqueue(me_engine *e, long long row);
 

@@ -33,7 +33,32 @@
 // a k-step -> the k-steps in sample order -> the block's tiles in order -> partials[block][C (C + 1) / 2] (packed lower
 // triangle) in global memory -> k_mbar_gram_finish adds the blocks in ascending order, one thread per entry, and writes G[i][j]
 // and G[j][i] from the same sum, so G is symmetric bit for bit.
-// Registers (hipcc -O3, gfx950): k_mbar_gram 93 VGPRs + 72 AGPRs (the accumulators), 3 wavefronts per SIMD, no scratch.
+//
+// The observable form (me_mbar_gram_observables and its engine-less twin): error bars for the reweighted means of the Q <= 16
+// recorded columns A_q (ObsColumns: an engine's store or host columns).  C = K + n_targets (1 + Q):
+//     state column of target t         W_na as above                                          column K + t (1 + Q),         count 0
+//     observable column q of target t  W_nA = W_na (A_qn - S_q) / (mean_tq - S_q)               column K + t (1 + Q) + 1 + q, count 0
+// S_q = (the least finite value of column q over the used samples) - 1, so that every factor is >= 1 (a zero-mean observable
+// is no special case), and mean_tq is what the observable reweighting kernels (me_mbar_obs.hip) leave on the device.  A column
+// whose mean_tq is not finite (a non-finite A_q in a used sample) gets a NaN normaliser: its row and column of G are NaN and
+// no other entry changes.  Targets go in chunks of (128 - K) / (1 + Q), at least 3, every chunk with the ladder columns.
+// Kernels: k_mbar_compact also packs the columns of the used samples ([Q][n_used]); k_mbar_min_columns (grid (blocks, Q)) is
+// k_mbar_min per column; k_mbar_gram_obs_columns (one block) is k_mbar_gram_columns with, per column of W, the observable it
+// carries (-1: none), its shift and its normaliser; k_mbar_gram<true> is k_mbar_gram<false> (the kernel of the energy form)
+// with two additions: per 256 samples every lane parks the Q values of its sample in LDS beside (E_n, d_n), as [Q][257]
+// doubles -- the fill threads of a half-wavefront read 2 rows x 16 columns, that is observables q .. q + 15 of samples s, s + 1;
+// with the odd stride 257 value (q, s) lies in bank 2 (q + s) mod 64 for the 8-byte reads, so only pairs with equal q + s
+// collide (two-way), where the stride 256 would put all sixteen observables of a sample on one bank -- and the fill multiplies
+// the exponential by (A_qn - S_q) / (mean_tq - S_q).  The MFMA loop, the tile assignment and the summation order are the same
+// code, so an entry that pairs ladder and state columns has the bits the energy form gives it, and an observable column has the
+// same bits alone as among 16.
+// LDS per block: [2][16][Cp] sub-tile buffers (36 KiB at C = 128), 4 KiB (E_n, d_n), 3 KiB column constants; the observable form
+// adds Q x 257 x 8 bytes (32.1 KiB at Q = 16) and 1.5 KiB of column constants: 76.6 KiB at C = 128, Q = 16, which needs the
+// raised dynamic-LDS limit and lets two blocks share a CU's 160 KiB (2 wavefronts per SIMD); 46.5 KiB at Q = 1 (3 blocks).
+// Registers (hipcc -O3, gfx950, -Rpass-analysis=kernel-resource-usage): k_mbar_gram<false> 93 VGPRs + 72 AGPRs (the
+// accumulators), 3 wavefronts per SIMD, no scratch; k_mbar_gram<true> 95 VGPRs + 72 AGPRs, 3 wavefronts per SIMD by
+// registers (2 where the LDS of 16 observables decides), no scratch; no other kernel of this file uses scratch.
+#include "me_launch.h"
 #include "me_mbar.h"
 
 namespace me {
@@ -44,6 +69,10 @@ constexpr int kMaxCols = 128;                   // columns of W per launch
 constexpr int kSub = 16;                        // samples per sub-tile in LDS
 constexpr int kSlots = 9;                       // 16 x 16 tiles of G per wavefront: 36 lower-triangle tiles / 4
 constexpr int kColB = 0, kColG = kMaxCols, kColMean = 2 * kMaxCols, kColShift = 3 * kMaxCols, kColDoubles = 3 * kMaxCols + 1;
+// the observable form's column constants: [b | g | normaliser | shift of the column | observable of the column, -1: none], then S_q
+constexpr int kColOwnShift = 3 * kMaxCols, kColWhich = 4 * kMaxCols, kColShifts = 5 * kMaxCols;
+constexpr int kObsColDoubles = 5 * kMaxCols + ME_MAX_RECORDED_OBSERVABLES;
+constexpr int kObsStride = kThreads + 1;        // doubles between two observables of the parked samples (odd: see the header)
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 
@@ -78,9 +107,11 @@ __global__ void __launch_bounds__(kThreads) k_mbar_scan(const unsigned int *__re
   }
 }
 
-// the finite energies of tile blockIdx.x, in their order, to packed[offsets[tile] ..)
+// the finite energies of tile blockIdx.x, in their order, to packed[offsets[tile] ..), and the columns `oc` of those samples
+// (oc.n_columns = 0: none) to packed_columns[column][n_used]
 __global__ void __launch_bounds__(kThreads) k_mbar_compact(const double *__restrict__ energies, long long n,
-                                                           const long long *__restrict__ offsets, double *packed) {
+                                                           const long long *__restrict__ offsets, double *packed, ObsColumns oc,
+                                                           double *packed_columns, long long n_used) {
   __shared__ unsigned int waves[kItems][kWaves];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   double e[kItems];
@@ -103,15 +134,30 @@ __global__ void __launch_bounds__(kThreads) k_mbar_compact(const double *__restr
       before += w < wave ? waves[r][w] : 0u;
       all += waves[r][w];
     }
-    if (isfinite(e[r])) packed[at + before + rank[r]] = e[r];
+    if (isfinite(e[r])) {
+      const long long to = at + before + rank[r];
+      packed[to] = e[r];
+      if (oc.n_columns > 0) {
+        const double *from = oc.data + obs_offset(oc, (long long)blockIdx.x * kTile + (long long)r * kThreads + threadIdx.x);
+        for (int q = 0; q < oc.n_columns; ++q) packed_columns[(long long)q * n_used + to] = from[(long long)q * oc.column_stride];
+      }
+    }
     at += all;
   }
+}
+
+// *dst = the least of the block's v
+__device__ __forceinline__ void block_min_store(double v, double *dst) {
+  __shared__ double waves[kWaves];
+  v = wave_min(v);
+  if ((threadIdx.x & 63) == 0) waves[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) *dst = fmin(fmin(waves[0], waves[1]), fmin(waves[2], waves[3]));
 }
 
 // minima[block] = the least finite energy of the block's tiles (+inf when it has none)
 __global__ void __launch_bounds__(kThreads) k_mbar_min(const double *__restrict__ energies, long long n, long long n_tiles,
                                                        double *minima) {
-  __shared__ double waves[kWaves];
   double v = INFINITY;
   for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x)
     for (int r = 0; r < kItems; ++r) {
@@ -119,10 +165,31 @@ __global__ void __launch_bounds__(kThreads) k_mbar_min(const double *__restrict_
       const double e = i < n ? energies[i] : NAN;
       if (isfinite(e)) v = fmin(v, e);
     }
-  v = wave_min(v);
-  if ((threadIdx.x & 63) == 0) waves[threadIdx.x >> 6] = v;
+  block_min_store(v, minima + blockIdx.x);
+}
+
+// minima[column][block] = the least finite value of column blockIdx.y over the block's tiles; grid (blocks, columns)
+__global__ void __launch_bounds__(kThreads) k_mbar_min_columns(ObsColumns oc, long long n, long long n_tiles, double *minima) {
+  const double *column = oc.data + (long long)blockIdx.y * oc.column_stride;
+  double v = INFINITY;
+  for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x)
+    for (int r = 0; r < kItems; ++r) {
+      const long long i = tile * kTile + (long long)r * kThreads + threadIdx.x;
+      const double a = i < n ? column[obs_offset(oc, i)] : NAN;
+      if (isfinite(a)) v = fmin(v, a);
+    }
+  block_min_store(v, minima + (size_t)blockIdx.y * gridDim.x + blockIdx.x);
+}
+
+// the least of minima[0 .. n_blocks), in every thread of a block of kMaxCols
+__device__ __forceinline__ double least_of_blocks(const double *__restrict__ minima, int n_blocks, double *part) {
+  double v = INFINITY;
+  for (int b = threadIdx.x; b < n_blocks; b += kMaxCols) v = fmin(v, minima[b]);
+  part[threadIdx.x] = v;
   __syncthreads();
-  if (threadIdx.x == 0) minima[blockIdx.x] = fmin(fmin(waves[0], waves[1]), fmin(waves[2], waves[3]));
+  v = part[0];
+  for (int k = 1; k < kMaxCols; ++k) v = fmin(v, part[k]);
+  return v;
 }
 
 // cols = [b | g | mean | E_shift] of the K ladder columns and of the two columns of each of n_targets temperatures, whose
@@ -132,13 +199,7 @@ __global__ void __launch_bounds__(kMaxCols) k_mbar_gram_columns(const double *__
                                                                 const double *__restrict__ out, int n_targets,
                                                                 const double *__restrict__ minima, int n_blocks, double *cols) {
   __shared__ double part[kMaxCols];
-  double v = INFINITY;
-  for (int b = threadIdx.x; b < n_blocks; b += kMaxCols) v = fmin(v, minima[b]);
-  part[threadIdx.x] = v;
-  __syncthreads();
-  v = part[0];
-  for (int k = 1; k < kMaxCols; ++k) v = fmin(v, part[k]);
-  const double shift = v - 1.0;
+  const double shift = least_of_blocks(minima, n_blocks, part) - 1.0;
   const int c = threadIdx.x;
   double b = 0.0, g = 0.0, mean = 0.0;
   if (c < n_rungs) {
@@ -156,13 +217,57 @@ __global__ void __launch_bounds__(kMaxCols) k_mbar_gram_columns(const double *__
   if (c == 0) cols[kColShift] = shift;
 }
 
-// partials[block] = the packed lower triangle of the block's part of W^T W, n_cols = K + 2 n_targets <= kMaxCols columns.
-// Dynamic LDS: 2 * kSub * cp doubles, cp the padded row length (see the header of this file).
+// The observable form's cols = [b | g | normaliser | shift | observable] of the K ladder columns and of the 1 + nq columns of
+// each of n_targets temperatures, then S_q: (ln_z, ., ., .) of the targets in `out`, the reweighted means [n_targets][nq] in
+// `means`, both as the reweighting kernels left them; minima is [nq][n_blocks]
+__global__ void __launch_bounds__(kMaxCols) k_mbar_gram_obs_columns(const double *__restrict__ table, int n_rungs,
+                                                                    const double *__restrict__ inv_temps,
+                                                                    const double *__restrict__ out, const double *__restrict__ means,
+                                                                    int nq, int n_targets, const double *__restrict__ minima,
+                                                                    int n_blocks, double *cols) {
+  __shared__ double part[kMaxCols], shifts[ME_MAX_RECORDED_OBSERVABLES];
+  for (int q = 0; q < nq; ++q) {
+    const double least = least_of_blocks(minima + (size_t)q * n_blocks, n_blocks, part);
+    if (threadIdx.x == 0) shifts[q] = least - 1.0;
+    __syncthreads();                                             // (`part` is written again)
+  }
+  const int c = threadIdx.x;
+  double b = 0.0, g = 0.0, mean = 0.0, shift = 0.0, which = -1.0;
+  if (c < n_rungs) {
+    b = table[kBeta + c];
+    g = table[kF + c];
+  } else if (c < n_rungs + (1 + nq) * n_targets) {
+    const int t = (c - n_rungs) / (1 + nq), j = (c - n_rungs) - t * (1 + nq);
+    b = inv_temps[t];
+    g = -out[4 * t];
+    if (j > 0) {
+      const double m = means[t * nq + j - 1];
+      which = (double)(j - 1);
+      shift = shifts[j - 1];
+      mean = isfinite(m) ? m - shift : NAN;                      // (NaN: the whole column of W, and its row and column of G)
+    }
+  }
+  cols[kColB + c] = b;
+  cols[kColG + c] = g;
+  cols[kColMean + c] = mean;
+  cols[kColOwnShift + c] = shift;
+  cols[kColWhich + c] = which;
+  if (c < nq) cols[kColShifts + c] = shifts[c];
+}
+
+// partials[block] = the packed lower triangle of the block's part of W^T W, n_cols <= kMaxCols columns.  kObs = false: the
+// energy form, n_cols = K + 2 n_targets, `oc` unused; kObs = true: the observable form, n_cols = K + (1 + Q) n_targets, `cols` of
+// k_mbar_gram_obs_columns.  Dynamic LDS: 2 * kSub * cp doubles, cp the padded row length (see the header of this file), and
+// in the observable form oc.n_columns * kObsStride more.
+template <bool kObs>
 __global__ void __launch_bounds__(kThreads) k_mbar_gram(const double *__restrict__ energies, long long n, int n_rungs,
                                                         const double *__restrict__ table, const double *__restrict__ cols,
-                                                        int n_cols, int cp, long long n_tiles, double *partials) {
-  extern __shared__ double w_lds[];                              // [2][kSub][cp]
+                                                        int n_cols, int cp, long long n_tiles, double *partials, ObsColumns oc) {
+  extern __shared__ double w_lds[];                              // [2][kSub][cp], then s_a [Q][kObsStride]
   __shared__ double s_e[kThreads], s_d[kThreads], c_b[kMaxCols], c_g[kMaxCols], c_mean[kMaxCols];
+  __shared__ double c_shift[kObs ? kMaxCols : 1];
+  __shared__ int c_which[kObs ? kMaxCols : 1];
+  double *const s_a = w_lds + 2 * kSub * cp;
   const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int h4 = lane >> 4, j16 = lane & 15;                     // the MFMA's (k, i / j) of this lane
   const int tn = (n_cols + 15) >> 4, n_pairs = tn * (tn + 1) / 2;
@@ -170,8 +275,12 @@ __global__ void __launch_bounds__(kThreads) k_mbar_gram(const double *__restrict
     c_b[t] = cols[kColB + t];
     c_g[t] = cols[kColG + t];
     c_mean[t] = cols[kColMean + t];
+    if constexpr (kObs) {
+      c_shift[t] = cols[kColOwnShift + t];
+      c_which[t] = (int)cols[kColWhich + t];
+    }
   }
-  const double shift = cols[kColShift];
+  const double shift = kObs ? 0.0 : cols[kColShift];
   // this wavefront's tiles: pair p = wave + 4 s = I (I + 1) / 2 + J, column offsets 16 I and 16 J
   int off_i[kSlots], off_j[kSlots];
 #pragma unroll
@@ -199,6 +308,18 @@ __global__ void __launch_bounds__(kThreads) k_mbar_gram(const double *__restrict
       // (every thread has passed the last barrier of the step before, so its fills have read s_e and s_d)
       s_e[t] = ok ? e : 0.0;
       s_d[t] = ok ? m + log(s) : INFINITY;
+      if constexpr (kObs) {
+        if (i < n) {
+          // (the record of the step's first sample is wave-uniform: the division stays off the vector registers)
+          long long record = (i - t) / oc.n_chains, chain = (i - t) - record * oc.n_chains + t;
+          while (chain >= oc.n_chains) {
+            chain -= oc.n_chains;
+            record += 1;
+          }
+          const double *a = oc.data + record * oc.record_stride + chain;
+          for (int c = 0; c < oc.n_columns; ++c) s_a[c * kObsStride + t] = a[(long long)c * oc.column_stride];
+        }
+      }
       __syncthreads();
 #pragma unroll 1
       for (int q = 0; q < kThreads / kSub; ++q) {
@@ -211,8 +332,13 @@ __global__ void __launch_bounds__(kThreads) k_mbar_gram(const double *__restrict
             double w = 0.0;
             if (used && col < n_cols) {
               w = math64::exp_nonpos(fmin(__builtin_fma(-c_b[col], es, c_g[col]) - ds, 0.0));
-              const double mean = c_mean[col];
-              if (mean != 0.0) w = w * (es - shift) / mean;
+              if constexpr (kObs) {
+                const int which = c_which[col];
+                if (which >= 0) w = w * (s_a[which * kObsStride + q * kSub + row] - c_shift[col]) / c_mean[col];
+              } else {
+                const double mean = c_mean[col];
+                if (mean != 0.0) w = w * (es - shift) / mean;
+              }
             }
             buf[row * cp + col] = w;
           }
@@ -261,75 +387,162 @@ int padded_row(int n_cols) {
   return cpad % 32 == 0 ? cpad + 16 : cpad;
 }
 
-// Waits for the stream and writes host arrays: gram[C][C] (C = n_rungs + 2 n_targets; the target-target blocks of targets
-// from different chunks are NaN), column_counts[C], ln_z / mean_e[n_targets] (may be nullptr).  With an empty rung
-// (p.empty_rung) nothing else is computed.
+// The used samples of a problem alone, in their order, with their observable columns (the rungs are in the counts already):
+// the problem's own arrays when every energy is finite, a packed copy otherwise.
+struct UsedSamples {
+  MbarSamples sm{};
+  ObsColumns oc{};
+  DeviceBuffer energies, columns, tile_counts, tile_offsets;
+};
+hipError_t pack_used(const Problem &p, const ObsColumns &oc, UsedSamples &u) {
+  const MbarSamples &sm = p.sm;
+  u.sm = MbarSamples{sm.energies, nullptr, p.n_used_ll, 1, 1};
+  u.oc = oc;
+  if (p.n_used_ll == sm.n_samples) return hipSuccess;
+  const long long all_tiles = tiles_of(sm.n_samples);
+  ME_MBAR_HIP(u.energies.resize((size_t)p.n_used_ll * sizeof(double)));
+  ME_MBAR_HIP(u.columns.resize((size_t)p.n_used_ll * (size_t)oc.n_columns * sizeof(double)));
+  ME_MBAR_HIP(u.tile_counts.resize((size_t)all_tiles * sizeof(unsigned int)));
+  ME_MBAR_HIP(u.tile_offsets.resize((size_t)all_tiles * sizeof(long long)));
+  hipLaunchKernelGGL(k_mbar_used_tiles, dim3((unsigned)all_tiles), dim3(kThreads), 0, p.stream, sm.energies, sm.n_samples,
+                     u.tile_counts.get<unsigned int>());
+  hipLaunchKernelGGL(k_mbar_scan, dim3(1), dim3(kThreads), 0, p.stream, u.tile_counts.get<const unsigned int>(), all_tiles,
+                     u.tile_offsets.get<long long>());
+  hipLaunchKernelGGL(k_mbar_compact, dim3((unsigned)all_tiles), dim3(kThreads), 0, p.stream, sm.energies, sm.n_samples,
+                     u.tile_offsets.get<const long long>(), u.energies.get<double>(), oc, u.columns.get<double>(), p.n_used_ll);
+  ME_MBAR_HIP(hipGetLastError());
+  u.sm.energies = u.energies.get<double>();
+  if (oc.n_columns > 0) u.oc = ObsColumns{u.columns.get<const double>(), oc.n_columns, p.n_used_ll, 0, p.n_used_ll};
+  return hipSuccess;
+}
+
+// The Gram matrix of a weight matrix of n_rungs + per_target n_targets columns over n_samples samples, in chunks of targets
+// that each carry the ladder columns.  launch(t0, nt, n_cols, cp, partials) enqueues the column constants and the Gram kernel
+// of the nt targets from t0 (n_cols = n_rungs + per_target nt columns, padded row cp); copy_results() enqueues the copies of
+// whatever else the caller returns.  Waits for the stream and writes gram[C][C] (the target-target blocks of targets from
+// different chunks are NaN) and column_counts[C].
+template <class Launch, class Copy>
+hipError_t gram_chunks(Problem &p, long long n_samples, int per_target, int n_targets, double *gram, double *column_counts,
+                       Launch launch, Copy copy_results) {
+  const int n_rungs = p.n_rungs, n_blocks = blocks_of(n_samples);
+  hipStream_t stream = p.stream;
+  const int per_chunk = (kMaxCols - n_rungs) / per_target;        // targets of one pass: K + per_target per_chunk <= kMaxCols
+  const int n_chunks = std::max(1, (n_targets + per_chunk - 1) / per_chunk);
+  const int max_cols = n_rungs + per_target * std::min(n_targets, per_chunk);
+  DeviceBuffer chunk_partials, dense;
+  ME_MBAR_HIP(chunk_partials.resize((size_t)n_blocks * (size_t)(max_cols * (max_cols + 1) / 2) * sizeof(double)));
+  ME_MBAR_HIP(dense.resize((size_t)n_chunks * kMaxCols * kMaxCols * sizeof(double)));
+  for (int c = 0; c < n_chunks; ++c) {
+    const int t0 = c * per_chunk, nt = std::min(per_chunk, n_targets - t0), n_cols = n_rungs + per_target * nt;
+    ME_MBAR_HIP(launch(t0, nt, n_cols, padded_row(n_cols), chunk_partials.get<double>()));
+    hipLaunchKernelGGL(k_mbar_gram_finish, dim3(n_cols), dim3(kMaxCols), 0, stream, chunk_partials.get<const double>(), n_blocks, n_cols,
+                       dense.get<double>() + (size_t)c * kMaxCols * kMaxCols);
+  }
+  ME_MBAR_HIP(hipGetLastError());
+  std::vector<double> host((size_t)n_chunks * kMaxCols * kMaxCols);
+  ME_MBAR_HIP(hipMemcpyAsync(host.data(), dense.get(), host.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+  ME_MBAR_HIP(copy_results());
+  ME_MBAR_HIP(hipStreamSynchronize(stream));
+  const int n_all = n_rungs + per_target * n_targets;
+  std::fill(gram, gram + (size_t)n_all * n_all, (double)NAN);
+  for (int c = 0; c < n_chunks; ++c) {
+    const int t0 = c * per_chunk, nt = std::min(per_chunk, n_targets - t0), n_cols = n_rungs + per_target * nt;
+    const double *chunk = host.data() + (size_t)c * kMaxCols * kMaxCols;
+    auto global = [&](int l) { return l < n_rungs ? l : l + per_target * t0; };
+    for (int i = 0; i < n_cols; ++i)
+      for (int j = 0; j < n_cols; ++j) gram[(size_t)global(i) * n_all + global(j)] = chunk[i * n_cols + j];
+  }
+  for (int k = 0; k < n_all; ++k) column_counts[k] = k < n_rungs ? (double)p.counts[k] : 0.0;
+  return hipSuccess;
+}
+
+// Waits for the stream and writes host arrays: gram[C][C] (C = n_rungs + 2 n_targets), column_counts[C], ln_z /
+// mean_e[n_targets] (may be nullptr).  With an empty rung (p.empty_rung) nothing else is computed.
 hipError_t mbar_gram(Problem &p, const Source &src, const double *f, const double *temps, int n_targets, double *gram,
                      double *column_counts, double *ln_z, double *mean_e) {
   ME_MBAR_HIP(prepare(p, src, f));
   if (p.empty_rung >= 0) return hipSuccess;
   Work &w = p.w;
-  const MbarSamples &sm = p.sm;
   const int n_rungs = p.n_rungs;
   hipStream_t stream = p.stream;
-  // the used samples alone, in their order (the rungs are in the counts already)
-  MbarSamples packed_samples{sm.energies, nullptr, p.n_used_ll, 1, 1};
-  DeviceBuffer packed, tile_counts, tile_offsets;
-  if (p.n_used_ll != sm.n_samples) {
-    const long long all_tiles = tiles_of(sm.n_samples);
-    ME_MBAR_HIP(packed.resize((size_t)p.n_used_ll * sizeof(double)));
-    ME_MBAR_HIP(tile_counts.resize((size_t)all_tiles * sizeof(unsigned int)));
-    ME_MBAR_HIP(tile_offsets.resize((size_t)all_tiles * sizeof(long long)));
-    hipLaunchKernelGGL(k_mbar_used_tiles, dim3((unsigned)all_tiles), dim3(kThreads), 0, stream, sm.energies, sm.n_samples,
-                       tile_counts.get<unsigned int>());
-    hipLaunchKernelGGL(k_mbar_scan, dim3(1), dim3(kThreads), 0, stream, tile_counts.get<const unsigned int>(), all_tiles,
-                       tile_offsets.get<long long>());
-    hipLaunchKernelGGL(k_mbar_compact, dim3((unsigned)all_tiles), dim3(kThreads), 0, stream, sm.energies, sm.n_samples,
-                       tile_offsets.get<const long long>(), packed.get<double>());
-    ME_MBAR_HIP(hipGetLastError());
-    packed_samples.energies = packed.get<double>();
-  }
-  const MbarSamples &ps = packed_samples;
-  std::vector<double> inv;                                        // (on its way to the device until the wait below)
+  UsedSamples used;
+  ME_MBAR_HIP(pack_used(p, ObsColumns{}, used));
+  const MbarSamples &ps = used.sm;
+  std::vector<double> inv;                                        // (on its way to the device until the wait in gram_chunks)
   if (n_targets > 0) ME_MBAR_HIP(reweight_enqueue(p, ps, temps, n_targets, inv));
   const int n_blocks = blocks_of(ps.n_samples);
   const long long n_tiles = tiles_of(ps.n_samples);
-  const int per_chunk = (kMaxCols - n_rungs) / 2;                 // targets of one pass: K + 2 per_chunk <= kMaxCols
-  const int n_chunks = std::max(1, (n_targets + per_chunk - 1) / per_chunk);
-  const int max_cols = n_rungs + 2 * std::min(n_targets, per_chunk);
-  DeviceBuffer minima, cols, chunk_partials, dense;
+  DeviceBuffer minima, cols;
   ME_MBAR_HIP(minima.resize((size_t)n_blocks * sizeof(double)));
   ME_MBAR_HIP(cols.resize(kColDoubles * sizeof(double)));
-  ME_MBAR_HIP(chunk_partials.resize((size_t)n_blocks * (size_t)(max_cols * (max_cols + 1) / 2) * sizeof(double)));
-  ME_MBAR_HIP(dense.resize((size_t)n_chunks * kMaxCols * kMaxCols * sizeof(double)));
   hipLaunchKernelGGL(k_mbar_min, dim3(n_blocks), dim3(kThreads), 0, stream, ps.energies, ps.n_samples, n_tiles, minima.get<double>());
-  for (int c = 0; c < n_chunks; ++c) {
-    const int t0 = c * per_chunk, nt = std::min(per_chunk, n_targets - t0), n_cols = n_rungs + 2 * nt, cp = padded_row(n_cols);
-    hipLaunchKernelGGL(k_mbar_gram_columns, dim3(1), dim3(kMaxCols), 0, stream, w.table.get<const double>(), n_rungs,
-                       n_targets > 0 ? w.inv_temps.get<const double>() + t0 : nullptr,
-                       n_targets > 0 ? w.out.get<const double>() + 4 * (size_t)t0 : nullptr, nt, minima.get<const double>(), n_blocks,
-                       cols.get<double>());
-    hipLaunchKernelGGL(k_mbar_gram, dim3(n_blocks), dim3(kThreads), 2 * kSub * cp * sizeof(double), stream, ps.energies, ps.n_samples,
-                       n_rungs, w.table.get<const double>(), cols.get<const double>(), n_cols, cp, n_tiles, chunk_partials.get<double>());
-    hipLaunchKernelGGL(k_mbar_gram_finish, dim3(n_cols), dim3(kMaxCols), 0, stream, chunk_partials.get<const double>(), n_blocks, n_cols,
-                       dense.get<double>() + (size_t)c * kMaxCols * kMaxCols);
-  }
-  ME_MBAR_HIP(hipGetLastError());
-  std::vector<double> host((size_t)n_chunks * kMaxCols * kMaxCols), out(4 * (size_t)n_targets);
-  ME_MBAR_HIP(hipMemcpyAsync(host.data(), dense.get(), host.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-  if (n_targets > 0) ME_MBAR_HIP(hipMemcpyAsync(out.data(), w.out.get(), out.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-  ME_MBAR_HIP(hipStreamSynchronize(stream));
-  const int n_all = n_rungs + 2 * n_targets;
-  std::fill(gram, gram + (size_t)n_all * n_all, (double)NAN);
-  for (int c = 0; c < n_chunks; ++c) {
-    const int t0 = c * per_chunk, nt = std::min(per_chunk, n_targets - t0), n_cols = n_rungs + 2 * nt;
-    const double *chunk = host.data() + (size_t)c * kMaxCols * kMaxCols;
-    auto global = [&](int l) { return l < n_rungs ? l : l + 2 * t0; };
-    for (int i = 0; i < n_cols; ++i)
-      for (int j = 0; j < n_cols; ++j) gram[(size_t)global(i) * n_all + global(j)] = chunk[i * n_cols + j];
-  }
-  for (int k = 0; k < n_all; ++k) column_counts[k] = k < n_rungs ? (double)p.counts[k] : 0.0;
+  std::vector<double> out(4 * (size_t)n_targets);
+  ME_MBAR_HIP(gram_chunks(
+      p, ps.n_samples, 2, n_targets, gram, column_counts,
+      [&](int t0, int nt, int n_cols, int cp, double *partials) {
+        hipLaunchKernelGGL(k_mbar_gram_columns, dim3(1), dim3(kMaxCols), 0, stream, w.table.get<const double>(), n_rungs,
+                           n_targets > 0 ? w.inv_temps.get<const double>() + t0 : nullptr,
+                           n_targets > 0 ? w.out.get<const double>() + 4 * (size_t)t0 : nullptr, nt, minima.get<const double>(),
+                           n_blocks, cols.get<double>());
+        hipLaunchKernelGGL(k_mbar_gram<false>, dim3(n_blocks), dim3(kThreads), 2 * kSub * cp * sizeof(double), stream, ps.energies,
+                           ps.n_samples, n_rungs, w.table.get<const double>(), cols.get<const double>(), n_cols, cp, n_tiles, partials,
+                           ObsColumns{});
+        return hipSuccess;
+      },
+      [&] {
+        if (n_targets == 0) return hipSuccess;
+        return hipMemcpyAsync(out.data(), w.out.get(), out.size() * sizeof(double), hipMemcpyDeviceToHost, stream);
+      }));
   unpack_targets(out, n_targets, ln_z, mean_e, nullptr, nullptr);
+  return hipSuccess;
+}
+
+// The observable form: gram[C][C] and column_counts[C] with C = n_rungs + n_targets (1 + Q), ln_z[n_targets], mean[n_targets][Q]
+// and shifts[Q] (the last three may be nullptr).  n_targets >= 1 and src has columns.
+hipError_t mbar_gram_observables(Problem &p, const Source &src, const double *f, const double *temps, int n_targets, double *gram,
+                                 double *column_counts, double *ln_z, double *mean, double *shifts) {
+  ME_MBAR_HIP(prepare(p, src, f));
+  if (p.empty_rung >= 0) return hipSuccess;
+  Work &w = p.w;
+  const int n_rungs = p.n_rungs, nq = src.columns.n_columns;
+  hipStream_t stream = p.stream;
+  UsedSamples used;
+  ME_MBAR_HIP(pack_used(p, src.columns, used));
+  const MbarSamples &ps = used.sm;
+  const size_t cells = (size_t)n_targets * nq;
+  std::vector<double> inv;
+  ObsScratch scratch;
+  DeviceBuffer obs_out, minima, cols;
+  ME_MBAR_HIP(reweight_enqueue(p, ps, temps, n_targets, inv));
+  ME_MBAR_HIP(obs_out.resize((3 * cells + (size_t)n_targets) * sizeof(double)));
+  ME_MBAR_HIP(reweight_observables_enqueue(p, ps, used.oc, w.inv_temps.get<const double>(), n_targets, scratch, obs_out.get<double>()));
+  const int n_blocks = blocks_of(ps.n_samples);
+  const long long n_tiles = tiles_of(ps.n_samples);
+  ME_MBAR_HIP(minima.resize((size_t)nq * n_blocks * sizeof(double)));
+  ME_MBAR_HIP(cols.resize(kObsColDoubles * sizeof(double)));
+  ME_MBAR_HIP(raise_lds_limit<k_mbar_gram<true>>((2 * kSub * padded_row(kMaxCols) + ME_MAX_RECORDED_OBSERVABLES * kObsStride) * sizeof(double)));
+  hipLaunchKernelGGL(k_mbar_min_columns, dim3(n_blocks, nq), dim3(kThreads), 0, stream, used.oc, ps.n_samples, n_tiles, minima.get<double>());
+  std::vector<double> out(4 * (size_t)n_targets), means(cells), own_shifts((size_t)nq);
+  ME_MBAR_HIP(gram_chunks(
+      p, ps.n_samples, 1 + nq, n_targets, gram, column_counts,
+      [&](int t0, int nt, int n_cols, int cp, double *partials) {
+        hipLaunchKernelGGL(k_mbar_gram_obs_columns, dim3(1), dim3(kMaxCols), 0, stream, w.table.get<const double>(), n_rungs,
+                           w.inv_temps.get<const double>() + t0, w.out.get<const double>() + 4 * (size_t)t0,
+                           obs_out.get<const double>() + (size_t)t0 * nq, nq, nt, minima.get<const double>(), n_blocks, cols.get<double>());
+        hipLaunchKernelGGL(k_mbar_gram<true>, dim3(n_blocks), dim3(kThreads), (2 * kSub * cp + nq * kObsStride) * sizeof(double), stream,
+                           ps.energies, ps.n_samples, n_rungs, w.table.get<const double>(), cols.get<const double>(), n_cols, cp, n_tiles,
+                           partials, used.oc);
+        return hipSuccess;
+      },
+      [&] {
+        ME_MBAR_HIP(hipMemcpyAsync(out.data(), w.out.get(), out.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+        ME_MBAR_HIP(hipMemcpyAsync(means.data(), obs_out.get(), cells * sizeof(double), hipMemcpyDeviceToHost, stream));
+        return hipMemcpyAsync(own_shifts.data(), cols.get<double>() + kColShifts, own_shifts.size() * sizeof(double), hipMemcpyDeviceToHost,
+                              stream);
+      }));
+  unpack_targets(out, n_targets, ln_z, nullptr, nullptr, nullptr);
+  if (mean) std::copy(means.begin(), means.end(), mean);
+  if (shifts) std::copy(own_shifts.begin(), own_shifts.end(), shifts);
   return hipSuccess;
 }
 
@@ -362,6 +575,19 @@ int gram_common(const Source &src, const double *f, const double *temps, int n_t
   return ME_OK;
 }
 
+// the two forms of me_mbar_gram_observables behind their Source
+int gram_observables_common(const Source &src, const double *f, const double *temps, int n_targets, double *gram, double *column_counts,
+                            double *ln_z, double *mean, double *shifts, int64_t *n_used) {
+  if (!gram || !column_counts) return fail(src.e, ME_ERR_INVALID, "gram and column_counts are needed");
+  int rc = check_f_and_targets(src.e, f, std::min(src.n_rungs, kK), temps, n_targets, 1);
+  if (rc) return rc;
+  Problem p;
+  rc = mbar_check_common(src.e, p, mbar_gram_observables(p, src, f, temps, n_targets, gram, column_counts, ln_z, mean, shifts));
+  if (rc) return rc;
+  if (n_used) *n_used = p.n_used_ll;
+  return ME_OK;
+}
+
 }  // namespace
 }  // namespace mbar
 }  // namespace me
@@ -376,6 +602,16 @@ int me_mbar_gram(me_engine *e, const double *f, const double *temps, int32_t n_t
   Source src;
   const int rc = src.from_engine(e);
   return rc ? rc : gram_common(src, f, temps, n_targets, gram, column_counts, ln_z, mean_e, n_used);
+}
+
+int me_mbar_gram_observables(me_engine *e, const double *f, const double *temps, int32_t n_targets, double *gram, double *column_counts,
+                             double *ln_z, double *mean, double *shifts, int64_t *n_used) {
+  Source src;
+  const int rc = src.from_engine(e);
+  if (rc) return rc;
+  if (src.columns.n_columns == 0)
+    return fail(e, ME_ERR_STATE, "no recorded observables: me_observable_samples_enable, then me_energy_samples_record");
+  return gram_observables_common(src, f, temps, n_targets, gram, column_counts, ln_z, mean, shifts, n_used);
 }
 
 int me_mbar_energy_shift(me_engine *e, double *shift) {
@@ -395,6 +631,15 @@ int me_mbar_gram_samples(int32_t device_id, const double *energies, const int32_
   Source src;
   const int rc = src.from_host(device_id, energies, rungs, n_samples, ladder_temps, n_rungs);
   return rc ? rc : src.finish(gram_common(src, f, temps, n_targets, gram, column_counts, ln_z, mean_e, n_used));
+}
+
+int me_mbar_gram_observables_samples(int32_t device_id, const double *energies, const int32_t *rungs, int64_t n_samples,
+                                     const double *ladder_temps, int32_t n_rungs, const double *observables, int32_t n_columns,
+                                     const double *f, const double *temps, int32_t n_targets, double *gram, double *column_counts,
+                                     double *ln_z, double *mean, double *shifts, int64_t *n_used) {
+  Source src;
+  const int rc = src.from_host(device_id, energies, rungs, n_samples, ladder_temps, n_rungs, observables, n_columns);
+  return rc ? rc : src.finish(gram_observables_common(src, f, temps, n_targets, gram, column_counts, ln_z, mean, shifts, n_used));
 }
 
 }  // extern "C"

@@ -312,38 +312,15 @@ hipError_t reweight_observables(Problem &p, const Source &src, const double *f, 
                                 double *var, double *cov, double *neff) {
   ME_MBAR_HIP(prepare(p, src, f));
   if (p.empty_rung >= 0) return hipSuccess;
-  const ObsColumns &oc = src.columns;
   Work &w = p.w;
-  const MbarSamples &sm = p.sm;
-  hipStream_t stream = p.stream;
-  const double n_used = p.n_used;
-  const int n_rungs = p.n_rungs, n_blocks = blocks_of(sm.n_samples), nq_all = oc.n_columns;
-  const long long n_tiles = tiles_of(sm.n_samples), n_padded = n_tiles * kTile;
-  const size_t cells = (size_t)n_temps * nq_all;
+  const size_t cells = (size_t)n_temps * src.columns.n_columns;
   std::vector<double> inv;
-  DeviceBuffer d, partials;
-  ME_MBAR_HIP(d.resize((size_t)n_padded * sizeof(double)));
-  ME_MBAR_HIP(partials.resize((size_t)n_blocks * kObsTargets * sizeof(TargetState)));
+  ObsScratch scratch;
   ME_MBAR_HIP(upload_targets(p, temps, n_temps, 3 * cells + (size_t)n_temps, inv));
-  double *o_mean = w.out.get<double>(), *o_var = o_mean + cells, *o_cov = o_var + cells, *o_neff = o_cov + cells;
-  hipLaunchKernelGGL(k_mbar_log_denominator, dim3(n_blocks), dim3(kThreads), 0, stream, sm.energies, sm.n_samples, n_padded, n_rungs,
-                     w.table.get<const double>(), d.get<double>());
-  for (int t0 = 0; t0 < n_temps; t0 += kObsTargets) {
-    const int nt = std::min(kObsTargets, n_temps - t0);
-    for (int q0 = 0; q0 < nq_all; q0 += kObsCols) {
-      const int nq = std::min(kObsCols, nq_all - q0);
-      const size_t cell = (size_t)t0 * nq_all + q0;
-      hipLaunchKernelGGL(k_mbar_reweight_obs, dim3(n_blocks), dim3(kThreads), 0, stream, sm.energies, d.get<const double>(),
-                         oc.data + (size_t)q0 * oc.column_stride, sm.n_samples, oc.n_chains, oc.record_stride, oc.column_stride, nq,
-                         w.inv_temps.get<const double>() + t0, nt, n_tiles, partials.get<TargetState>());
-      hipLaunchKernelGGL(k_mbar_reweight_obs_finish, dim3(nt), dim3(kThreads), 0, stream, partials.get<const TargetState>(), n_blocks, nq,
-                         nq_all, n_used, q0 == 0 ? 1 : 0, o_mean + cell, o_var + cell, o_cov + cell, o_neff + t0);
-    }
-  }
-  ME_MBAR_HIP(hipGetLastError());
+  ME_MBAR_HIP(reweight_observables_enqueue(p, p.sm, src.columns, w.inv_temps.get<const double>(), n_temps, scratch, w.out.get<double>()));
   std::vector<double> out(3 * cells + (size_t)n_temps);
-  ME_MBAR_HIP(hipMemcpyAsync(out.data(), w.out.get(), out.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-  ME_MBAR_HIP(hipStreamSynchronize(stream));      // (also: `inv`, `d` and `partials` leave scope)
+  ME_MBAR_HIP(hipMemcpyAsync(out.data(), w.out.get(), out.size() * sizeof(double), hipMemcpyDeviceToHost, p.stream));
+  ME_MBAR_HIP(hipStreamSynchronize(p.stream));    // (also: `inv` and `scratch` leave scope)
   if (mean) std::copy(out.begin(), out.begin() + cells, mean);
   if (var) std::copy(out.begin() + cells, out.begin() + 2 * cells, var);
   if (cov) std::copy(out.begin() + 2 * cells, out.begin() + 3 * cells, cov);
@@ -363,6 +340,32 @@ int reweight_observables_common(const Source &src, const double *f, const double
 int catalogue_size(const me_engine *e) { return e->d + e->nobs + e->n_terms; }
 
 }  // namespace
+
+hipError_t reweight_observables_enqueue(Problem &p, const MbarSamples &sm, const ObsColumns &oc, const double *inv_temps, int n_temps,
+                                        ObsScratch &scratch, double *out) {
+  hipStream_t stream = p.stream;
+  const int n_rungs = p.n_rungs, n_blocks = blocks_of(sm.n_samples), nq_all = oc.n_columns;
+  const long long n_tiles = tiles_of(sm.n_samples), n_padded = n_tiles * kTile;
+  const size_t cells = (size_t)n_temps * nq_all;
+  ME_MBAR_HIP(scratch.d.resize((size_t)n_padded * sizeof(double)));
+  ME_MBAR_HIP(scratch.partials.resize((size_t)n_blocks * kObsTargets * sizeof(TargetState)));
+  double *o_mean = out, *o_var = o_mean + cells, *o_cov = o_var + cells, *o_neff = o_cov + cells;
+  hipLaunchKernelGGL(k_mbar_log_denominator, dim3(n_blocks), dim3(kThreads), 0, stream, sm.energies, sm.n_samples, n_padded, n_rungs,
+                     p.w.table.get<const double>(), scratch.d.get<double>());
+  for (int t0 = 0; t0 < n_temps; t0 += kObsTargets) {
+    const int nt = std::min(kObsTargets, n_temps - t0);
+    for (int q0 = 0; q0 < nq_all; q0 += kObsCols) {
+      const int nq = std::min(kObsCols, nq_all - q0);
+      const size_t cell = (size_t)t0 * nq_all + q0;
+      hipLaunchKernelGGL(k_mbar_reweight_obs, dim3(n_blocks), dim3(kThreads), 0, stream, sm.energies, scratch.d.get<const double>(),
+                         oc.data + (size_t)q0 * oc.column_stride, sm.n_samples, oc.n_chains, oc.record_stride, oc.column_stride, nq,
+                         inv_temps + t0, nt, n_tiles, scratch.partials.get<TargetState>());
+      hipLaunchKernelGGL(k_mbar_reweight_obs_finish, dim3(nt), dim3(kThreads), 0, stream, scratch.partials.get<const TargetState>(),
+                         n_blocks, nq, nq_all, p.n_used, q0 == 0 ? 1 : 0, o_mean + cell, o_var + cell, o_cov + cell, o_neff + t0);
+    }
+  }
+  return hipGetLastError();
+}
 
 // me_energy_samples_record's second kernel: row `row` of the observable store (the caller has checked that it exists)
 hipError_t observable_record_enqueue(me_engine *e, long long row) {

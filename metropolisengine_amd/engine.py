@@ -793,6 +793,25 @@ class MetropolisEngine:
         f = self._ladder_f(f, finite=False)
         return statistics._reweight_observables(self._lib.me_mbar_reweight_observables, (self._handle,), f, temps, names)
 
+    def observable_uncertainties(self, temps, f=None, inefficiency=1.0):
+        """Asymptotic standard errors of :meth:`reweight_observables`' means (``me_mbar_gram_observables``: one further pass
+        over the recorded samples on the matrix cores): ``{"temps", "names", "mean", "d_mean", "mean_cov", "ln_z", "d_ln_z",
+        "n_samples"}``, see :func:`metropolisengine_amd.statistics.mbar_observable_uncertainties`.  ``f``: the free energies of
+        :meth:`ladder_free_energies` (solved with the defaults when ``None``).  ``inefficiency``: the statistical inefficiency
+        of the recorded series, a scalar or one entry per recorded column (finite, ``>= 1``).  ``ValueError`` for invalid
+        ``temps`` or ``inefficiency`` and without an observable store; raises without a ladder or without records."""
+        from . import statistics
+        temps = statistics.validate_mbar_temps(temps)
+        names = self.recorded_observables
+        if not names:
+            raise ValueError("no observable store: call record_observables first")
+        g = statistics.validate_mbar_observable_inefficiency(inefficiency, len(names))
+        if f is None:
+            f = self.ladder_free_energies()["f"]
+        f = self._ladder_f(f, finite=True)
+        k = max(f.size, 1)      # (the ladder's rungs; without a ladder the library refuses before it writes)
+        return statistics._observable_uncertainties(self._lib.me_mbar_gram_observables, (self._handle,), k, f, temps, names, g)
+
     # ------------------------------------------------------------------ scalar temperature and population annealing
     def set_temp(self, temp):
         """Change the scalar temperature of the running engine (``me_set_temperature``); the next step uses it, so a schedule

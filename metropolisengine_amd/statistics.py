@@ -354,6 +354,81 @@ def mbar_uncertainties(energies, rungs, temps, f, targets=None, inefficiency=1.0
                           lambda: e[np.isfinite(e)].min() - 1.0)
 
 
+def validate_mbar_observable_inefficiency(inefficiency, n_columns):
+    """The statistical inefficiencies of ``n_columns`` observables as a ``(n_columns,)`` float64 array: a scalar (every
+    column's) or one entry per column, each validated like :func:`validate_mbar_inefficiency` (``ValueError`` otherwise)."""
+    g = np.asarray(inefficiency, dtype=np.float64)
+    if g.ndim > 1 or (g.ndim == 1 and g.shape != (n_columns,)):
+        raise ValueError("inefficiency must be a scalar or hold one entry per observable column (%d)" % n_columns)
+    return np.array([validate_mbar_inefficiency(v) for v in np.broadcast_to(g, (n_columns,))])
+
+
+def _observable_uncertainty_result(gram, column_counts, n_rungs, targets, names, ln_z, mean, shifts, n_used, inefficiency):
+    """The dictionary of :func:`mbar_observable_uncertainties` from what ``me_mbar_gram_observables`` returns.  Targets are taken
+    in the chunks the device used (each with the ladder columns), each chunk on those of its columns whose entries of ``gram``
+    are finite: a poisoned observable column (its mean is not finite) drops out of the algebra and gets NaN."""
+    k, q, n_targets = n_rungs, len(names), targets.size
+    per = (MBAR_GRAM_MAX_COLUMNS - k) // (1 + q)
+    d_ln_z = np.zeros(n_targets)
+    d_mean, mean_cov = np.full((n_targets, q), np.nan), np.full((n_targets, q, q), np.nan)
+    root_g = np.sqrt(inefficiency)
+    for t0 in range(0, n_targets, per):
+        nt = min(per, n_targets - t0)
+        idx = np.concatenate([np.arange(k), k + (1 + q) * t0 + np.arange((1 + q) * nt)]).astype(np.intp)
+        idx = idx[np.isfinite(np.diag(gram)[idx])]
+        at = {int(c): i for i, c in enumerate(idx)}      # column of gram -> row of theta
+        theta = mbar_theta(gram[np.ix_(idx, idx)], column_counts[idx])
+        for t in range(t0, t0 + nt):
+            a = at[k + (1 + q) * t]
+            d_ln_z[t] = np.sqrt(max(theta[a, a] + theta[0, 0] - 2.0 * theta[a, 0], 0.0) * inefficiency.max())
+            own = [c for c in range(q) if k + (1 + q) * t + 1 + c in at]
+            rows = np.array([at[k + (1 + q) * t + 1 + c] for c in own], dtype=np.intp)
+            if rows.size == 0:
+                continue
+            own = np.array(own, dtype=np.intp)
+            # (column A holds A_q - S_q, whose mean is mean_tq - S_q; the shift drops out of the covariance)
+            scale = (mean[t, own] - shifts[own]) * root_g[own]
+            cov = theta[np.ix_(rows, rows)] + theta[a, a] - theta[rows, a][:, None] - theta[rows, a][None, :]
+            mean_cov[np.ix_([t], own, own)] = scale[:, None] * scale[None, :] * cov
+            d_mean[t, own] = np.abs(scale) * np.sqrt(np.clip(np.diag(cov), 0.0, None))
+    return {"temps": targets, "names": tuple(names), "mean": mean, "d_mean": d_mean, "mean_cov": mean_cov, "ln_z": ln_z,
+            "d_ln_z": d_ln_z, "n_samples": int(n_used)}
+
+
+def _observable_uncertainties(fn, lead, n_rungs, f, targets, names, inefficiency):
+    q = len(names)
+    c = n_rungs + targets.size * (1 + q)
+    gram, counts = np.zeros((c, c)), np.zeros(c)
+    ln_z, mean, shifts = np.zeros(targets.size), np.zeros((targets.size, q)), np.zeros(q)
+    n_used = ctypes.c_int64()
+    _call(fn, lead, _capi.double_ptr(f), _capi.double_ptr(targets), targets.size, _capi.double_ptr(gram), _capi.double_ptr(counts),
+          _capi.double_ptr(ln_z), _capi.double_ptr(mean), _capi.double_ptr(shifts), ctypes.byref(n_used))
+    return _observable_uncertainty_result(gram, counts, n_rungs, targets, names, ln_z, mean, shifts, n_used.value, inefficiency)
+
+
+def mbar_observable_uncertainties(energies, rungs, temps, f, targets, observables, inefficiency=1.0, device=0):
+    """Asymptotic standard errors of the reweighted means of :func:`mbar_reweight_observables`
+    (``me_mbar_gram_observables_samples``: the Gram matrix of the MBAR weight matrix with one observable-weighted column per
+    target and column, on the matrix cores; the algebra of Shirts & Chodera 2008, eqs. 8, 12-15 and D8, runs here in float64;
+    the engine form is ``MetropolisEngine.observable_uncertainties``).  Returns ``{"temps", "names", "mean" (T, Q), "d_mean" (T,
+    Q), "mean_cov" (T, Q, Q), "ln_z", "d_ln_z", "n_samples"}``: ``mean`` is :func:`mbar_reweight_observables`' (bit for bit when
+    every energy is finite), ``d_mean`` its standard error and ``mean_cov[t]`` the covariance matrix of the Q ESTIMATES at
+    target ``t`` -- what the error bar of a ratio or a difference of two observables needs; ``d_mean ** 2`` is its diagonal.
+
+    The formula assumes INDEPENDENT samples: pass the statistical inefficiency ``g >= 1`` of the series as ``inefficiency``, a
+    scalar or one entry per column; ``d_mean[:, q]`` is multiplied by ``sqrt(g_q)``, ``mean_cov[:, q, r]`` by ``sqrt(g_q
+    g_r)`` and ``d_ln_z`` by the square root of the largest.  A non-finite value of column ``q`` in a used sample gives NaN in
+    ``mean[:, q]``, ``d_mean[:, q]`` and row and column ``q`` of ``mean_cov``, and nothing else."""
+    e, r, t = validate_mbar_samples(energies, rungs, temps)
+    targets = validate_mbar_temps(targets, "targets")
+    f = validate_mbar_f(f, t.size)
+    a = validate_mbar_observables(observables, e.size)
+    g = validate_mbar_observable_inefficiency(inefficiency, a.shape[0])
+    lead = _host_samples(device, e, r, t) + (_capi.double_ptr(a), a.shape[0])
+    return _observable_uncertainties(_capi.load().me_mbar_gram_observables_samples, lead, t.size, f, targets,
+                                     tuple(range(a.shape[0])), g)
+
+
 def get_equilibration_points(df, device=None):
     """Per column ``[t0, g, Neff_max]``; constant columns are skipped and complex columns split into ``_real`` /
     ``_imag`` (statistics.py:25-48).  With ``device`` set, all columns go to the GPU in one batch."""

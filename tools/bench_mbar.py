@@ -4,6 +4,8 @@
     python tools/bench_mbar.py --one-solve 16       (a single solve, for a kernel trace around it)
     python tools/bench_mbar.py --gram               (the Gram pass of the asymptotic error bars, profiles/mbar_uncertainty.txt)
     python tools/bench_mbar.py --observables        (reweighting of recorded observables: whole-call time beside the energy-only call)
+    python tools/bench_mbar.py --observable-gram    (the Gram pass with observable columns beside me_mbar_gram at an equal
+                                                     column count, profiles/mbar_observable_uncertainty.txt)
 
 Per ladder size K: synthetic energies of a 16-dimensional quadratic form (E / T Gamma(8) distributed) on T_k = 0.5 r^k with
 r chosen so that the ladder spans the same range for every K, injected with set_energy_samples; one warm-up solve, then a
@@ -126,6 +128,61 @@ def time_observables(k, log2_chains, records, n_targets=8, columns=(1, 4, 16)):
                                       100 * traffic / (1e-3 * ms) / HBM_RATE, 1e-12 * HBM_RATE), flush=True)
 
 
+def time_observable_gram(k, log2_chains, records, n_targets=8, columns=(1, 4, 16)):
+    """me_mbar_gram_observables (csrc/me_mbar_cov.hip) for Q recorded columns at ``n_targets`` temperatures beside me_mbar_gram
+    with as many targets as give the same number of target columns, (1 + Q) n_targets / 2, on the same samples in the same
+    run.  Both are whole calls (counting pass, reweighting of the targets, the Gram launches of every chunk, the copy of G);
+    the observable form's call also holds the reweighting of the observables that supplies its normalising means, which is
+    timed alone beside it (me_mbar_reweight_observables, a whole call too).  Columns are counted per launch: every chunk of
+    targets carries the K ladder columns."""
+    import ctypes
+    eng, _ = loaded_engine(k, log2_chains, records)
+    n = records << log2_chains
+    f = eng.ladder_free_energies(tol=1e-8)["f"]
+    dp = ctypes.POINTER(ctypes.c_double)
+    targets = np.geomspace(0.5, 3.0, n_targets)
+    energies = eng.energy_samples()
+
+    def best(call, repeats=3):
+        call()                                                  # warm-up: allocations, code objects
+        times = []
+        for _ in range(repeats):
+            t0 = time.perf_counter()
+            call()
+            times.append(time.perf_counter() - t0)
+        return 1e3 * min(times), 1e3 * max(times)
+
+    def launched(per_target, nt):
+        per_chunk = (128 - k) // per_target
+        return [k + per_target * min(per_chunk, nt - t0) for t0 in range(0, nt, per_chunk)]
+
+    print("K = %d, %d samples, %d targets" % (k, n, n_targets), flush=True)
+    for q in columns:
+        eng.record_observables([j % 4 for j in range(q)])       # (one real parameter: a catalogue of 4 entries, duplicates
+        eng.set_energy_samples(energies)                        # allowed; the values are set below)
+        scale = 1.0 + 0.125 * np.arange(q)
+        eng.set_observable_samples(energies[:, None, :] * scale[None, :, None])
+        c = k + n_targets * (1 + q)
+        gram, counts = np.zeros((c, c)), np.zeros(c)
+        obs_ms, obs_max = best(lambda: eng._check(eng._lib.me_mbar_gram_observables(
+            eng._handle, f.ctypes.data_as(dp), targets.ctypes.data_as(dp), n_targets, gram.ctypes.data_as(dp), counts.ctypes.data_as(dp),
+            None, None, None, None)))
+        rw_ms, _ = best(lambda: eng.reweight_observables(targets, f))
+        nt_e = max(1, (n_targets * (1 + q) + 1) // 2)
+        targets_e = np.geomspace(0.5, 3.0, nt_e)
+        ce = k + 2 * nt_e
+        gram_e, counts_e = np.zeros((ce, ce)), np.zeros(ce)
+        e_ms, e_max = best(lambda: eng._check(eng._lib.me_mbar_gram(
+            eng._handle, f.ctypes.data_as(dp), targets_e.ctypes.data_as(dp), nt_e, gram_e.ctypes.data_as(dp), counts_e.ctypes.data_as(dp),
+            None, None, None)))
+        cols_o, cols_e = launched(1 + q, n_targets), launched(2, nt_e)
+        print("    Q = %2d: me_mbar_gram_observables %.3f ms (slowest of 3: %.3f), launches of %s columns; of that the observables' "
+              "reweighting alone %.3f ms; me_mbar_gram with %d targets %.3f ms (slowest of 3: %.3f), launches of %s columns; ratio "
+              "of the times %.2f, of the launched columns %.2f, of their squares %.2f"
+              % (q, obs_ms, obs_max, cols_o, rw_ms, nt_e, e_ms, e_max, cols_e, obs_ms / e_ms, sum(cols_o) / sum(cols_e),
+                 sum(x * x for x in cols_o) / sum(x * x for x in cols_e)), flush=True)
+
+
 def time_reference(k, log2_samples):
     n = 1 << log2_samples
     temps = ladder(k)
@@ -167,7 +224,12 @@ if __name__ == "__main__":
     ap.add_argument("--one-solve", type=int, default=0)
     ap.add_argument("--gram", action="store_true")
     ap.add_argument("--observables", action="store_true")
+    ap.add_argument("--observable-gram", action="store_true")
     cli = ap.parse_args()
+    if cli.observable_gram:
+        for k in cli.rungs:
+            time_observable_gram(k, cli.log2_chains, cli.records)
+        sys.exit(0)
     if cli.observables:
         time_observables(8, cli.log2_chains, cli.records)
         sys.exit(0)
