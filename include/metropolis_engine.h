@@ -456,8 +456,27 @@ int me_mbar_energy_shift(me_engine *engine, double *shift);
  *                       fixed order.  Errors as for me_mbar_gram, and ME_ERR_INVALID for n_targets < 1, ME_ERR_STATE without an
  *                       observable store.
  *   me_mbar_gram_observables_samples   the same on host arrays; observables is [n_columns][n_samples], 1 <= n_columns <=
- *                       ME_MAX_RECORDED_OBSERVABLES (ME_ERR_INVALID otherwise). */
+ *                       ME_MAX_RECORDED_OBSERVABLES (ME_ERR_INVALID otherwise).
+ *   me_mbar_histogram          the reweighted histogram of one quantity A over the recorded samples at each of the n target
+ *                       temperatures (finite, > 0), with the normalised weights w of me_mbar_reweight (sum over the used
+ *                       samples = 1; a sample is used when its ENERGY is finite; csrc/me_mbar_hist.hip has the definition).
+ *                       column >= 0: the recorded observable column (ME_ERR_STATE without an observable store, ME_ERR_INVALID
+ *                       beyond the recorded columns); column = -1: the energy itself, which needs the energy store only.
+ *                       edges[n_bins + 1] finite and strictly increasing, any spacing, 1 <= n_bins <= ME_MAX_HISTOGRAM_BINS
+ *                       (ME_ERR_INVALID otherwise).  Every used sample falls into exactly one of n_bins + 3 slots: bin b,
+ *                       edges[b] <= A < edges[b + 1] (half-open everywhere); slot n_bins, A < edges[0] (-inf included); slot
+ *                       n_bins + 1, A >= edges[n_bins] (+inf included: a value ON the last edge lies above); slot n_bins + 2,
+ *                       A is NaN.  mass is [n][n_bins + 3], the sum of w per slot, divided by the total over all slots so that a
+ *                       row sums to 1; counts [n_bins + 3] the used samples per slot (the same at every temperature);
+ *                       neff_fraction [n] as me_mbar_reweight's.  Any output may be NULL.  A slot without a sample has mass
+ *                       exactly 0.  No floating-point atomics: all sums have a fixed order, and a mass is bit for bit the same
+ *                       run to run, whether its temperature is asked for alone or among any number of others, and through
+ *                       me_mbar_histogram_samples on the same samples in the same order.  The free-energy profile is F(A; T) =
+ *                       -T ln(mass / bin width).  Errors otherwise as for me_mbar_reweight.
+ *   me_mbar_histogram_samples  the same kernels on host arrays, like me_mbar_reweight_samples; values[n_samples] holds A of
+ *                       every sample (pass the energies for an energy histogram). */
 #define ME_MAX_RECORDED_OBSERVABLES 16
+#define ME_MAX_HISTOGRAM_BINS 256
 int me_observable_samples_enable(me_engine *engine, const int32_t *indices, int32_t n_observables);
 int me_observable_samples_info(me_engine *engine, int32_t *n_observables, int32_t *indices);
 int me_observable_samples_get(me_engine *engine, int64_t record_begin, int64_t n_records, double *dst);
@@ -474,6 +493,12 @@ int me_mbar_gram_observables_samples(int32_t device_id, const double *energies, 
                                      const double *ladder_temps, int32_t n_rungs, const double *observables, int32_t n_columns,
                                      const double *f, const double *temps, int32_t n_targets, double *gram,
                                      double *column_counts, double *ln_z, double *mean, double *shifts, int64_t *n_used);
+int me_mbar_histogram(me_engine *engine, const double *f, const double *temps, int32_t n, int32_t column, const double *edges,
+                      int32_t n_bins, double *mass, int64_t *counts, double *neff_fraction);
+int me_mbar_histogram_samples(int32_t device_id, const double *energies, const int32_t *rungs, int64_t n_samples,
+                              const double *ladder_temps, int32_t n_rungs, const double *f, const double *temps, int32_t n,
+                              const double *values, const double *edges, int32_t n_bins, double *mass, int64_t *counts,
+                              double *neff_fraction);
 
 /* Text of the last error on this engine (or of the last failed me_create when engine is NULL). */
 int me_last_error(me_engine *engine, char *buf, size_t buf_bytes);

@@ -1,8 +1,8 @@
-// What the MBAR units share (me_mbar.hip: samples, solve, reweighting; me_mbar_cov.hip: the Gram matrix of the weight
-// matrix for the asymptotic covariance; me_mbar_obs.hip: recorded observables and their reweighting): the tile policy, the
-// device table of a ladder, the per-sample sums, and the host scaffolding of an entry point, which me_mbar.hip defines: where
-// the samples come from (Source), the prepared problem (Problem, prepare) and the argument checks.  Private to the host side,
-// like me_engine.h.
+// What the MBAR units share (me_mbar.hip: samples, solve, reweighting; me_mbar_cov.hip: the Gram matrix of the weight matrix
+// for the asymptotic covariance; me_mbar_obs.hip: recorded observables and their reweighting; me_mbar_hist.hip: reweighted
+// histograms along an observable): the tile policy, the device table of a ladder, the per-sample sums, and the host
+// scaffolding of an entry point, which me_mbar.hip defines: where the samples come from (Source), the prepared problem
+// (Problem, prepare) and the argument checks.  Private to the host side, like me_engine.h.
 #pragma once
 
 #include <algorithm>
@@ -138,6 +138,9 @@ int mbar_check_temps(me_engine *e, const double *temps, int n, const char *what)
 struct ObsScratch {
   DeviceBuffer d, partials;
 };
+// Enqueues d_n = m_n + ln s_n of every sample of `sm` into `d`, sized here to whole tiles: NaN for a sample whose energy is not
+// finite and for the padding behind the last sample.  Does not wait: `d` is the caller's to keep.
+hipError_t log_denominator_enqueue(Problem &p, const MbarSamples &sm, DeviceBuffer &d);
 // Enqueues the reweighting of the columns `oc` of `sm` (the problem's samples, or the used ones of them packed) to the n_temps
 // temperatures whose 1 / T_t are on the device at inv_temps: afterwards out = [mean | var | cov_energy][target][column], then
 // neff_fraction[target], 3 n_temps Q + n_temps doubles of device memory.  Does not wait: `scratch` is the caller's to keep until

@@ -341,17 +341,23 @@ int catalogue_size(const me_engine *e) { return e->d + e->nobs + e->n_terms; }
 
 }  // namespace
 
+hipError_t log_denominator_enqueue(Problem &p, const MbarSamples &sm, DeviceBuffer &d) {
+  const long long n_padded = tiles_of(sm.n_samples) * kTile;
+  ME_MBAR_HIP(d.resize((size_t)n_padded * sizeof(double)));
+  hipLaunchKernelGGL(k_mbar_log_denominator, dim3(blocks_of(sm.n_samples)), dim3(kThreads), 0, p.stream, sm.energies, sm.n_samples,
+                     n_padded, p.n_rungs, p.w.table.get<const double>(), d.get<double>());
+  return hipGetLastError();
+}
+
 hipError_t reweight_observables_enqueue(Problem &p, const MbarSamples &sm, const ObsColumns &oc, const double *inv_temps, int n_temps,
                                         ObsScratch &scratch, double *out) {
   hipStream_t stream = p.stream;
-  const int n_rungs = p.n_rungs, n_blocks = blocks_of(sm.n_samples), nq_all = oc.n_columns;
-  const long long n_tiles = tiles_of(sm.n_samples), n_padded = n_tiles * kTile;
+  const int n_blocks = blocks_of(sm.n_samples), nq_all = oc.n_columns;
+  const long long n_tiles = tiles_of(sm.n_samples);
   const size_t cells = (size_t)n_temps * nq_all;
-  ME_MBAR_HIP(scratch.d.resize((size_t)n_padded * sizeof(double)));
+  ME_MBAR_HIP(log_denominator_enqueue(p, sm, scratch.d));
   ME_MBAR_HIP(scratch.partials.resize((size_t)n_blocks * kObsTargets * sizeof(TargetState)));
   double *o_mean = out, *o_var = o_mean + cells, *o_cov = o_var + cells, *o_neff = o_cov + cells;
-  hipLaunchKernelGGL(k_mbar_log_denominator, dim3(n_blocks), dim3(kThreads), 0, stream, sm.energies, sm.n_samples, n_padded, n_rungs,
-                     p.w.table.get<const double>(), scratch.d.get<double>());
   for (int t0 = 0; t0 < n_temps; t0 += kObsTargets) {
     const int nt = std::min(kObsTargets, n_temps - t0);
     for (int q0 = 0; q0 < nq_all; q0 += kObsCols) {

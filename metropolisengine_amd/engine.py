@@ -793,6 +793,48 @@ class MetropolisEngine:
         f = self._ladder_f(f, finite=False)
         return statistics._reweight_observables(self._lib.me_mbar_reweight_observables, (self._handle,), f, temps, names)
 
+    def free_energy_profile(self, which, edges, temps, f=None):
+        """The reweighted histogram of one recorded quantity and the free-energy profile ``F(A; T) = -T ln p(A; T)`` along it at
+        each temperature of ``temps`` (``me_mbar_histogram``, on the device: the samples stay there).  ``which``: a name of
+        :attr:`recorded_observables`, an index into the recorded columns, or ``"energy"`` (the recorded energies themselves,
+        which need no observable store).  ``edges``: 2 to 257 finite, strictly increasing bin edges of any spacing.  ``f``: the
+        free energies of :meth:`ladder_free_energies` (solved with the defaults when ``None``).
+
+        Every sample with a finite energy falls into exactly one slot: bin ``b`` when ``edges[b] <= A < edges[b + 1]``
+        (half-open everywhere), *below*, *above* (``A >= edges[-1]``: a value equal to the LAST edge is above, unlike
+        ``np.histogram``, which closes its last bin) or *not a number*.  Returns ``{"temps", "name", "edges", "centers",
+        "widths", "mass", "below", "above", "not_a_number", "density", "free_energy", "counts", "counts_outside",
+        "neff_fraction"}``, see :func:`metropolisengine_amd.statistics.mbar_free_energy_profile`.  Bitwise reproducible, and
+        a temperature's row does not depend on which others are asked for.  ``ValueError`` for bad edges, an unknown name, an
+        index outside the recorded columns and empty, non-finite or non-positive ``temps``; raises without a ladder or
+        without records."""
+        from . import statistics
+        temps = statistics.validate_mbar_temps(temps)
+        edges = statistics.validate_histogram_edges(edges)
+        if isinstance(which, str) and which == "energy":
+            column, name = -1, "energy"
+        else:
+            names = self.recorded_observables
+            if not names:
+                raise ValueError("no observable store: call record_observables first")
+            if isinstance(which, str):
+                if which not in names:
+                    raise ValueError("unknown recorded observable %r; this engine records %s" % (which, ", ".join(names)))
+                column = names.index(which)
+            elif isinstance(which, (int, np.integer)) and not isinstance(which, bool):
+                if not 0 <= int(which) < len(names):
+                    raise ValueError("column %d outside the %d recorded columns" % (int(which), len(names)))
+                column = int(which)
+            else:
+                raise ValueError("the quantity is named by str or int, got %r" % (which,))
+            name = names[column]
+        if f is None:
+            f = self.ladder_free_energies()["f"]
+        f = self._ladder_f(f, finite=False)
+        out = statistics._free_energy_profile(self._lib.me_mbar_histogram, (self._handle,), f, temps, (column,), edges)
+        out["name"] = name
+        return out
+
     def observable_uncertainties(self, temps, f=None, inefficiency=1.0):
         """Asymptotic standard errors of :meth:`reweight_observables`' means (``me_mbar_gram_observables``: one further pass
         over the recorded samples on the matrix cores): ``{"temps", "names", "mean", "d_mean", "mean_cov", "ln_z", "d_ln_z",

@@ -262,6 +262,71 @@ def mbar_reweight_observables(energies, rungs, temps, f, targets, observables, d
                                  tuple(range(a.shape[0])))
 
 
+MBAR_MAX_HISTOGRAM_BINS = 256   # bins of a reweighted histogram (ME_MAX_HISTOGRAM_BINS)
+
+
+def validate_histogram_edges(edges):
+    """Bin edges as a contiguous 1-D float64 array: between 2 and 257 of them (1 to 256 bins), finite and strictly
+    increasing, any spacing (``ValueError`` otherwise)."""
+    e = np.ascontiguousarray(np.asarray(edges, dtype=np.float64))
+    if e.ndim != 1 or not 1 <= e.size - 1 <= MBAR_MAX_HISTOGRAM_BINS:
+        raise ValueError("edges must be a 1-D sequence of 2 to %d entries (1 to %d bins)"
+                         % (MBAR_MAX_HISTOGRAM_BINS + 1, MBAR_MAX_HISTOGRAM_BINS))
+    if not np.all(np.isfinite(e)) or not np.all(np.diff(e) > 0):
+        raise ValueError("edges must be finite and strictly increasing")
+    return e
+
+
+def _profile_result(temps, edges, mass, counts, neff):
+    b = edges.size - 1
+    widths = np.diff(edges)
+    density = mass[:, :b] / widths[None, :]
+    with np.errstate(divide="ignore"):
+        free_energy = -temps[:, None] * np.log(density)
+    free_energy[mass[:, :b] == 0] = np.inf
+    return {"temps": temps, "edges": edges, "centers": 0.5 * (edges[:-1] + edges[1:]), "widths": widths,
+            "mass": mass[:, :b].copy(), "below": mass[:, b].copy(), "above": mass[:, b + 1].copy(),
+            "not_a_number": mass[:, b + 2].copy(), "density": density, "free_energy": free_energy,
+            "counts": counts[:b].copy(), "counts_outside": counts[b:].copy(), "neff_fraction": neff}
+
+
+def _free_energy_profile(fn, lead, f, targets, middle, edges):
+    """``middle``: the arguments between the target count and the edges (the engine's column; the host form's values)."""
+    b = edges.size - 1
+    mass, counts, neff = np.zeros((targets.size, b + 3)), np.zeros(b + 3, dtype=np.int64), np.zeros(targets.size)
+    _call(fn, lead, _capi.double_ptr(f), _capi.double_ptr(targets), targets.size, *middle, _capi.double_ptr(edges), b,
+          _capi.double_ptr(mass), _capi.int64_ptr(counts), _capi.double_ptr(neff))
+    return _profile_result(targets, edges, mass, counts, neff)
+
+
+def mbar_free_energy_profile(energies, rungs, temps, f, targets, values, edges, device=0):
+    """The reweighted histogram of ``values`` (one value ``A`` per sample, in the order of ``energies``) and the free-energy
+    profile ``F(A; T) = -T ln p(A; T)`` along it at the temperatures ``targets``, from the samples of a ladder (``temps``,
+    free energies ``f`` of :func:`mbar_free_energies`) on the host (``me_mbar_histogram_samples``; the engine form is
+    ``MetropolisEngine.free_energy_profile``).  ``edges``: 2 to 257 finite, strictly increasing bin edges of any spacing.
+
+    Every sample with a finite ENERGY falls into exactly one slot: bin ``b`` when ``edges[b] <= A < edges[b + 1]`` (half-open
+    everywhere), *below* when ``A < edges[0]``, *above* when ``A >= edges[-1]``, *not a number* when ``A`` is NaN -- the rule
+    ``np.searchsorted(edges, A, side="right") - 1``.  A value equal to the LAST edge is *above*: unlike ``np.histogram``, the
+    last bin is not closed on the right.
+
+    Returns ``{"temps", "edges", "centers", "widths", "mass", "below", "above", "not_a_number", "density", "free_energy",
+    "counts", "counts_outside", "neff_fraction"}``: ``mass`` ``(T, B)`` the reweighted probability of every bin, ``below``,
+    ``above`` and ``not_a_number`` ``(T,)`` that of the three outer slots (all of them together sum to 1), ``density = mass /
+    widths``, ``free_energy = -T ln density`` (``+inf`` where the mass is 0), ``counts`` ``(B,)`` the samples per bin and
+    ``counts_outside`` ``(3,)`` those below, above and not a number, ``neff_fraction`` as :func:`mbar_reweight`'s.  The sums
+    have a fixed order: bitwise reproducible, and a temperature's row does not depend on which others are asked for."""
+    e, r, t = validate_mbar_samples(energies, rungs, temps)
+    targets = validate_mbar_temps(targets, "targets")
+    f = validate_mbar_f(f, t.size)
+    edges = validate_histogram_edges(edges)
+    a = np.ascontiguousarray(np.asarray(values, dtype=np.float64).ravel())
+    if a.size != e.size:
+        raise ValueError("values needs one entry per sample (%d), got %d" % (e.size, a.size))
+    return _free_energy_profile(_capi.load().me_mbar_histogram_samples, _host_samples(device, e, r, t), f, targets,
+                                (_capi.double_ptr(a),), edges)
+
+
 MBAR_GRAM_MAX_COLUMNS = 128     # columns of the weight matrix per device pass (csrc/me_mbar_cov.hip)
 
 

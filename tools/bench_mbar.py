@@ -6,6 +6,8 @@
     python tools/bench_mbar.py --observables        (reweighting of recorded observables: whole-call time beside the energy-only call)
     python tools/bench_mbar.py --observable-gram    (the Gram pass with observable columns beside me_mbar_gram at an equal
                                                      column count, profiles/mbar_observable_uncertainty.txt)
+    python tools/bench_mbar.py --profile            (reweighted histograms along an observable beside the one-column observable
+                                                     reweighting, profiles/mbar_profile.txt)
 
 Per ladder size K: synthetic energies of a 16-dimensional quadratic form (E / T Gamma(8) distributed) on T_k = 0.5 r^k with
 r chosen so that the ladder spans the same range for every K, injected with set_energy_samples; one warm-up solve, then a
@@ -183,6 +185,51 @@ def time_observable_gram(k, log2_chains, records, n_targets=8, columns=(1, 4, 16
                  sum(x * x for x in cols_o) / sum(x * x for x in cols_e)), flush=True)
 
 
+def time_profile(k, log2_chains, records, n_targets=8, bins=(64, 256)):
+    """me_mbar_histogram (csrc/me_mbar_hist.hip) for one recorded column at ``n_targets`` temperatures, on two inputs: one
+    whose values all fall in ONE bin (a wavefront's 64 lanes share a slot: one match round and a butterfly per temperature)
+    and one where consecutive samples fall in 64 DIFFERENT bins (64 match rounds per item, every lane adds its own weight).
+    Beside them, on the same samples in the same run, me_mbar_reweight_observables with that one column and the energy-only
+    me_mbar_reweight.  All are whole calls (counting pass, table upload, allocations, every launch, the copy back and the
+    wait); the histogram's call holds me_mbar_reweight's kernels (they supply ln_z and neff_fraction), the pass that writes
+    d_n, and ceil(T / 4) passes that each read 24 bytes per sample."""
+    eng, _ = loaded_engine(k, log2_chains, records)
+    n = records << log2_chains
+    f = eng.ladder_free_energies(tol=1e-8)["f"]
+    targets = np.geomspace(0.5, 3.0, n_targets)
+
+    def best(call, repeats=3):
+        call()                                                  # warm-up: allocations, code objects
+        times = []
+        for _ in range(repeats):
+            t0 = time.perf_counter()
+            call()
+            times.append(time.perf_counter() - t0)
+        return 1e3 * min(times)
+
+    energy_ms = best(lambda: eng.reweight(targets, f))
+    energies = eng.energy_samples()
+    eng.record_observables([0])
+    eng.set_energy_samples(energies)
+    chain = np.arange(eng.n_chains)
+    inputs = (("every value in one bin", np.full(eng.n_chains, 0.5)),
+              ("consecutive samples in 64 different bins", (chain % 64) + 0.5))
+    print("K = %d, %d samples, %d targets: energy-only reweighting (me_mbar_reweight) %.3f ms" % (k, n, n_targets, energy_ms),
+          flush=True)
+    for label, row in inputs:
+        eng.set_observable_samples(np.broadcast_to(row[None, None, :], (records, 1, eng.n_chains)))
+        obs_ms = best(lambda: eng.reweight_observables(targets, f))
+        print("    %s: reweight_observables with this one column %.3f ms" % (label, obs_ms), flush=True)
+        for b in bins:
+            edges = np.linspace(0.0, float(b), b + 1)
+            out = eng.free_energy_profile(0, edges, targets, f)
+            assert int((out["counts"] > 0).sum()) == (1 if row.max() == row.min() else 64) and out["counts"].sum() == n
+            ms = best(lambda: eng.free_energy_profile(0, edges, targets, f))
+            print("        %3d bins: free_energy_profile %.3f ms = %.2f x the one-column observable reweighting, %.2f x energy-only; "
+                  "%.3e exponentials/s over the whole call" % (b, ms, ms / obs_ms, ms / energy_ms, n * n_targets / (1e-3 * ms)),
+                  flush=True)
+
+
 def time_reference(k, log2_samples):
     n = 1 << log2_samples
     temps = ladder(k)
@@ -225,7 +272,11 @@ if __name__ == "__main__":
     ap.add_argument("--gram", action="store_true")
     ap.add_argument("--observables", action="store_true")
     ap.add_argument("--observable-gram", action="store_true")
+    ap.add_argument("--profile", action="store_true")
     cli = ap.parse_args()
+    if cli.profile:
+        time_profile(8, cli.log2_chains, cli.records)
+        sys.exit(0)
     if cli.observable_gram:
         for k in cli.rungs:
             time_observable_gram(k, cli.log2_chains, cli.records)

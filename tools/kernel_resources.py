@@ -1,5 +1,7 @@
-"""Dev tool: per-kernel register / scratch / occupancy table for one (n_real, n_complex) kernel set.
+"""Dev tool: per-kernel register / scratch / occupancy table for one (n_real, n_complex) kernel set, or for one of the
+dimension-independent units.
     python tools/kernel_resources.py 16 0 [extra hipcc flags]
+    python tools/kernel_resources.py --unit me_mbar_hist [extra hipcc flags]
 """
 import os
 import re
@@ -7,12 +9,15 @@ import subprocess
 import sys
 
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-nr, nc = sys.argv[1], sys.argv[2]
-extra = sys.argv[3:]
-cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", os.path.join(root, "include"),
-       "-DME_NR=" + nr, "-DME_NC=" + nc, "-DME_DENSE=1", "-DME_PER_CHAIN=" + ("2" if int(nr) > 17 and int(nc) == 0 else ("0" if int(nr) > 32 else "1"))] + extra + \
-      ["-c", os.path.join(root, "metropolisengine_amd/csrc/me_kernels.hip"), "-o", "/tmp/kres.o",
-       "-Rpass-analysis=kernel-resource-usage"]
+if sys.argv[1] == "--unit":      # a dimension-independent unit, e.g. --unit me_mbar_hist
+    source, defines, extra = sys.argv[2] + ".hip", [], sys.argv[3:]
+else:
+    nr, nc = sys.argv[1], sys.argv[2]
+    source, extra = "me_kernels.hip", sys.argv[3:]
+    defines = ["-DME_NR=" + nr, "-DME_NC=" + nc, "-DME_DENSE=1",
+               "-DME_PER_CHAIN=" + ("2" if int(nr) > 17 and int(nc) == 0 else ("0" if int(nr) > 32 else "1"))]
+cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", os.path.join(root, "include")] + defines + extra + \
+      ["-c", os.path.join(root, "metropolisengine_amd/csrc", source), "-o", "/tmp/kres.o", "-Rpass-analysis=kernel-resource-usage"]
 out = subprocess.run(cmd, capture_output=True, text=True).stderr
 rows, cur = [], None
 for line in out.splitlines():
