@@ -219,6 +219,11 @@ int me_set_accept_stats(me_engine *engine, uint64_t accepted, uint64_t proposed)
  * torch tensor) so that the caller can all-reduce it with RCCL in place; it is enqueued on the engine's stream
  * and followed by a stream synchronise. */
 int me_pooled_moments_size(me_engine *engine, int64_t *n_doubles);
+/* Which first stage the reduction of ALL the engine's chains launches (for tests that must know which kernel they hold to
+ * account): matrix_core 1 = the Gram kernels of the engine's kernel set, 0 = the generic kernel; the chains it stages per
+ * tile (64 / 32 / 16); the rows of partial sums, one per workgroup (matrix_core with at most 32 augmented rows, generic)
+ * or per wavefront (matrix_core, 64 parameters). */
+int me_pooled_moments_geometry(me_engine *engine, int32_t *matrix_core, int32_t *tile_chains, int32_t *partial_rows);
 int me_pooled_moments(me_engine *engine, double *host_out, int64_t n_doubles);
 int me_pooled_moments_device(me_engine *engine, void *device_out, int64_t n_doubles);
 /* Split form that does not stall the engine's stream: _begin enqueues the reduction behind the work already queued and

@@ -83,6 +83,8 @@ SYMBOLS = {
     "me_set_counters": (ctypes.c_int, [_H, ctypes.c_uint64, ctypes.c_uint64]),
     "me_accept_stats": (ctypes.c_int, [_H, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]),
     "me_pooled_moments_size": (ctypes.c_int, [_H, ctypes.POINTER(ctypes.c_int64)]),
+    "me_pooled_moments_geometry": (ctypes.c_int, [_H, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                                  ctypes.POINTER(ctypes.c_int32)]),
     "me_pooled_moments": (ctypes.c_int, [_H, _dp, ctypes.c_int64]),
     "me_pooled_moments_device": (ctypes.c_int, [_H, ctypes.c_void_p, ctypes.c_int64]),
     "me_comm_unique_id": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t]),

@@ -1099,6 +1099,16 @@ int me_pooled_moments_size(me_engine *e, int64_t *n_doubles) {
   return ME_OK;
 }
 
+int me_pooled_moments_geometry(me_engine *e, int32_t *matrix_core, int32_t *tile_chains, int32_t *partial_rows) {
+  if (!e || !matrix_core || !tile_chains || !partial_rows) return ME_ERR_INVALID;
+  if (!e->pool.partials) return fail(e, ME_ERR_UNSUPPORTED, "pooled moments: dimension too large for the reduction kernel");
+  // what launch_pool_reduce does with these arguments: the kernel set's own first stage where it has one
+  *matrix_core = e->ks->pool_stage1 ? 1 : 0;
+  *tile_chains = e->ks->pool_stage1 ? 64 : pool_tile_chains(e->nr, e->nc, e->dtype);
+  *partial_rows = pool_reduce_blocks(e->n, e->nr, e->nc);
+  return ME_OK;
+}
+
 namespace {
 // Waits for `ev`, polling for the first two milliseconds.  hipEventSynchronize gives up its own active wait after a few
 // microseconds and blocks; the thread is then woken by an interrupt, and on a host that is otherwise idle (one OpenMP

@@ -5,7 +5,8 @@
 // read it back TRANSPOSED as MFMA operands -- lane l of v_mfma_f32_32x32x2_f32 holds A[row l&31][k = l>>5], i.e.
 // parameter l&31 of chain 2s + (l>>5); B's map is the mirror image, so A's fragment of block nb IS B's operand and only
 // the three lower blocks (0,0), (1,0), (1,1) are formed (96 MFMAs per tile).  fp32 products and sums inside a tile, fp64
-// across tiles -- the same numerics class as the generic kernel -- and the per-wavefront partial sums go to
+// across tiles -- the class whose forward-error bound DESIGN.md states under "Pooled moments: the criterion" and
+// tests/test_gpu_pooled_moments_conformance.py holds every stage-1 kernel to -- and the per-wavefront partial sums go to
 // partials[wavefront][entry] in the order k_pool_finish expects.  2^19 chains: 56 us (MFMA loop ~23, loads ~11, row sums
 // ~4, the rest LDS staging and the fp64 flush), against 237 us for the generic kernel.
 #pragma once

@@ -534,6 +534,13 @@ class MetropolisEngine:
         self._check(self._lib.me_pooled_moments(self._handle, _as_double_ptr(out), size.value))
         return out
 
+    def pooled_moments_geometry(self):
+        """(matrix_core, tile_chains, partial_rows) of the first stage :meth:`pooled_moments` launches: whether it is the
+        kernel set's Gram kernel, the chains it stages per tile, and its rows of partial sums."""
+        core, tile, rows = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+        self._check(self._lib.me_pooled_moments_geometry(self._handle, ctypes.byref(core), ctypes.byref(tile), ctypes.byref(rows)))
+        return bool(core.value), tile.value, rows.value
+
     def pooled_moments_begin(self):
         """Enqueue the pooled-moment reduction of the CURRENT state and its copy to the host without waiting; work
         enqueued afterwards overlaps it.  Collect with :meth:`pooled_moments_end`."""
