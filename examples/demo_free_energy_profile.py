@@ -4,7 +4,9 @@ E = 4 (x^2 - 1)^2, sampled by parallel tempering with x of every chain recorded 
 on 40 bins and F(x; T) = -T ln p(x; T) at three temperatures -- a cold one at which the plain samples of that temperature alone
 hardly ever see the barrier, one in between and a hot one -- printed next to the exact profile of the same bins,
 -T ln (integral over the bin of exp(-E / T) dx / (width Z(T))) = 4 (x^2 - 1)^2 + T ln Z(T) averaged over the bin, from a
-numerical quadrature.
+numerical quadrature.  ``free_energy_profile_uncertainties`` adds the asymptotic standard error of every F(x; T), printed as
++-, and the covariance of the bins, from which the error bar of the barrier height F(0) - F(well) follows: the two values
+come from the same samples, so their errors do not simply add in quadrature.
 
     python examples/demo_free_energy_profile.py [--quick]        (needs an MI355X and the built library)
 """
@@ -56,16 +58,31 @@ def sample(chains_per_rung=4096, burn_in=600, n_records=64, sweeps=5, rounds_per
     return engine
 
 
+def barrier_height(out, i):
+    """``(height, error, bin of the barrier top, bin of the well)`` at temperature ``i``: F of the bin left of x = 0 minus F of
+    the bin of largest density, and its standard error ``T sqrt(C_tt + C_ww - 2 C_tw)`` from ``C = log_mass_cov[i]``."""
+    top, well = int(np.searchsorted(out["edges"], 0.0)) - 1, int(out["lowest"][i])
+    c = out["log_mass_cov"][i]
+    height = out["free_energy"][i, top] - out["free_energy"][i, well]
+    return height, out["temps"][i] * np.sqrt(max(c[top, top] + c[well, well] - 2.0 * c[top, well], 0.0)), top, well
+
+
 def main(temps=TEMPS, edges=EDGES, **kw):
     engine = sample(**kw)
-    out = engine.free_energy_profile("real_0", edges, temps)
+    out = engine.free_energy_profile_uncertainties("real_0", edges, temps)
     exact = quadrature(out["edges"], out["temps"])
     print("samples %d, outside the bins: %s; neff_fraction %s" % (out["counts"].sum() + out["counts_outside"].sum(),
                                                                  out["counts_outside"].tolist(), np.round(out["neff_fraction"], 4)))
-    print("      x    samples" + "".join("   F(x; %.2f): MBAR     exact" % t for t in out["temps"]))
+    print("      x    samples" + "".join("   F(x; %.2f): MBAR    +-       exact" % t for t in out["temps"]))
     for b, x in enumerate(out["centers"]):
         print("%7.3f   %8d" % (x, out["counts"][b]) +
-              "".join("   %17.4f  %8.4f" % (out["free_energy"][i, b], exact[i, b]) for i in range(len(out["temps"]))))
+              "".join("   %17.4f  %6.4f  %8.4f" % (out["free_energy"][i, b], out["d_free_energy"][i, b], exact[i, b])
+                      for i in range(len(out["temps"]))))
+    for i, t in enumerate(out["temps"]):
+        height, error, top, well = barrier_height(out, i)
+        print("T = %.2f: barrier height F(%.2f) - F(%.2f) = %.4f +- %.4f (exact %.4f); errors of the two bins alone %.4f and %.4f"
+              % (t, out["centers"][top], out["centers"][well], height, error, exact[i, top] - exact[i, well],
+                 out["d_free_energy"][i, top], out["d_free_energy"][i, well]))
     return {"result": out, "exact": exact, "engine": engine}
 
 

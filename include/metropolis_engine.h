@@ -479,7 +479,26 @@ int me_mbar_energy_shift(me_engine *engine, double *shift);
  *                       me_mbar_histogram_samples on the same samples in the same order.  The free-energy profile is F(A; T) =
  *                       -T ln(mass / bin width).  Errors otherwise as for me_mbar_reweight.
  *   me_mbar_histogram_samples  the same kernels on host arrays, like me_mbar_reweight_samples; values[n_samples] holds A of
- *                       every sample (pass the energies for an energy histogram). */
+ *                       every sample (pass the energies for an energy histogram).
+ *   me_mbar_histogram_gram     me_mbar_histogram with what the asymptotic error bars of its masses need (csrc/
+ *                       me_mbar_hist_cov.hip has the definition).  mass, counts and neff_fraction are me_mbar_histogram's, bit
+ *                       for bit (the same code).  With K = n_rungs, W_nj = exp(min(f_j - E_n / T_j - d_n, 0)) the ladder column j
+ *                       of me_mbar_gram and w_nt the unnormalised weight behind mass[t] (w_nt = exp(min(-E_n / T_t - d_n -
+ *                       ln_z_t, 0))), slot_gram is [n][K + 1][n_bins + 3]:
+ *                           slot_gram[t][j][s] = sum over the used samples of slot s of W_nj w_nt     (j < K)
+ *                           slot_gram[t][K][s] = sum over the used samples of slot s of w_nt^2.
+ *                       The weight matrix [K ladder columns | state column w_nt | one column w_nt 1[slot = s] / mass[t][s] per
+ *                       slot] has disjoint slot columns, so its whole Gram matrix follows from slot_gram, mass and ladder_gram
+ *                       without being formed: ladder_j x slot_s = slot_gram[t][j][s] / mass[t][s], state x slot_s =
+ *                       slot_gram[t][K][s] / mass[t][s], slot_s x slot_s = slot_gram[t][K][s] / mass[t][s]^2 (0 between different
+ *                       slots), ladder_j x state and state x state the sums of slot_gram[t][j][.] and slot_gram[t][K][.] over the
+ *                       slots.  ladder_gram [K][K] and column_counts [K] are the ladder block and the counts of me_mbar_gram
+ *                       with n_targets = 0 (that pass itself); *n_used the used samples.  Every output may be NULL.  A slot
+ *                       without a sample has slot_gram exactly 0.  No floating-point atomics: all sums have a fixed order, and
+ *                       slot_gram[t][j][s] is bit for bit the same run to run, whatever other temperatures are asked for, and
+ *                       through me_mbar_histogram_gram_samples on the same samples in the same order.  Arguments are checked
+ *                       and errors reported exactly as by me_mbar_histogram.
+ *   me_mbar_histogram_gram_samples  the same on host arrays, like me_mbar_histogram_samples. */
 #define ME_MAX_RECORDED_OBSERVABLES 16
 #define ME_MAX_HISTOGRAM_BINS 256
 int me_observable_samples_enable(me_engine *engine, const int32_t *indices, int32_t n_observables);
@@ -504,6 +523,14 @@ int me_mbar_histogram_samples(int32_t device_id, const double *energies, const i
                               const double *ladder_temps, int32_t n_rungs, const double *f, const double *temps, int32_t n,
                               const double *values, const double *edges, int32_t n_bins, double *mass, int64_t *counts,
                               double *neff_fraction);
+int me_mbar_histogram_gram(me_engine *engine, const double *f, const double *temps, int32_t n, int32_t column,
+                           const double *edges, int32_t n_bins, double *slot_gram, double *ladder_gram, double *column_counts,
+                           double *mass, int64_t *counts, double *neff_fraction, int64_t *n_used);
+int me_mbar_histogram_gram_samples(int32_t device_id, const double *energies, const int32_t *rungs, int64_t n_samples,
+                                   const double *ladder_temps, int32_t n_rungs, const double *f, const double *temps, int32_t n,
+                                   const double *values, const double *edges, int32_t n_bins, double *slot_gram,
+                                   double *ladder_gram, double *column_counts, double *mass, int64_t *counts,
+                                   double *neff_fraction, int64_t *n_used);
 
 /* Text of the last error on this engine (or of the last failed me_create when engine is NULL). */
 int me_last_error(me_engine *engine, char *buf, size_t buf_bytes);

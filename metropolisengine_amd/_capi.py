@@ -158,6 +158,12 @@ SYMBOLS = {
     "me_mbar_histogram_samples": (ctypes.c_int, [ctypes.c_int32, _dp, ctypes.POINTER(ctypes.c_int32), ctypes.c_int64, _dp,
                                                  ctypes.c_int32, _dp, _dp, ctypes.c_int32, _dp, _dp, ctypes.c_int32, _dp,
                                                  ctypes.POINTER(ctypes.c_int64), _dp]),
+    "me_mbar_histogram_gram": (ctypes.c_int, [_H, _dp, _dp, ctypes.c_int32, ctypes.c_int32, _dp, ctypes.c_int32, _dp, _dp, _dp, _dp,
+                                              ctypes.POINTER(ctypes.c_int64), _dp, ctypes.POINTER(ctypes.c_int64)]),
+    "me_mbar_histogram_gram_samples": (ctypes.c_int, [ctypes.c_int32, _dp, ctypes.POINTER(ctypes.c_int32), ctypes.c_int64, _dp,
+                                                      ctypes.c_int32, _dp, _dp, ctypes.c_int32, _dp, _dp, ctypes.c_int32, _dp, _dp,
+                                                      _dp, _dp, ctypes.POINTER(ctypes.c_int64), _dp,
+                                                      ctypes.POINTER(ctypes.c_int64)]),
 }
 
 

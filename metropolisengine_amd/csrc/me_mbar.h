@@ -1,8 +1,9 @@
 // What the MBAR units share (me_mbar.hip: samples, solve, reweighting; me_mbar_cov.hip: the Gram matrix of the weight matrix
 // for the asymptotic covariance; me_mbar_obs.hip: recorded observables and their reweighting; me_mbar_hist.hip: reweighted
-// histograms along an observable): the tile policy, the device table of a ladder, the per-sample sums, and the host
-// scaffolding of an entry point, which me_mbar.hip defines: where the samples come from (Source), the prepared problem
-// (Problem, prepare) and the argument checks.  Private to the host side, like me_engine.h.
+// histograms along an observable; me_mbar_hist_cov.hip: the slot Gram sums behind their error bars): the tile policy, the
+// device table of a ladder, the per-sample sums, and the host scaffolding of an entry point, which me_mbar.hip defines: where
+// the samples come from (Source), the prepared problem (Problem, prepare) and the argument checks.  Private to the host side,
+// like me_engine.h.
 #pragma once
 
 #include <algorithm>
@@ -149,6 +150,40 @@ hipError_t reweight_observables_enqueue(Problem &p, const MbarSamples &sm, const
                                         ObsScratch &scratch, double *out);
 // me_energy_samples_record's second kernel: row `row` of the engine's observable store (which exists) on the engine's stream
 hipError_t observable_record_enqueue(me_engine *e, long long row);
+
+
+// ---- defined in me_mbar_cov.hip -----------------------------------------------------------------------------------------
+// The Gram matrix of the weight matrix [K ladder columns | state and energy column of each target]: prepares `p`, waits for the
+// stream and writes host arrays gram[C][C] (C = n_rungs + 2 n_targets), column_counts[C], ln_z / mean_e[n_targets] (may be
+// nullptr).  With an empty rung (p.empty_rung) nothing else is computed.
+hipError_t mbar_gram(Problem &p, const Source &src, const double *f, const double *temps, int n_targets, double *gram,
+                     double *column_counts, double *ln_z, double *mean_e);
+
+// ---- defined in me_mbar_hist.hip ----------------------------------------------------------------------------------------
+// A histogram request: edges[n_bins + 1] and the host outputs mass[n_temps][n_bins + 3], counts[n_bins + 3], neff[n_temps] (each
+// may be nullptr)
+struct Histogram {
+  const double *edges;
+  int n_bins;
+  double *mass;
+  int64_t *counts;
+  double *neff;
+};
+// what a histogram leaves on the device for a pass that follows it: d_n of every sample (log_denominator_enqueue), the edges, and
+// `top` of slot_of (me_mbar_slots.h)
+struct HistogramScratch {
+  DeviceBuffer d, edges;
+  int top = 1;
+};
+// Prepares `p`, reweights to temps[0 .. n_temps) (afterwards p.w.inv_temps and p.w.out are reweight_enqueue's), fills the
+// histogram of the one column `values` (n_columns = 1) and waits for the stream.  With an empty rung nothing else is computed.
+hipError_t histogram(Problem &p, const Source &src, const ObsColumns &values, const double *f, const double *temps, int n_temps,
+                     const Histogram &h, HistogramScratch &keep);
+// ME_ERR_INVALID unless 1 <= n_bins <= ME_MAX_HISTOGRAM_BINS and edges[0 .. n_bins] is there, finite and strictly increasing
+int check_edges(me_engine *e, const double *edges, int n_bins);
+// `values` = the column of an engine's Source that a histogram entry point names: a recorded column (ME_ERR_STATE without an
+// observable store, ME_ERR_INVALID beyond the recorded columns) or, for -1, the energies themselves
+int histogram_column(const Source &src, int column, ObsColumns &values);
 
 }  // namespace mbar
 }  // namespace me

@@ -456,8 +456,11 @@ hipError_t gram_chunks(Problem &p, long long n_samples, int per_target, int n_ta
   return hipSuccess;
 }
 
+}  // namespace
+
 // Waits for the stream and writes host arrays: gram[C][C] (C = n_rungs + 2 n_targets), column_counts[C], ln_z /
-// mean_e[n_targets] (may be nullptr).  With an empty rung (p.empty_rung) nothing else is computed.
+// mean_e[n_targets] (may be nullptr).  With an empty rung (p.empty_rung) nothing else is computed.  (Declared in me_mbar.h:
+// me_mbar_hist_cov.hip takes its ladder block from here.)
 hipError_t mbar_gram(Problem &p, const Source &src, const double *f, const double *temps, int n_targets, double *gram,
                      double *column_counts, double *ln_z, double *mean_e) {
   ME_MBAR_HIP(prepare(p, src, f));
@@ -496,6 +499,8 @@ hipError_t mbar_gram(Problem &p, const Source &src, const double *f, const doubl
   unpack_targets(out, n_targets, ln_z, mean_e, nullptr, nullptr);
   return hipSuccess;
 }
+
+namespace {
 
 // The observable form: gram[C][C] and column_counts[C] with C = n_rungs + n_targets (1 + Q), ln_z[n_targets], mean[n_targets][Q]
 // and shifts[Q] (the last three may be nullptr).  n_targets >= 1 and src has columns.

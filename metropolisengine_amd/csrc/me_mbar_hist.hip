@@ -22,6 +22,8 @@
 //                        end, and NO atomic touches a floating-point number.
 //   k_mbar_hist_sum      block (slot, t): the block partials of one cell in a fixed order; the integer counts.
 //   k_mbar_hist_normalise  block t: the total over the slots in a fixed order, then the division.
+// (slot_of, steps 1 to 3 below as slot_accumulate, and k_mbar_hist_sum live in me_mbar_slots.h: me_mbar_hist_cov.hip fills
+// its tables by the same code.)
 // How a wavefront adds the 64 weights of one item of the tile into its table, all lanes active throughout (the loop condition
 // is a ballot, wave-uniform; no cross-lane operation ever runs under a partial lane mask):
 //   0. every lane adds 1 to its slot's count with an integer LDS atomic (integers: exact in any order);
@@ -46,7 +48,7 @@
 // through the engine's store or host arrays of the same samples in the same order (the values are addressed through strides).
 // Registers and LDS (hipcc -O3, gfx950): see profiles/mbar_profile.txt; no kernel uses scratch.  LDS per workgroup: (n_bins +
 // 1) 8 + 4 (n_bins + 3)(4 x 8 + 4) bytes, 39 352 at 256 bins.
-#include "me_mbar.h"
+#include "me_mbar_slots.h"
 
 #pragma clang fp contract(off)
 
@@ -55,25 +57,6 @@ namespace mbar {
 namespace {
 
 constexpr int kHistTargets = 4;                 // temperatures per pass
-#ifndef ME_HIST_DENSE
-#define ME_HIST_DENSE 8
-#endif
-// lanes of a wavefront sharing a slot beyond which they are summed by butterfly (0: every group, 64: none; the build uses 8,
-// the other values are there to be measured against: profiles/mbar_profile.txt)
-constexpr int kDense = ME_HIST_DENSE;
-
-// the slot of value a: searchsorted(edges, a, side = "right") - 1 mapped onto [0, n_bins + 3); `top` = the largest power of
-// two <= n_edges (wave-uniform), so the loop takes floor(log2 n_edges) + 1 <= 9 steps
-__device__ __forceinline__ int slot_of(const double *edges, int n_edges, int top, double a) {
-  int pos = 0;                                  // edges <= a
-  for (int step = top; step >= 1; step >>= 1) {
-    const int cand = pos + step;
-    const bool ok = cand <= n_edges && edges[min(cand, n_edges) - 1] <= a;
-    pos = ok ? cand : pos;
-  }
-  const int n_bins = n_edges - 1;
-  return a != a ? n_bins + 2 : pos == 0 ? n_bins : pos == n_edges ? n_bins + 1 : pos - 1;
-}
 
 // values: sample i = record * n_chains + chain sits at values[record * record_stride + chain] (a column of the engine's store:
 // n_chains, Q n_chains; a host array or the energies themselves: n, 0).  `d` is padded to whole tiles.  ln_z has stride 4
@@ -126,83 +109,17 @@ __global__ void __launch_bounds__(kThreads) k_mbar_hist(const double *__restrict
         record += 1;
       }
       if (slot >= 0) atomicAdd(&my_count[slot], 1u);          // (integers: exact in any order)
-      // every lane is active from here on: the loop conditions are wave-uniform
-      unsigned long long todo = __ballot(slot >= 0);
-      int rank = 0, rounds = 0;
-      while (todo) {
-        const int leader = __ffsll((long long)todo) - 1;
-        const int s = __builtin_amdgcn_readlane(slot, leader);
-        const bool mine = slot == s;
-        const unsigned long long group = __ballot(mine);
-        const int size = __popcll(group);
-        if (size > kDense) {
-#pragma unroll
-          for (int t = 0; t < kHistTargets; ++t)
-            if (t < n_targets) {
-              const double sum = wave_sum(mine ? w[t] : 0.0);
-              if (lane == 0) my_mass[t * n_slots + s] = my_mass[t * n_slots + s] + sum;
-            }
-        } else {
-          rank = mine ? __popcll(group & below_me) + 1 : rank;
-          rounds = max(rounds, size);
-        }
-        todo &= ~group;
-      }
-      for (int round = 1; round <= rounds; ++round) {
-        // The lanes of one round hold different slots, so its plain loads and stores never meet in one address.  A round
-        // must see the table as the rounds before it left it, through OTHER lanes: a wavefront's LDS operations issue and
-        // complete in program order, and the wavefront-scope fence with the barrier keeps the compiler from moving a
-        // round's non-atomic LDS accesses across those of its neighbours.
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        if (rank == round) {
-#pragma unroll
-          for (int t = 0; t < kHistTargets; ++t)
-            if (t < n_targets) my_mass[t * n_slots + slot] = my_mass[t * n_slots + slot] + w[t];
-        }
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-      __builtin_amdgcn_wave_barrier();
+      // every lane is active from here on (me_mbar_slots.h)
+      slot_accumulate<kHistTargets>(my_mass, n_slots, n_targets, slot, w, lane, below_me);
     }
   }
   __syncthreads();
-  // the wavefront tables in wavefront order
-  for (int c = threadIdx.x; c < n_targets * n_slots; c += kThreads) {
-    double sum = s_mass[c];
-    for (int k = 1; k < kWaves; ++k) sum = sum + s_mass[k * kHistTargets * n_slots + c];
-    partials[(size_t)blockIdx.x * kHistTargets * n_slots + c] = sum;
-  }
+  slot_tables_store(s_mass, kHistTargets, n_targets, n_slots, partials);
   for (int c = threadIdx.x; c < n_slots; c += kThreads) {
     unsigned long long sum = 0;
     for (int k = 0; k < kWaves; ++k) sum += s_count[k * n_slots + c];
     count_partials[(size_t)blockIdx.x * n_slots + c] = sum;
   }
-}
-
-// block (slot, t): the block partials of the pass's target t and one slot in a fixed order into sums[t][slot]; with `counts`
-// the blocks of target 0 also add the slot's counts (integers)
-__global__ void __launch_bounds__(kThreads) k_mbar_hist_sum(const double *partials, const unsigned long long *count_partials, int n_blocks,
-                                                            int n_slots, double *sums, long long *counts) {
-  __shared__ double waves[kWaves];
-  __shared__ unsigned long long total;
-  const int s = blockIdx.x, t = blockIdx.y;
-  double v = 0.0;
-  for (int b = threadIdx.x; b < n_blocks; b += kThreads) v = v + partials[((size_t)b * kHistTargets + t) * n_slots + s];
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) waves[threadIdx.x >> 6] = v;
-  if (threadIdx.x == 0) total = 0;
-  __syncthreads();
-  if (counts && t == 0) {
-    unsigned long long c = 0;
-    for (int b = threadIdx.x; b < n_blocks; b += kThreads) c += count_partials[(size_t)b * n_slots + s];
-    if (c) atomicAdd(&total, c);
-  }
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  double sum = waves[0];
-  for (int k = 1; k < kWaves; ++k) sum = sum + waves[k];
-  sums[(size_t)t * n_slots + s] = sum;
-  if (counts && t == 0) counts[s] = (long long)total;
 }
 
 // block t: mass[t][slot] = sums[t][slot] / (the sum over all slots, in a fixed order)
@@ -219,17 +136,11 @@ __global__ void __launch_bounds__(kThreads) k_mbar_hist_normalise(int n_slots, d
   for (int s = threadIdx.x; s < n_slots; s += kThreads) row[s] = row[s] / total;
 }
 
-struct Histogram {
-  const double *edges;
-  int n_bins;
-  double *mass;
-  int64_t *counts;
-  double *neff;
-};
+}  // namespace
 
 // `values`: one column (n_columns = 1) that goes with the problem's samples
 hipError_t histogram(Problem &p, const Source &src, const ObsColumns &values, const double *f, const double *temps, int n_temps,
-                     const Histogram &h) {
+                     const Histogram &h, HistogramScratch &keep) {
   ME_MBAR_HIP(prepare(p, src, f));
   if (p.empty_rung >= 0) return hipSuccess;
   Work &w = p.w;
@@ -237,8 +148,10 @@ hipError_t histogram(Problem &p, const Source &src, const ObsColumns &values, co
   const long long n_tiles = tiles_of(p.sm.n_samples);
   int top = 1;
   while (2 * top <= n_edges) top *= 2;
+  keep.top = top;
   std::vector<double> inv;
-  DeviceBuffer d, edges, partials, count_partials, mass, counts;
+  DeviceBuffer &d = keep.d, &edges = keep.edges;
+  DeviceBuffer partials, count_partials, mass, counts;
   ME_MBAR_HIP(reweight_enqueue(p, p.sm, temps, n_temps, inv));      // ln_z and neff_fraction of every target into w.out
   ME_MBAR_HIP(log_denominator_enqueue(p, p.sm, d));
   ME_MBAR_HIP(edges.resize((size_t)n_edges * sizeof(double)));
@@ -256,7 +169,7 @@ hipError_t histogram(Problem &p, const Source &src, const ObsColumns &values, co
                        w.inv_temps.get<const double>() + t0, w.out.get<const double>() + 4 * (size_t)t0, nt, n_tiles,
                        partials.get<double>(), count_partials.get<unsigned long long>());
     hipLaunchKernelGGL(k_mbar_hist_sum, dim3(n_slots, nt), dim3(kThreads), 0, p.stream, partials.get<const double>(),
-                       count_partials.get<const unsigned long long>(), n_blocks, n_slots, sums,
+                       count_partials.get<const unsigned long long>(), n_blocks, kHistTargets, n_slots, sums,
                        t0 == 0 ? counts.get<long long>() : nullptr);
     hipLaunchKernelGGL(k_mbar_hist_normalise, dim3(nt), dim3(kThreads), 0, p.stream, n_slots, sums);
   }
@@ -266,7 +179,7 @@ hipError_t histogram(Problem &p, const Source &src, const ObsColumns &values, co
   ME_MBAR_HIP(hipMemcpyAsync(out.data(), w.out.get(), out.size() * sizeof(double), hipMemcpyDeviceToHost, p.stream));
   ME_MBAR_HIP(hipMemcpyAsync(mass_host.data(), mass.get(), mass.bytes(), hipMemcpyDeviceToHost, p.stream));
   ME_MBAR_HIP(hipMemcpyAsync(counts_host.data(), counts.get(), counts.bytes(), hipMemcpyDeviceToHost, p.stream));
-  ME_MBAR_HIP(hipStreamSynchronize(p.stream));    // (also: `inv` and the scratch buffers leave scope)
+  ME_MBAR_HIP(hipStreamSynchronize(p.stream));    // (also: `inv` and the scratch buffers but `keep` leave scope)
   unpack_targets(out, n_temps, nullptr, nullptr, nullptr, h.neff);
   if (h.mass) std::copy(mass_host.begin(), mass_host.end(), h.mass);
   if (h.counts) std::copy(counts_host.begin(), counts_host.end(), h.counts);
@@ -283,6 +196,26 @@ int check_edges(me_engine *e, const double *edges, int n_bins) {
   return ME_OK;
 }
 
+// column >= 0: that recorded column of an engine's store; -1: the energies themselves
+int histogram_column(const Source &src, int column, ObsColumns &values) {
+  me_engine *e = src.e;
+  values = ObsColumns{src.sm.energies, 1, src.sm.n_samples, 0, src.sm.n_samples};
+  if (column >= 0) {
+    if (src.columns.n_columns == 0)
+      return fail(e, ME_ERR_STATE, "no recorded observables: me_observable_samples_enable, then me_energy_samples_record");
+    if (column >= src.columns.n_columns)
+      return fail(e, ME_ERR_INVALID, "column " + std::to_string(column) + " outside the " + std::to_string(src.columns.n_columns) +
+                                         " recorded columns");
+    values = ObsColumns{src.columns.data + (size_t)column * (size_t)src.columns.column_stride, 1, src.columns.n_chains,
+                        src.columns.record_stride, src.columns.column_stride};
+  } else if (column != -1) {
+    return fail(e, ME_ERR_INVALID, "column must be a recorded column or -1 (the energy)");
+  }
+  return ME_OK;
+}
+
+namespace {
+
 // the two forms of me_mbar_histogram behind their Source
 int histogram_common(const Source &src, const ObsColumns &values, const double *f, const double *temps, int n, const Histogram &h) {
   int rc = check_edges(src.e, h.edges, h.n_bins);
@@ -290,7 +223,8 @@ int histogram_common(const Source &src, const ObsColumns &values, const double *
   rc = check_f_and_targets(src.e, f, src.n_rungs, temps, n, 1);
   if (rc) return rc;
   Problem p;
-  return mbar_check_common(src.e, p, histogram(p, src, values, f, temps, n, h));
+  HistogramScratch keep;
+  return mbar_check_common(src.e, p, histogram(p, src, values, f, temps, n, h, keep));
 }
 
 }  // namespace
@@ -305,20 +239,11 @@ extern "C" {
 int me_mbar_histogram(me_engine *e, const double *f, const double *temps, int32_t n, int32_t column, const double *edges,
                       int32_t n_bins, double *mass, int64_t *counts, double *neff_fraction) {
   Source src;
-  const int rc = src.from_engine(e);
+  int rc = src.from_engine(e);
   if (rc) return rc;
-  ObsColumns values{src.sm.energies, 1, src.sm.n_samples, 0, src.sm.n_samples};      // column -1: the energy itself
-  if (column >= 0) {
-    if (src.columns.n_columns == 0)
-      return fail(e, ME_ERR_STATE, "no recorded observables: me_observable_samples_enable, then me_energy_samples_record");
-    if (column >= src.columns.n_columns)
-      return fail(e, ME_ERR_INVALID, "column " + std::to_string(column) + " outside the " + std::to_string(src.columns.n_columns) +
-                                         " recorded columns");
-    values = ObsColumns{src.columns.data + (size_t)column * (size_t)src.columns.column_stride, 1, src.columns.n_chains,
-                        src.columns.record_stride, src.columns.column_stride};
-  } else if (column != -1) {
-    return fail(e, ME_ERR_INVALID, "column must be a recorded column or -1 (the energy)");
-  }
+  ObsColumns values{};
+  rc = histogram_column(src, column, values);
+  if (rc) return rc;
   return histogram_common(src, values, f, temps, n, Histogram{edges, n_bins, mass, counts, neff_fraction});
 }
 

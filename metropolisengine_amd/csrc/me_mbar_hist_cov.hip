@@ -1,0 +1,251 @@
+// The slot Gram sums behind the error bars of a reweighted histogram (me_mbar_histogram_gram and its engine-less twin in the
+// public header): what the asymptotic covariance of MBAR (me_mbar_cov.hip; Shirts & Chodera 2008, eq. D8) needs for the
+// weight matrix [K ladder columns | state column of target t | one indicator column per slot], WITHOUT forming that matrix.
+//
+// Definition.  Notation of me_mbar_cov.hip and me_mbar_hist.hip: a sample is USED when its energy is finite, d_n is the log
+// denominator, slot_n in [0, n_bins + 3) the slot of its value (half-open bins, then below, above, NaN),
+//     W_nj = exp(min(f_j - E_n / T_j - d_n, 0))              ladder column j, the expression of k_mbar_gram's fill
+//     w_nt = exp(min(-E_n / T_t - d_n - ln_z_t, 0))          state column of target t, the weight k_mbar_hist forms
+// and the indicator column of (t, s) is w_nt 1[slot_n = s] / p_ts with p_ts the histogram's mass.  The indicator columns of
+// one target are disjoint, so every entry of the Gram matrix that involves them follows from
+//     H[t][j][s] = sum_{n used, slot_n = s} W_nj w_nt   (j < K),       H[t][K][s] = sum_{n used, slot_n = s} w_nt^2:
+// ladder_j x slot_s = H[t][j][s] / p_ts, state x slot_s = H[t][K][s] / p_ts, slot_s x slot_s' = delta_ss' H[t][K][s] / p_ts^2,
+// ladder_j x state = sum_s H[t][j][s], state x state = sum_s H[t][K][s]; the ladder x ladder block is mbar_gram's with no
+// targets.  The host assembles the matrix (statistics.py), at most 64 + 1 + 259 columns per temperature.
+//
+// Kernels.  The masses, counts, ln_z_t and d_n are those of histogram() (me_mbar_hist.hip), called first: the same code, the
+// same bits.  k_mbar_hist_cov<R> is k_mbar_hist with the table's temperature axis replaced by a chunk of R rows j of ONE
+// temperature: one pass per (t, chunk), n ceil((K + 1) / R) passes, each reading 24 bytes per sample, finding the slot and
+// forming w_nt once and one more exponential per ladder row; the accumulation into the wavefront-private LDS table is
+// slot_accumulate (me_mbar_slots.h), so no atomic touches a floating-point number and no cross-lane operation runs under a
+// partial lane mask.  k_mbar_hist_sum (the same header) adds the block partials of every (row, slot) in a fixed order.
+// Summation order of one H[t][j][s]: that of a mass in me_mbar_hist.hip, fixed by the samples' slots and order alone.  It
+// depends neither on t, nor on j, nor on R, nor on which chunk a row falls into, and a row's terms are formed by the same
+// instructions at every position of a chunk (`fp contract(off)`): H[t][j][s] is bit for bit the same run to run, whatever
+// other targets are asked for, and through the engine's store or host arrays of the same samples in the same order.
+// Rows per pass: R is a pure cost choice, passes against LDS (occupancy): the widest of 16, 8, 4 whose table leaves
+// kMinBlocksPerCu = 4 workgroups on a CU (rows_per_pass): 16 up to 75 bins, 8 up to 152, 4 beyond.  Measured at 2^25 samples,
+// 8 targets, K = 32, R = 4 / 8 / 16 forced (profiles/mbar_profile_uncertainty.txt), milliseconds for all passes: 64 bins, every
+// value in one bin 39.8 / 34.5 / 34.9, 64 different bins per wavefront 97.0 / 58.4 / 47.1 (a wide R shares the match loop, the
+// slot search and w_nt among its rows); 256 bins 46.5 / 57.5 / 86.6 and 109.8 / 103.4 / 129.1 (R = 16 leaves ONE workgroup per
+// CU, one wavefront per SIMD, and nothing hides the LDS round trips of the table).  LDS per workgroup: (n_bins + 1) 8 + 4 R
+// (n_bins + 3) 8 bytes: 34 824 at 64 bins with R = 16, 35 208 at 256 bins with R = 4.  Registers (hipcc -O3, gfx950): 56 / 73 /
+// 113 VGPRs for R = 4 / 8 / 16, 7 / 6 / 4 wavefronts per SIMD, no AGPRs; no kernel uses scratch.
+#include "me_launch.h"
+#include "me_mbar_slots.h"
+
+#pragma clang fp contract(off)
+
+namespace me {
+namespace mbar {
+namespace {
+
+#ifndef ME_HIST_COV_ROWS
+#define ME_HIST_COV_ROWS 0
+#endif
+// 0: the rule of rows_per_pass; 4, 8, 16: that R at every bin count (to be measured against: profiles/mbar_profile_uncertainty.txt)
+constexpr int kForcedRows = ME_HIST_COV_ROWS;
+constexpr int kMaxRows = 16;
+constexpr size_t kCuLds = 160 * 1024;           // LDS of a CU
+constexpr int kMinBlocksPerCu = 4;              // 4 wavefronts per SIMD, k_mbar_hist's own occupancy at 256 bins
+
+constexpr size_t lds_bytes(int rows, int n_bins) {
+  return (size_t)(n_bins + 1) * sizeof(double) + (size_t)kWaves * rows * (n_bins + 3) * sizeof(double);
+}
+
+// R of a launch: the widest of 16, 8, 4 with which kMinBlocksPerCu workgroups fit a CU's LDS (R = 4 always does).
+// tools/bench_mbar.py (time_profile_uncertainty) restates this rule to print its pass counts: change both together.
+int rows_per_pass(int n_bins) {
+  if (kForcedRows) return kForcedRows;
+  for (int rows = kMaxRows; rows > 4; rows /= 2)
+    if (kMinBlocksPerCu * lds_bytes(rows, n_bins) <= kCuLds) return rows;
+  return 4;
+}
+
+// One pass: rows j0 .. j0 + n_rows (n_rows <= kRows, j0 + n_rows <= n_rungs + 1) of target *inv_temp, *ln_z.  Row j < n_rungs
+// is ladder column j (beta_j, f_j from the ladder table), row n_rungs the state column itself.  Samples and values are
+// addressed as in k_mbar_hist; `d` is padded to whole tiles.  Dynamic LDS: [edges | table[kWaves][kRows][n_slots]];
+// partials[block][kRows][n_slots].
+template <int kRows>
+__global__ void __launch_bounds__(kThreads) k_mbar_hist_cov(const double *__restrict__ energies, const double *__restrict__ d,
+                                                            const double *__restrict__ values, long long n_chains,
+                                                            long long record_stride, const double *__restrict__ edges, int n_bins,
+                                                            int top, const double *__restrict__ table, int n_rungs,
+                                                            const double *__restrict__ inv_temp, const double *__restrict__ ln_z,
+                                                            int j0, int n_rows, long long n_tiles, double *partials) {
+  extern __shared__ double lds[];
+  const int n_edges = n_bins + 1, n_slots = n_bins + 3;
+  double *s_edges = lds, *s_table = lds + n_edges;
+  for (int i = threadIdx.x; i < n_edges; i += kThreads) s_edges[i] = edges[i];
+  for (int i = threadIdx.x; i < kWaves * kRows * n_slots; i += kThreads) s_table[i] = 0.0;
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  double *my_table = s_table + wave * kRows * n_slots;
+  const unsigned long long below_me = (1ull << lane) - 1ull;
+  const double inv = inv_temp[0], lz = ln_z[0];
+  double beta[kRows], g[kRows];
+#pragma unroll
+  for (int r = 0; r < kRows; ++r) {
+    const bool ladder = j0 + r < n_rungs;       // (wave-uniform)
+    beta[r] = ladder ? table[kBeta + j0 + r] : 0.0;
+    g[r] = ladder ? table[kF + j0 + r] : 0.0;
+  }
+  for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    const long long base = tile * kTile + threadIdx.x;
+    long long record = base / n_chains, chain = base - record * n_chains;
+#pragma unroll 1
+    for (int it = 0; it < kItems; ++it) {
+      const long long i = base + (long long)it * kThreads;
+      const double dn = d[i];                   // (padded: in bounds; NaN beyond n and for an unused sample)
+      int slot = -1;
+      double w[kRows];
+#pragma unroll
+      for (int r = 0; r < kRows; ++r) w[r] = 0.0;
+      if (dn == dn) {
+        const double e = energies[i];
+        slot = slot_of(s_edges, n_edges, top, values[record * record_stride + chain]);
+        const double wt = math64::exp_nonpos(fmin(__builtin_fma(-e, inv, -dn) - lz, 0.0));      // k_mbar_hist's weight
+#pragma unroll
+        for (int r = 0; r < kRows; ++r)
+          if (r < n_rows) {
+            // k_mbar_gram's ladder column; the last row of all pairs the state column with itself
+            const double col = j0 + r < n_rungs ? math64::exp_nonpos(fmin(__builtin_fma(-beta[r], e, g[r]) - dn, 0.0)) : wt;
+            w[r] = col * wt;
+          }
+      }
+      chain += kThreads;
+      while (chain >= n_chains) {
+        chain -= n_chains;
+        record += 1;
+      }
+      // every lane is active from here on (me_mbar_slots.h)
+      slot_accumulate<kRows>(my_table, n_slots, n_rows, slot, w, lane, below_me);
+    }
+  }
+  __syncthreads();
+  slot_tables_store(s_table, kRows, n_rows, n_slots, partials);
+}
+
+struct PassArgs {
+  const MbarSamples *sm;
+  const ObsColumns *values;
+  const HistogramScratch *keep;
+  const double *table, *inv_temp, *ln_z;
+  int n_bins, n_rungs, j0, n_rows, n_blocks;
+  long long n_tiles;
+  double *partials;
+};
+
+template <int kRows>
+hipError_t launch_pass(const PassArgs &a, hipStream_t stream) {
+  constexpr size_t most = lds_bytes(kRows, ME_MAX_HISTOGRAM_BINS);
+  if (most > 64 * 1024) ME_MBAR_HIP(raise_lds_limit<k_mbar_hist_cov<kRows>>(most));
+  hipLaunchKernelGGL(k_mbar_hist_cov<kRows>, dim3(a.n_blocks), dim3(kThreads), lds_bytes(kRows, a.n_bins), stream, a.sm->energies,
+                     a.keep->d.get<const double>(), a.values->data, a.values->n_chains, a.values->record_stride,
+                     a.keep->edges.get<const double>(), a.n_bins, a.keep->top, a.table, a.n_rungs, a.inv_temp, a.ln_z, a.j0, a.n_rows,
+                     a.n_tiles, a.partials);
+  return hipSuccess;
+}
+
+// slot_gram[n_temps][n_rungs + 1][n_bins + 3] (host) of a problem whose histogram() has just run: p.w.inv_temps and p.w.out
+// hold its targets, `keep` its d_n and edges.  Waits for the stream.
+hipError_t slot_gram(Problem &p, const ObsColumns &values, const HistogramScratch &keep, int n_bins, int n_temps, double *slot_gram) {
+  const int n_slots = n_bins + 3, n_blocks = blocks_of(p.sm.n_samples), n_cols = p.n_rungs + 1, rows = rows_per_pass(n_bins);
+  const size_t cells = (size_t)n_temps * n_cols * n_slots;
+  DeviceBuffer partials, sums;
+  ME_MBAR_HIP(partials.resize((size_t)n_blocks * rows * n_slots * sizeof(double)));
+  ME_MBAR_HIP(sums.resize(cells * sizeof(double)));
+  PassArgs a{&p.sm, &values, &keep, p.w.table.get<const double>(), nullptr, nullptr, n_bins, p.n_rungs, 0, 0, n_blocks,
+             tiles_of(p.sm.n_samples), partials.get<double>()};
+  for (int t = 0; t < n_temps; ++t)
+    for (int j0 = 0; j0 < n_cols; j0 += rows) {
+      a.inv_temp = p.w.inv_temps.get<const double>() + t;
+      a.ln_z = p.w.out.get<const double>() + 4 * (size_t)t;
+      a.j0 = j0;
+      a.n_rows = std::min(rows, n_cols - j0);
+      ME_MBAR_HIP(rows == 16 ? launch_pass<16>(a, p.stream) : rows == 8 ? launch_pass<8>(a, p.stream) : launch_pass<4>(a, p.stream));
+      hipLaunchKernelGGL(k_mbar_hist_sum, dim3(n_slots, a.n_rows), dim3(kThreads), 0, p.stream, partials.get<const double>(),
+                         (const unsigned long long *)nullptr, n_blocks, rows, n_slots,
+                         sums.get<double>() + ((size_t)t * n_cols + j0) * n_slots, (long long *)nullptr);
+    }
+  ME_MBAR_HIP(hipGetLastError());
+  ME_MBAR_HIP(hipMemcpyAsync(slot_gram, sums.get(), cells * sizeof(double), hipMemcpyDeviceToHost, p.stream));
+  return hipStreamSynchronize(p.stream);
+}
+
+struct HistogramGram {
+  Histogram h;
+  double *slot_gram, *ladder_gram, *column_counts;
+  int64_t *n_used;
+};
+
+// the two forms of me_mbar_histogram_gram behind their Source; the checks and their order are histogram_common's
+int histogram_gram_common(const Source &src, const ObsColumns &values, const double *f, const double *temps, int n,
+                          const HistogramGram &hg) {
+  int rc = check_edges(src.e, hg.h.edges, hg.h.n_bins);
+  if (rc) return rc;
+  rc = check_f_and_targets(src.e, f, src.n_rungs, temps, n, 1);
+  if (rc) return rc;
+  long long n_used = 0;
+  {
+    Problem p;
+    HistogramScratch keep;
+    rc = mbar_check_common(src.e, p, histogram(p, src, values, f, temps, n, hg.h, keep));
+    if (rc) return rc;
+    if (hg.slot_gram) {
+      rc = mbar_check_common(src.e, p, slot_gram(p, values, keep, hg.h.n_bins, n, hg.slot_gram));
+      if (rc) return rc;
+    }
+    n_used = p.n_used_ll;
+  }                                                                // (the problem's device scratch and d_n go before the next pass)
+  if (hg.ladder_gram || hg.column_counts) {
+    // The Gram pass with no targets (me_mbar_cov.hip), reused whole: it prepares a problem of its own (a second counting pass
+    // over the samples) because it packs the used samples before anything else.
+    Problem ladder;
+    std::vector<double> gram((size_t)src.n_rungs * src.n_rungs), column_counts((size_t)src.n_rungs);
+    rc = mbar_check_common(src.e, ladder, mbar_gram(ladder, src, f, nullptr, 0, gram.data(), column_counts.data(), nullptr, nullptr));
+    if (rc) return rc;
+    if (hg.ladder_gram) std::copy(gram.begin(), gram.end(), hg.ladder_gram);
+    if (hg.column_counts) std::copy(column_counts.begin(), column_counts.end(), hg.column_counts);
+  }
+  if (hg.n_used) *hg.n_used = n_used;
+  return ME_OK;
+}
+
+}  // namespace
+}  // namespace mbar
+}  // namespace me
+
+using namespace me;
+using namespace me::mbar;
+
+extern "C" {
+
+int me_mbar_histogram_gram(me_engine *e, const double *f, const double *temps, int32_t n, int32_t column, const double *edges,
+                           int32_t n_bins, double *slot_gram, double *ladder_gram, double *column_counts, double *mass,
+                           int64_t *counts, double *neff_fraction, int64_t *n_used) {
+  Source src;
+  int rc = src.from_engine(e);
+  if (rc) return rc;
+  ObsColumns values{};
+  rc = histogram_column(src, column, values);
+  if (rc) return rc;
+  return histogram_gram_common(src, values, f, temps, n,
+                               HistogramGram{Histogram{edges, n_bins, mass, counts, neff_fraction}, slot_gram, ladder_gram,
+                                             column_counts, n_used});
+}
+
+int me_mbar_histogram_gram_samples(int32_t device_id, const double *energies, const int32_t *rungs, int64_t n_samples,
+                                   const double *ladder_temps, int32_t n_rungs, const double *f, const double *temps, int32_t n,
+                                   const double *values, const double *edges, int32_t n_bins, double *slot_gram,
+                                   double *ladder_gram, double *column_counts, double *mass, int64_t *counts,
+                                   double *neff_fraction, int64_t *n_used) {
+  Source src;
+  const int rc = src.from_host(device_id, energies, rungs, n_samples, ladder_temps, n_rungs, values, 1);
+  return rc ? rc
+            : src.finish(histogram_gram_common(src, src.columns, f, temps, n,
+                                               HistogramGram{Histogram{edges, n_bins, mass, counts, neff_fraction}, slot_gram,
+                                                             ladder_gram, column_counts, n_used}));
+}
+
+}  // extern "C"

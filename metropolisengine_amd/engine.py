@@ -818,29 +818,57 @@ class MetropolisEngine:
         from . import statistics
         temps = statistics.validate_mbar_temps(temps)
         edges = statistics.validate_histogram_edges(edges)
-        if isinstance(which, str) and which == "energy":
-            column, name = -1, "energy"
-        else:
-            names = self.recorded_observables
-            if not names:
-                raise ValueError("no observable store: call record_observables first")
-            if isinstance(which, str):
-                if which not in names:
-                    raise ValueError("unknown recorded observable %r; this engine records %s" % (which, ", ".join(names)))
-                column = names.index(which)
-            elif isinstance(which, (int, np.integer)) and not isinstance(which, bool):
-                if not 0 <= int(which) < len(names):
-                    raise ValueError("column %d outside the %d recorded columns" % (int(which), len(names)))
-                column = int(which)
-            else:
-                raise ValueError("the quantity is named by str or int, got %r" % (which,))
-            name = names[column]
+        column, name = self._profile_column(which)
         if f is None:
             f = self.ladder_free_energies()["f"]
         f = self._ladder_f(f, finite=False)
         out = statistics._free_energy_profile(self._lib.me_mbar_histogram, (self._handle,), f, temps, (column,), edges)
         out["name"] = name
         return out
+
+    def free_energy_profile_uncertainties(self, which, edges, temps, f=None, inefficiency=1.0):
+        """:meth:`free_energy_profile` with the asymptotic standard errors of the masses and of the profile
+        (``me_mbar_histogram_gram``, on the device: ``K + 1`` weighted histograms per temperature and the ladder block of the
+        Gram matrix; the samples stay there).  Arguments as there.  Returns every key of :meth:`free_energy_profile`, bit for
+        bit, and ``{"d_mass", "d_below", "d_above", "d_not_a_number", "d_free_energy", "log_mass_cov",
+        "d_free_energy_from_lowest", "lowest", "n_samples"}``, see
+        :func:`metropolisengine_amd.statistics.mbar_free_energy_profile_uncertainties`: the error of a barrier height ``F_b -
+        F_b'`` at temperature ``t`` is ``T sqrt(C[b, b] + C[b', b'] - 2 C[b, b'])`` with ``C = log_mass_cov[t]``.
+        ``inefficiency``: the statistical inefficiency of the recorded series, a finite scalar ``>= 1`` that multiplies every
+        variance.  ``ValueError`` as :meth:`free_energy_profile` and for an invalid ``inefficiency``; raises without a ladder or
+        without records."""
+        from . import statistics
+        g = statistics.validate_profile_inefficiency(inefficiency)
+        temps = statistics.validate_mbar_temps(temps)
+        edges = statistics.validate_histogram_edges(edges)
+        column, name = self._profile_column(which)
+        if f is None:
+            f = self.ladder_free_energies()["f"]
+        f = self._ladder_f(f, finite=False)
+        k = max(f.size, 1)      # (the ladder's rungs; without a ladder the library refuses before it writes)
+        out = statistics._free_energy_profile_uncertainties(self._lib.me_mbar_histogram_gram, (self._handle,), k, f, temps, (column,),
+                                                            edges, g)
+        out["name"] = name
+        return out
+
+    def _profile_column(self, which):
+        """``(column of the C ABI, name)`` of the quantity a profile runs along: -1 for ``"energy"``."""
+        if isinstance(which, str) and which == "energy":
+            return -1, "energy"
+        names = self.recorded_observables
+        if not names:
+            raise ValueError("no observable store: call record_observables first")
+        if isinstance(which, str):
+            if which not in names:
+                raise ValueError("unknown recorded observable %r; this engine records %s" % (which, ", ".join(names)))
+            column = names.index(which)
+        elif isinstance(which, (int, np.integer)) and not isinstance(which, bool):
+            if not 0 <= int(which) < len(names):
+                raise ValueError("column %d outside the %d recorded columns" % (int(which), len(names)))
+            column = int(which)
+        else:
+            raise ValueError("the quantity is named by str or int, got %r" % (which,))
+        return column, names[column]
 
     def observable_uncertainties(self, temps, f=None, inefficiency=1.0):
         """Asymptotic standard errors of :meth:`reweight_observables`' means (``me_mbar_gram_observables``: one further pass

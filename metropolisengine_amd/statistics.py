@@ -494,6 +494,115 @@ def mbar_observable_uncertainties(energies, rungs, temps, f, targets, observable
                                      tuple(range(a.shape[0])), g)
 
 
+def _profile_uncertainty_result(temps, edges, mass, counts, neff, slot_gram, ladder_gram, column_counts, n_used, inefficiency):
+    """The dictionary of :func:`mbar_free_energy_profile_uncertainties` from what ``me_mbar_histogram_gram`` returns.  One
+    matrix per temperature over the columns [K ladder | state | one per resolved slot], assembled from the slot Gram sums (the
+    slot columns are disjoint; include/metropolis_engine.h has the blocks), one ``mbar_theta`` each.  With ``a`` the state
+    column, ``Cov(ln p_s, ln p_s') = Theta_ss' + Theta_aa - Theta_sa - Theta_s'a``.
+
+    A slot is RESOLVED, and has a column, when ``H[K][s]``, the sum of its squared weights, is a normal float64 (at least
+    2.2e-308).  Below that the device's sum has lost its digits or is 0 -- the weights themselves are below 1.5e-154, which a cold
+    target reaches in a bin that only the hot rungs populate -- and ``H[K][s] / p_s^2`` would be 0 / 0.  Rescaling the column
+    cannot help, the sum is gone before the host sees it; the slot is left out and the others keep their results.  For a
+    resolved slot ``p_s^2 >= H[K][s]`` (the weights are >= 0), so neither division below can underflow."""
+    out = _profile_result(temps, edges, mass, counts, neff)
+    k, b, nt = ladder_gram.shape[0], edges.size - 1, temps.size
+    d_slot = np.zeros((nt, b + 3))
+    d_free, d_lowest = np.full((nt, b), np.nan), np.full((nt, b), np.nan)
+    log_cov = np.full((nt, b, b), np.nan)
+    lowest = np.zeros(nt, dtype=np.int64)
+    for t in range(nt):
+        p, h = mass[t], slot_gram[t]
+        resolved = h[k] >= np.finfo(np.float64).tiny
+        d_slot[t, (p > 0) & ~resolved] = np.nan          # (a mass, but no error bar; an empty slot keeps 0)
+        live = np.flatnonzero(resolved)
+        c = k + 1 + live.size
+        gram = np.zeros((c, c))
+        gram[:k, :k] = ladder_gram
+        gram[:k, k] = gram[k, :k] = h[:k].sum(axis=1)
+        gram[k, k] = h[k].sum()
+        gram[:k + 1, k + 1:] = h[:, live] / p[live][None, :]
+        gram[k + 1:, :k + 1] = gram[:k + 1, k + 1:].T
+        gram[k + 1 + np.arange(live.size), k + 1 + np.arange(live.size)] = h[k, live] / p[live] ** 2
+        theta = mbar_theta(gram, np.concatenate([column_counts, np.zeros(1 + live.size)]))
+        slots, to_state = theta[k + 1:, k + 1:], theta[k + 1:, k]
+        cov = (slots + theta[k, k] - to_state[:, None] - to_state[None, :]) * inefficiency
+        d_slot[t, live] = p[live] * np.sqrt(np.clip(np.diag(cov), 0.0, None))
+        bins = live < b                                  # (live is ascending: the bins come first)
+        own = live[bins]
+        if own.size == 0:
+            continue
+        d_free[t, own] = temps[t] * np.sqrt(np.clip(np.diag(cov)[bins], 0.0, None))
+        log_cov[np.ix_([t], own, own)] = cov[np.ix_(bins, bins)]
+        lowest[t] = int(np.argmax(out["density"][t]))
+        at = int(np.searchsorted(own, lowest[t]))
+        block = slots[np.ix_(bins, bins)]
+        diff = (np.diag(block) + block[at, at] - 2.0 * block[:, at]) * inefficiency
+        d_lowest[t, own] = temps[t] * np.sqrt(np.clip(diff, 0.0, None))
+        d_lowest[t, lowest[t]] = 0.0
+    out.update({"d_mass": d_slot[:, :b].copy(), "d_below": d_slot[:, b].copy(), "d_above": d_slot[:, b + 1].copy(),
+                "d_not_a_number": d_slot[:, b + 2].copy(), "d_free_energy": d_free, "log_mass_cov": log_cov,
+                "d_free_energy_from_lowest": d_lowest, "lowest": lowest, "n_samples": int(n_used)})
+    return out
+
+
+def _free_energy_profile_uncertainties(fn, lead, n_rungs, f, targets, middle, edges, inefficiency):
+    """``middle``: as in :func:`_free_energy_profile`."""
+    b, k = edges.size - 1, n_rungs
+    mass, counts, neff = np.zeros((targets.size, b + 3)), np.zeros(b + 3, dtype=np.int64), np.zeros(targets.size)
+    slot_gram, ladder_gram, column_counts = np.zeros((targets.size, k + 1, b + 3)), np.zeros((k, k)), np.zeros(k)
+    n_used = ctypes.c_int64()
+    _call(fn, lead, _capi.double_ptr(f), _capi.double_ptr(targets), targets.size, *middle, _capi.double_ptr(edges), b,
+          _capi.double_ptr(slot_gram), _capi.double_ptr(ladder_gram), _capi.double_ptr(column_counts), _capi.double_ptr(mass),
+          _capi.int64_ptr(counts), _capi.double_ptr(neff), ctypes.byref(n_used))
+    return _profile_uncertainty_result(targets, edges, mass, counts, neff, slot_gram, ladder_gram, column_counts, n_used.value,
+                                       inefficiency)
+
+
+def validate_profile_inefficiency(inefficiency):
+    """:func:`validate_mbar_inefficiency` for the profile's error bars, where the inefficiency is one scalar: anything with a
+    shape is a ``ValueError`` too."""
+    if np.ndim(inefficiency) != 0:
+        raise ValueError("inefficiency must be a scalar")
+    return validate_mbar_inefficiency(inefficiency)
+
+
+def mbar_free_energy_profile_uncertainties(energies, rungs, temps, f, targets, values, edges, inefficiency=1.0, device=0):
+    """:func:`mbar_free_energy_profile` with the asymptotic standard errors of its masses and of the free-energy profile
+    (``me_mbar_histogram_gram_samples``; the engine form is ``MetropolisEngine.free_energy_profile_uncertainties``).  The bin
+    indicators are columns of the MBAR weight matrix like any observable (Shirts & Chodera 2008, eqs. 8, D8), but DISJOINT ones:
+    the Gram matrix of [ladder | state | one column per slot] follows from ``K + 1`` weighted histograms per temperature
+    (csrc/me_mbar_hist_cov.hip), so any number of bins up to 256 costs no ``N x (K + 1 + B)`` matrix; the algebra, one matrix of at
+    most 64 + 1 + 259 columns per temperature, runs here in float64.
+
+    Returns every key of :func:`mbar_free_energy_profile`, bit for bit, and ``d_mass`` ``(T, B)``, ``d_below``, ``d_above``,
+    ``d_not_a_number`` ``(T,)``: the standard errors ``p sqrt(Var ln p)`` of the masses; ``d_free_energy`` ``(T, B)``: ``T
+    sqrt(Var ln p_b)``, the standard error of ``free_energy``; ``log_mass_cov`` ``(T, B, B)``: ``Cov(ln p_b, ln p_b')``, from
+    which the error of any difference ``F_b - F_b'`` follows as ``T sqrt(C_bb + C_b'b' - 2 C_bb')``; ``lowest`` ``(T,)``: the
+    bin of largest density; ``d_free_energy_from_lowest`` ``(T, B)``: the standard error of ``F_b - F_lowest`` (0 at
+    ``lowest``); ``n_samples``: the samples with a finite energy.
+
+    A slot whose mass is exactly 0 drops out of the algebra: its ``d_mass`` is 0, its ``d_free_energy``,
+    ``d_free_energy_from_lowest`` and its row and column of ``log_mass_cov`` are NaN.  The rule goes by the MASS, not by
+    ``counts``: at a cold target the weights of a bin that only hot rungs populate can all underflow.  The same holds, with
+    ``d_mass`` NaN as well, for a slot whose mass is positive but below about 1.5e-154: the sum of its squared weights is no
+    normal float64 any more and no error bar can be formed, although ``free_energy`` is still finite there.  Every other slot and
+    temperature keeps its results.
+
+    The formula assumes INDEPENDENT samples: pass the statistical inefficiency of the series as ``inefficiency`` (a finite
+    scalar ``>= 1``, ``ValueError`` otherwise) and every variance is multiplied by it."""
+    g = validate_profile_inefficiency(inefficiency)
+    e, r, t = validate_mbar_samples(energies, rungs, temps)
+    targets = validate_mbar_temps(targets, "targets")
+    f = validate_mbar_f(f, t.size)
+    edges = validate_histogram_edges(edges)
+    a = np.ascontiguousarray(np.asarray(values, dtype=np.float64).ravel())
+    if a.size != e.size:
+        raise ValueError("values needs one entry per sample (%d), got %d" % (e.size, a.size))
+    return _free_energy_profile_uncertainties(_capi.load().me_mbar_histogram_gram_samples, _host_samples(device, e, r, t), t.size, f,
+                                              targets, (_capi.double_ptr(a),), edges, g)
+
+
 def get_equilibration_points(df, device=None):
     """Per column ``[t0, g, Neff_max]``; constant columns are skipped and complex columns split into ``_real`` /
     ``_imag`` (statistics.py:25-48).  With ``device`` set, all columns go to the GPU in one batch."""

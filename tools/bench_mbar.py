@@ -8,6 +8,9 @@
                                                      column count, profiles/mbar_observable_uncertainty.txt)
     python tools/bench_mbar.py --profile            (reweighted histograms along an observable beside the one-column observable
                                                      reweighting, profiles/mbar_profile.txt)
+    python tools/bench_mbar.py --profile-uncertainty --rungs 8 32
+                                                    (the error bars of those histograms beside the histograms themselves,
+                                                     profiles/mbar_profile_uncertainty.txt)
 
 Per ladder size K: synthetic energies of a 16-dimensional quadratic form (E / T Gamma(8) distributed) on T_k = 0.5 r^k with
 r chosen so that the ladder spans the same range for every K, injected with set_energy_samples; one warm-up solve, then a
@@ -230,6 +233,56 @@ def time_profile(k, log2_chains, records, n_targets=8, bins=(64, 256)):
                   flush=True)
 
 
+def time_profile_uncertainty(k, log2_chains, records, n_targets=8, bins=(64, 256), forced_rows=0):
+    """me_mbar_histogram_gram (csrc/me_mbar_hist_cov.hip) on the two inputs of :func:`time_profile`, beside me_mbar_histogram on
+    the same samples in the same run.  Whole calls.  The new call holds the histogram's own kernels, ``n_targets ceil((K + 1) /
+    R)`` passes of the slot Gram kernel (R rows of the weight matrix per pass: 16, 8 or 4 by the bin count) where the
+    histogram takes ``ceil(n_targets / 4)``, and the Gram pass of the K ladder columns; ``sums`` is the same call without that
+    last pass and without the host algebra (the C entry point with ladder_gram = NULL).  ``forced_rows``: the R of a library
+    built with ``-DME_HIST_COV_ROWS=R`` (selected with METROPOLIS_HIP_LIB), for the pass counts that are printed."""
+    import ctypes
+    eng, _ = loaded_engine(k, log2_chains, records)
+    n = records << log2_chains
+    f = eng.ladder_free_energies(tol=1e-8)["f"]
+    targets = np.geomspace(0.5, 3.0, n_targets)
+    dp = ctypes.POINTER(ctypes.c_double)
+
+    def best(call, repeats=3):
+        call()                                                  # warm-up: allocations, code objects
+        times = []
+        for _ in range(repeats):
+            t0 = time.perf_counter()
+            call()
+            times.append(time.perf_counter() - t0)
+        return 1e3 * min(times)
+
+    energies = eng.energy_samples()
+    eng.record_observables([0])
+    eng.set_energy_samples(energies)
+    chain = np.arange(eng.n_chains)
+    inputs = (("every value in one bin", np.full(eng.n_chains, 0.5)),
+              ("consecutive samples in 64 different bins", (chain % 64) + 0.5))
+    print("K = %d, %d samples, %d targets" % (k, n, n_targets), flush=True)
+    for label, row in inputs:
+        eng.set_observable_samples(np.broadcast_to(row[None, None, :], (records, 1, eng.n_chains)))
+        print("    %s" % label, flush=True)
+        for b in bins:
+            edges = np.linspace(0.0, float(b), b + 1)
+            rows = forced_rows or next((r for r in (16, 8) if 4 * (8 * (b + 1) + 32 * r * (b + 3)) <= 160 * 1024), 4)   # rows_per_pass
+            out = eng.free_energy_profile_uncertainties(0, edges, targets, f)
+            assert out["counts"].sum() == n and np.all(np.isfinite(out["d_mass"]))
+            h = np.zeros((n_targets, k + 1, b + 3))
+            sums = best(lambda: eng._check(eng._lib.me_mbar_histogram_gram(
+                eng._handle, f.ctypes.data_as(dp), targets.ctypes.data_as(dp), n_targets, 0, edges.ctypes.data_as(dp), b,
+                h.ctypes.data_as(dp), None, None, None, None, None, None)))
+            whole = best(lambda: eng.free_energy_profile_uncertainties(0, edges, targets, f))
+            plain = best(lambda: eng.free_energy_profile(0, edges, targets, f))
+            passes, plain_passes = n_targets * -(-(k + 1) // rows), -(-n_targets // 4)
+            print("        %3d bins: free_energy_profile %.3f ms (%d passes); slot Gram sums %.3f ms (R = %d: %d more passes) = %.2f x, "
+                  "%.3f ms per added pass; free_energy_profile_uncertainties %.3f ms = %.2f x"
+                  % (b, plain, plain_passes, sums, rows, passes, sums / plain, (sums - plain) / passes, whole, whole / plain), flush=True)
+
+
 def time_reference(k, log2_samples):
     n = 1 << log2_samples
     temps = ladder(k)
@@ -273,9 +326,15 @@ if __name__ == "__main__":
     ap.add_argument("--observables", action="store_true")
     ap.add_argument("--observable-gram", action="store_true")
     ap.add_argument("--profile", action="store_true")
+    ap.add_argument("--profile-uncertainty", action="store_true")
+    ap.add_argument("--rows-per-pass", type=int, default=0, help="with --profile-uncertainty: the R of a -DME_HIST_COV_ROWS=R library")
     cli = ap.parse_args()
     if cli.profile:
         time_profile(8, cli.log2_chains, cli.records)
+        sys.exit(0)
+    if cli.profile_uncertainty:
+        for k in cli.rungs:
+            time_profile_uncertainty(k, cli.log2_chains, cli.records, forced_rows=cli.rows_per_pass)
         sys.exit(0)
     if cli.observable_gram:
         for k in cli.rungs:
