@@ -498,9 +498,27 @@ int me_mbar_energy_shift(me_engine *engine, double *shift);
  *                       slot_gram[t][j][s] is bit for bit the same run to run, whatever other temperatures are asked for, and
  *                       through me_mbar_histogram_gram_samples on the same samples in the same order.  Arguments are checked
  *                       and errors reported exactly as by me_mbar_histogram.
- *   me_mbar_histogram_gram_samples  the same on host arrays, like me_mbar_histogram_samples. */
+ *   me_mbar_histogram_gram_samples  the same on host arrays, like me_mbar_histogram_samples.
+ *   me_mbar_histogram_joint        the JOINT reweighted histogram of two quantities A (x) and B (y) with the weights of
+ *                       me_mbar_histogram (csrc/me_mbar_hist2d.hip has the definition).  column_x, column_y: as
+ *                       me_mbar_histogram's column, each a recorded column or -1 for the energy; the same column may be given
+ *                       twice (only the diagonal fills).  Each axis has its own edges[n_bins + 1], checked as there, and the
+ *                       slot rule of me_mbar_histogram: slot_x in [0, n_bins_x + 3), slot_y in [0, n_bins_y + 3) (bins, below,
+ *                       above, NaN).  A used sample falls into exactly one of the (n_bins_x + 3)(n_bins_y + 3) cells, cell =
+ *                       slot_x (n_bins_y + 3) + slot_y, and their number must not exceed ME_MAX_HISTOGRAM2D_SLOTS (33 x 33
+ *                       bins; ME_ERR_INVALID otherwise).  mass is [n][n_bins_x + 3][n_bins_y + 3], the sum of w per cell divided
+ *                       by the total over all cells, so that a temperature's masses sum to 1; counts [n_bins_x + 3][n_bins_y +
+ *                       3] the used samples per cell; neff_fraction [n] as me_mbar_reweight's.  Any output may be NULL.  A cell
+ *                       without a sample has mass exactly 0.  No floating-point atomics: all sums have a fixed order, and a
+ *                       mass is bit for bit the same run to run, whether its temperature is asked for alone or among any number
+ *                       of others, and through me_mbar_histogram_joint_samples on the same samples in the same order.  The
+ *                       free-energy surface is F(A, B; T) = -T ln(mass / (bin width x) (bin width y)).  Errors as for
+ *                       me_mbar_histogram.
+ *   me_mbar_histogram_joint_samples  the same kernels on host arrays; values_x[n_samples] and values_y[n_samples] hold A and B of
+ *                       every sample. */
 #define ME_MAX_RECORDED_OBSERVABLES 16
 #define ME_MAX_HISTOGRAM_BINS 256
+#define ME_MAX_HISTOGRAM2D_SLOTS 1296
 int me_observable_samples_enable(me_engine *engine, const int32_t *indices, int32_t n_observables);
 int me_observable_samples_info(me_engine *engine, int32_t *n_observables, int32_t *indices);
 int me_observable_samples_get(me_engine *engine, int64_t record_begin, int64_t n_records, double *dst);
@@ -531,6 +549,13 @@ int me_mbar_histogram_gram_samples(int32_t device_id, const double *energies, co
                                    const double *values, const double *edges, int32_t n_bins, double *slot_gram,
                                    double *ladder_gram, double *column_counts, double *mass, int64_t *counts,
                                    double *neff_fraction, int64_t *n_used);
+int me_mbar_histogram_joint(me_engine *engine, const double *f, const double *temps, int32_t n, int32_t column_x,
+                        const double *edges_x, int32_t n_bins_x, int32_t column_y, const double *edges_y, int32_t n_bins_y,
+                        double *mass, int64_t *counts, double *neff_fraction);
+int me_mbar_histogram_joint_samples(int32_t device_id, const double *energies, const int32_t *rungs, int64_t n_samples,
+                                const double *ladder_temps, int32_t n_rungs, const double *f, const double *temps, int32_t n,
+                                const double *values_x, const double *values_y, const double *edges_x, int32_t n_bins_x,
+                                const double *edges_y, int32_t n_bins_y, double *mass, int64_t *counts, double *neff_fraction);
 
 /* Text of the last error on this engine (or of the last failed me_create when engine is NULL). */
 int me_last_error(me_engine *engine, char *buf, size_t buf_bytes);

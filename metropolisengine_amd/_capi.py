@@ -164,6 +164,11 @@ SYMBOLS = {
                                                       ctypes.c_int32, _dp, _dp, ctypes.c_int32, _dp, _dp, ctypes.c_int32, _dp, _dp,
                                                       _dp, _dp, ctypes.POINTER(ctypes.c_int64), _dp,
                                                       ctypes.POINTER(ctypes.c_int64)]),
+    "me_mbar_histogram_joint": (ctypes.c_int, [_H, _dp, _dp, ctypes.c_int32, ctypes.c_int32, _dp, ctypes.c_int32, ctypes.c_int32, _dp,
+                                           ctypes.c_int32, _dp, ctypes.POINTER(ctypes.c_int64), _dp]),
+    "me_mbar_histogram_joint_samples": (ctypes.c_int, [ctypes.c_int32, _dp, ctypes.POINTER(ctypes.c_int32), ctypes.c_int64, _dp,
+                                                   ctypes.c_int32, _dp, _dp, ctypes.c_int32, _dp, _dp, _dp, ctypes.c_int32, _dp,
+                                                   ctypes.c_int32, _dp, ctypes.POINTER(ctypes.c_int64), _dp]),
 }
 
 

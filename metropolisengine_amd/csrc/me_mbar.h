@@ -1,6 +1,7 @@
 // What the MBAR units share (me_mbar.hip: samples, solve, reweighting; me_mbar_cov.hip: the Gram matrix of the weight matrix
 // for the asymptotic covariance; me_mbar_obs.hip: recorded observables and their reweighting; me_mbar_hist.hip: reweighted
-// histograms along an observable; me_mbar_hist_cov.hip: the slot Gram sums behind their error bars): the tile policy, the
+// histograms along an observable; me_mbar_hist_cov.hip: the slot Gram sums behind their error bars; me_mbar_hist2d.hip: joint
+// histograms along two): the tile policy, the
 // device table of a ladder, the per-sample sums, and the host scaffolding of an entry point, which me_mbar.hip defines: where
 // the samples come from (Source), the prepared problem (Problem, prepare) and the argument checks.  Private to the host side,
 // like me_engine.h.

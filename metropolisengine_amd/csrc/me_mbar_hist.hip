@@ -22,8 +22,8 @@
 //                        end, and NO atomic touches a floating-point number.
 //   k_mbar_hist_sum      block (slot, t): the block partials of one cell in a fixed order; the integer counts.
 //   k_mbar_hist_normalise  block t: the total over the slots in a fixed order, then the division.
-// (slot_of, steps 1 to 3 below as slot_accumulate, and k_mbar_hist_sum live in me_mbar_slots.h: me_mbar_hist_cov.hip fills
-// its tables by the same code.)
+// (slot_of, steps 1 to 3 below as slot_accumulate, k_mbar_hist_sum and k_mbar_hist_normalise live in me_mbar_slots.h:
+// me_mbar_hist_cov.hip and me_mbar_hist2d.hip fill their tables by the same code.)
 // How a wavefront adds the 64 weights of one item of the tile into its table, all lanes active throughout (the loop condition
 // is a ballot, wave-uniform; no cross-lane operation ever runs under a partial lane mask):
 //   0. every lane adds 1 to its slot's count with an integer LDS atomic (integers: exact in any order);
@@ -120,20 +120,6 @@ __global__ void __launch_bounds__(kThreads) k_mbar_hist(const double *__restrict
     for (int k = 0; k < kWaves; ++k) sum += s_count[k * n_slots + c];
     count_partials[(size_t)blockIdx.x * n_slots + c] = sum;
   }
-}
-
-// block t: mass[t][slot] = sums[t][slot] / (the sum over all slots, in a fixed order)
-__global__ void __launch_bounds__(kThreads) k_mbar_hist_normalise(int n_slots, double *mass) {
-  __shared__ double waves[kWaves];
-  double *row = mass + (size_t)blockIdx.x * n_slots;
-  double v = 0.0;
-  for (int s = threadIdx.x; s < n_slots; s += kThreads) v = v + row[s];
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) waves[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double total = waves[0];
-  for (int k = 1; k < kWaves; ++k) total = total + waves[k];
-  for (int s = threadIdx.x; s < n_slots; s += kThreads) row[s] = row[s] / total;
 }
 
 }  // namespace

@@ -1,6 +1,7 @@
-// The device side that the two histogram units share (me_mbar_hist.hip: the reweighted masses; me_mbar_hist_cov.hip: the slot
-// Gram sums behind their error bars): the slot of a value, the wavefront-private accumulation of one item's 64 samples into
-// a table [rows][n_slots] in LDS, and the reduction of the block partials.  me_mbar_hist.hip's header describes the scheme
+// The device side that the histogram units share (me_mbar_hist.hip: the reweighted masses; me_mbar_hist_cov.hip: the slot
+// Gram sums behind their error bars; me_mbar_hist2d.hip: the joint masses of two quantities, whose "slot" is a cell of the
+// grid): the slot of a value, the wavefront-private accumulation of one item's 64 samples into a table [rows][n_slots] in LDS,
+// the reduction of the block partials and the normalisation of a row.  me_mbar_hist.hip's header describes the scheme
 // and its summation order; nothing here depends on what a row of the table means (a temperature there, a column of the weight
 // matrix in me_mbar_hist_cov.hip), and the order in which a cell (row, slot) receives its terms depends on the samples' slots
 // and order alone, not on the number of rows.
@@ -114,6 +115,20 @@ __global__ void __launch_bounds__(kThreads) k_mbar_hist_sum(const double *partia
   for (int k = 1; k < kWaves; ++k) sum = sum + waves[k];
   sums[(size_t)t * n_slots + s] = sum;
   if (counts && t == 0) counts[s] = (long long)total;
+}
+
+// block t: mass[t][slot] = sums[t][slot] / (the sum over all slots, in a fixed order)
+__global__ void __launch_bounds__(kThreads) k_mbar_hist_normalise(int n_slots, double *mass) {
+  __shared__ double waves[kWaves];
+  double *row = mass + (size_t)blockIdx.x * n_slots;
+  double v = 0.0;
+  for (int s = threadIdx.x; s < n_slots; s += kThreads) v = v + row[s];
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) waves[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double total = waves[0];
+  for (int k = 1; k < kWaves; ++k) total = total + waves[k];
+  for (int s = threadIdx.x; s < n_slots; s += kThreads) row[s] = row[s] / total;
 }
 
 }  // namespace

@@ -851,6 +851,33 @@ class MetropolisEngine:
         out["name"] = name
         return out
 
+    def free_energy_surface(self, which_x, edges_x, which_y, edges_y, temps, f=None):
+        """The joint reweighted histogram of two recorded quantities and the free-energy surface ``F(A, B; T) = -T ln p(A, B;
+        T)`` over them at each temperature of ``temps`` (``me_mbar_histogram_joint``, on the device: the samples stay there).
+        ``which_x``, ``which_y``: as :meth:`free_energy_profile`'s ``which`` -- a name of :attr:`recorded_observables`, an
+        index into the recorded columns, or ``"energy"``; the same quantity may be given twice.  Each axis has edges of its
+        own as there, and the ``(Bx + 3)(By + 3)`` cells may not exceed 1296 (33 x 33 bins).  ``f``: the free energies of
+        :meth:`ladder_free_energies` (solved with the defaults when ``None``).
+
+        Every sample with a finite energy falls into exactly one cell: per axis a bin, *below*, *above* or *not a number* by
+        the rule of :meth:`free_energy_profile`.  Returns ``{"temps", "names", "edges_x", "edges_y", "centers_x",
+        "centers_y", "widths_x", "widths_y", "mass", "density", "free_energy", "mass_slots", "outside", "counts",
+        "counts_slots", "neff_fraction"}``, see :func:`metropolisengine_amd.statistics.mbar_free_energy_surface`; ``names`` is
+        the pair of the axes' names.  Bitwise reproducible, and a temperature's table does not depend on which others are asked
+        for.  ``ValueError`` for bad edges, too many cells, an unknown name, an index outside the recorded columns and empty,
+        non-finite or non-positive ``temps``; raises without a ladder or without records."""
+        from . import statistics
+        temps = statistics.validate_mbar_temps(temps)
+        edges_x, edges_y = statistics.validate_histogram2d_edges(edges_x, edges_y)
+        (column_x, name_x), (column_y, name_y) = self._profile_column(which_x), self._profile_column(which_y)
+        if f is None:
+            f = self.ladder_free_energies()["f"]
+        f = self._ladder_f(f, finite=False)
+        out = statistics._free_energy_surface(self._lib.me_mbar_histogram_joint, (self._handle,), f, temps, (column_x,), edges_x,
+                                              (column_y,), edges_y)
+        out["names"] = (name_x, name_y)
+        return out
+
     def _profile_column(self, which):
         """``(column of the C ABI, name)`` of the quantity a profile runs along: -1 for ``"energy"``."""
         if isinstance(which, str) and which == "energy":

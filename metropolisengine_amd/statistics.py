@@ -327,6 +327,79 @@ def mbar_free_energy_profile(energies, rungs, temps, f, targets, values, edges, 
                                 (_capi.double_ptr(a),), edges)
 
 
+MBAR_MAX_HISTOGRAM2D_SLOTS = 1296       # cells (Bx + 3)(By + 3) of a joint histogram: 33 x 33 bins (ME_MAX_HISTOGRAM2D_SLOTS)
+
+
+def validate_histogram2d_edges(edges_x, edges_y):
+    """The edges of both axes of a joint histogram, each as :func:`validate_histogram_edges` returns them; ``ValueError`` also
+    when the ``(Bx + 3)(By + 3)`` cells exceed 1296 (33 x 33 bins)."""
+    ex, ey = validate_histogram_edges(edges_x), validate_histogram_edges(edges_y)
+    if (ex.size + 2) * (ey.size + 2) > MBAR_MAX_HISTOGRAM2D_SLOTS:
+        raise ValueError("a joint histogram holds at most %d cells (Bx + 3)(By + 3), e.g. 33 x 33 bins; got %d x %d bins"
+                         % (MBAR_MAX_HISTOGRAM2D_SLOTS, ex.size - 1, ey.size - 1))
+    return ex, ey
+
+
+def _surface_result(temps, edges_x, edges_y, mass, counts, neff):
+    """``mass`` ``(T, Bx + 3, By + 3)`` and ``counts`` ``(Bx + 3, By + 3)`` as ``me_mbar_histogram_joint`` returns them."""
+    bx, by = edges_x.size - 1, edges_y.size - 1
+    widths_x, widths_y = np.diff(edges_x), np.diff(edges_y)
+    inner = mass[:, :bx, :by].copy()
+    density = inner / (widths_x[:, None] * widths_y[None, :])
+    with np.errstate(divide="ignore"):
+        free_energy = -temps[:, None, None] * np.log(density)
+    free_energy[inner == 0] = np.inf
+    # every cell outside the inner grid, in a fixed order: the outer rows (below, above, NaN on x), then the outer columns of
+    # the inner rows
+    outside = mass[:, bx:, :].reshape(temps.size, -1).sum(axis=1) + mass[:, :bx, by:].reshape(temps.size, -1).sum(axis=1)
+    return {"temps": temps, "edges_x": edges_x, "edges_y": edges_y, "centers_x": 0.5 * (edges_x[:-1] + edges_x[1:]),
+            "centers_y": 0.5 * (edges_y[:-1] + edges_y[1:]), "widths_x": widths_x, "widths_y": widths_y, "mass": inner,
+            "density": density, "free_energy": free_energy, "mass_slots": mass, "outside": outside,
+            "counts": counts[:bx, :by].copy(), "counts_slots": counts, "neff_fraction": neff}
+
+
+def _free_energy_surface(fn, lead, f, targets, middle_x, edges_x, middle_y, edges_y):
+    """``middle_x`` / ``middle_y``: the engine form's column of an axis, given in front of that axis's edges (the host form passes
+    both value arrays in ``middle_x`` and nothing in ``middle_y``)."""
+    bx, by = edges_x.size - 1, edges_y.size - 1
+    mass, counts = np.zeros((targets.size, bx + 3, by + 3)), np.zeros((bx + 3, by + 3), dtype=np.int64)
+    neff = np.zeros(targets.size)
+    _call(fn, lead, _capi.double_ptr(f), _capi.double_ptr(targets), targets.size, *middle_x, _capi.double_ptr(edges_x), bx,
+          *middle_y, _capi.double_ptr(edges_y), by, _capi.double_ptr(mass), _capi.int64_ptr(counts), _capi.double_ptr(neff))
+    return _surface_result(targets, edges_x, edges_y, mass, counts, neff)
+
+
+def mbar_free_energy_surface(energies, rungs, temps, f, targets, values_x, edges_x, values_y, edges_y, device=0):
+    """The joint reweighted histogram of ``values_x`` and ``values_y`` (one value of each per sample, in the order of
+    ``energies``) and the free-energy surface ``F(A, B; T) = -T ln p(A, B; T)`` at the temperatures ``targets``, from the samples
+    of a ladder (``temps``, free energies ``f`` of :func:`mbar_free_energies`) on the host (``me_mbar_histogram_joint_samples``; the
+    engine form is ``MetropolisEngine.free_energy_surface``).  Each axis has edges of its own as in
+    :func:`mbar_free_energy_profile`, and the ``(Bx + 3)(By + 3)`` cells may not exceed 1296 (33 x 33 bins).
+
+    Every sample with a finite ENERGY falls into exactly one cell ``(slot_x, slot_y)``, each slot by the rule of
+    :func:`mbar_free_energy_profile` along its axis: the bins, then *below*, *above* (a value ON the last edge is above) and
+    *not a number*.
+
+    Returns ``{"temps", "edges_x", "edges_y", "centers_x", "centers_y", "widths_x", "widths_y", "mass", "density",
+    "free_energy", "mass_slots", "outside", "counts", "counts_slots", "neff_fraction"}``: ``mass`` ``(T, Bx, By)`` the
+    reweighted probability of every cell of the inner grid, ``density = mass / (widths_x[:, None] * widths_y[None, :])``,
+    ``free_energy = -T ln density`` (``+inf`` where the mass is 0), ``mass_slots`` ``(T, Bx + 3, By + 3)`` the full table (it
+    sums to 1; its sums over an axis are the 1-D masses of the other with their below / above / NaN slots), ``outside``
+    ``(T,)`` the mass outside the inner grid, ``counts`` ``(Bx, By)`` and ``counts_slots`` ``(Bx + 3, By + 3)`` the samples per
+    cell, ``neff_fraction`` as :func:`mbar_reweight`'s.  The sums have a fixed order: bitwise reproducible, and a temperature's
+    table does not depend on which others are asked for."""
+    e, r, t = validate_mbar_samples(energies, rungs, temps)
+    targets = validate_mbar_temps(targets, "targets")
+    f = validate_mbar_f(f, t.size)
+    edges_x, edges_y = validate_histogram2d_edges(edges_x, edges_y)
+    a = np.ascontiguousarray(np.asarray(values_x, dtype=np.float64).ravel())
+    b = np.ascontiguousarray(np.asarray(values_y, dtype=np.float64).ravel())
+    if a.size != e.size or b.size != e.size:
+        raise ValueError("values_x and values_y need one entry per sample (%d), got %d and %d" % (e.size, a.size, b.size))
+    return _free_energy_surface(_capi.load().me_mbar_histogram_joint_samples, _host_samples(device, e, r, t), f, targets,
+                                (_capi.double_ptr(a), _capi.double_ptr(b)), edges_x, (), edges_y)
+
+
 MBAR_GRAM_MAX_COLUMNS = 128     # columns of the weight matrix per device pass (csrc/me_mbar_cov.hip)
 
 

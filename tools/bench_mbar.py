@@ -11,6 +11,8 @@
     python tools/bench_mbar.py --profile-uncertainty --rungs 8 32
                                                     (the error bars of those histograms beside the histograms themselves,
                                                      profiles/mbar_profile_uncertainty.txt)
+    python tools/bench_mbar.py --surface            (joint histograms along two observables on 8 x 8, 16 x 16 and 33 x 33 bins
+                                                     beside the 1-D histograms, profiles/mbar_surface.txt)
 
 Per ladder size K: synthetic energies of a 16-dimensional quadratic form (E / T Gamma(8) distributed) on T_k = 0.5 r^k with
 r chosen so that the ladder spans the same range for every K, injected with set_energy_samples; one warm-up solve, then a
@@ -283,6 +285,65 @@ def time_profile_uncertainty(k, log2_chains, records, n_targets=8, bins=(64, 256
                   % (b, plain, plain_passes, sums, rows, passes, sums / plain, (sums - plain) / passes, whole, whole / plain), flush=True)
 
 
+def surface_rows(n_cells):
+    """rows_per_pass of csrc/me_mbar_hist2d.hip: the temperatures per pass, from the number of cells alone."""
+    return 4 if n_cells <= 374 else 2 if n_cells <= 666 else 1
+
+
+def time_surface(k, log2_chains, records, n_targets=8, grids=(8, 16, 33), bins=(64, 256), forced_rows=0):
+    """me_mbar_histogram_joint (csrc/me_mbar_hist2d.hip) for two recorded columns at ``n_targets`` temperatures on square grids,
+    beside me_mbar_histogram (64 and 256 bins) on the same samples in the same run, on the two kinds of input of
+    :func:`time_profile`: every sample in ONE cell (a wavefront's 64 lanes share it) and consecutive samples in 64 DIFFERENT
+    cells (an 8 x 8 block of the grid; 64 different bins for the 1-D call).  Whole calls (counting pass, table upload,
+    allocations, every launch, the copy back and the wait); the joint call holds me_mbar_reweight's kernels, the pass that writes
+    d_n and ceil(T / R) passes that each read 32 bytes per sample, R = 4, 2 or 1 by the number of cells.  ``forced_rows``: the R
+    of a library built with ``-DME_HIST2D_ROWS=R`` (selected with METROPOLIS_HIP_LIB), for the pass counts that are printed."""
+    eng, _ = loaded_engine(k, log2_chains, records)
+    n = records << log2_chains
+    f = eng.ladder_free_energies(tol=1e-8)["f"]
+    targets = np.geomspace(0.5, 3.0, n_targets)
+
+    def best(call, repeats=3):
+        call()                                                  # warm-up: allocations, code objects
+        times = []
+        for _ in range(repeats):
+            t0 = time.perf_counter()
+            call()
+            times.append(time.perf_counter() - t0)
+        return 1e3 * min(times)
+
+    energies = eng.energy_samples()
+    eng.record_observables([0, 1, 2])                           # columns: x, y, and the 1-D call's value
+    eng.set_energy_samples(energies)
+    chain = np.arange(eng.n_chains)
+    half = np.full(eng.n_chains, 0.5)
+    inputs = (("every sample in one cell", np.stack([half, half, half])),
+              ("consecutive samples in 64 different cells", np.stack([(chain % 64) // 8 + 0.5, (chain % 8) + 0.5, (chain % 64) + 0.5])))
+    print("K = %d, %d samples, %d targets" % (k, n, n_targets), flush=True)
+    for label, rows in inputs:
+        eng.set_observable_samples(np.broadcast_to(rows[None, :, :], (records, 3, eng.n_chains)))
+        print("    %s" % label, flush=True)
+        filled = 1 if label.startswith("every") else 64
+        plain = {}
+        for b in bins:
+            edges = np.linspace(0.0, float(b), b + 1)
+            out = eng.free_energy_profile(2, edges, targets, f)
+            assert int((out["counts"] > 0).sum()) == filled and out["counts"].sum() == n
+            plain[b] = best(lambda: eng.free_energy_profile(2, edges, targets, f))
+            print("        %3d bins: free_energy_profile %.3f ms (%d passes of 24 bytes per sample)" % (b, plain[b], -(-n_targets // 4)),
+                  flush=True)
+        for g in grids:
+            edges = np.linspace(0.0, float(g), g + 1)
+            out = eng.free_energy_surface(0, edges, 1, edges, targets, f)
+            assert int((out["counts"] > 0).sum()) == filled and out["counts"].sum() == n
+            assert np.max(np.abs(out["mass"].reshape(n_targets, -1).sum(axis=1) - 1.0)) <= 1e-13
+            r = forced_rows or surface_rows((g + 3) * (g + 3))
+            ms = best(lambda: eng.free_energy_surface(0, edges, 1, edges, targets, f))
+            print("        %2d x %2d bins (%4d cells, R = %d: %d passes of 32 bytes per sample): free_energy_surface %.3f ms = %s"
+                  % (g, g, (g + 3) * (g + 3), r, -(-n_targets // r), ms,
+                     ", ".join("%.2f x the %d-bin profile" % (ms / plain[b], b) for b in bins)), flush=True)
+
+
 def time_reference(k, log2_samples):
     n = 1 << log2_samples
     temps = ladder(k)
@@ -327,8 +388,14 @@ if __name__ == "__main__":
     ap.add_argument("--observable-gram", action="store_true")
     ap.add_argument("--profile", action="store_true")
     ap.add_argument("--profile-uncertainty", action="store_true")
-    ap.add_argument("--rows-per-pass", type=int, default=0, help="with --profile-uncertainty: the R of a -DME_HIST_COV_ROWS=R library")
+    ap.add_argument("--surface", action="store_true")
+    ap.add_argument("--rows-per-pass", type=int, default=0, help="with --profile-uncertainty: the R of a -DME_HIST_COV_ROWS=R library; "
+                    "with --surface: of a -DME_HIST2D_ROWS=R library")
+    ap.add_argument("--grids", type=int, nargs="*", default=[8, 16, 33], help="with --surface: the bins per axis")
     cli = ap.parse_args()
+    if cli.surface:
+        time_surface(8, cli.log2_chains, cli.records, grids=cli.grids, forced_rows=cli.rows_per_pass)
+        sys.exit(0)
     if cli.profile:
         time_profile(8, cli.log2_chains, cli.records)
         sys.exit(0)
