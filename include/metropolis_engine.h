@@ -361,6 +361,15 @@ int me_set_population_families(me_engine *engine, int64_t chain_begin, int64_t n
  *                       change, *iterations the count, n_used[k] the finite samples of rung k (non-finite energies are
  *                       skipped).  All sums have a fixed order: a solve is bitwise reproducible.  ME_ERR_STATE without a
  *                       ladder, without records, or when a rung has no finite sample; ME_ERR_UNSUPPORTED beyond 64 rungs.
+ *   me_mbar_solve_newton       the same free energies by Newton's method (csrc/me_mbar_newton.hip has the iteration): two
+ *                       self-consistent passes, then Newton steps f <- f + H^-1 (N - S) with H = diag(S) - W^T W formed on
+ *                       the matrix cores in the same pass over the samples; a Newton step after which gamma = max_k |S_k /
+ *                       N_k - 1| did not fall is withdrawn and a failed Cholesky factorisation skipped, each in favour of a
+ *                       self-consistent step (*fallback_steps counts both, *newton_steps the Newton steps taken).  Every pass
+ *                       over the samples counts as an iteration; tolerance, max_iterations, *residual, n_used and the error
+ *                       codes as for me_mbar_solve; *gradient is gamma at the last pass.  Converges quadratically where
+ *                       me_mbar_solve converges linearly, at about the rounding error of f.  Bitwise reproducible.  Any
+ *                       output pointer but f_out may be NULL.  me_mbar_solve_newton_samples: the same on host arrays.
  *   me_mbar_reweight           for each of the n target temperatures (finite, > 0), from f of me_mbar_solve: ln_z =
  *                       ln Z(T) / Z(T_0), the mean and variance of the energy at T and neff_fraction = (sum w)^2 / (N sum w^2)
  *                       of the reweighting weights w (N = all finite samples).  Any output pointer may be NULL.
@@ -393,6 +402,12 @@ int me_energy_samples_get(me_engine *engine, int64_t record_begin, int64_t n_rec
 int me_energy_samples_set(me_engine *engine, int64_t n_records, const double *src);
 int me_mbar_solve(me_engine *engine, double tolerance, int32_t max_iterations, double *f_out, int32_t *iterations,
                   double *residual, int64_t *n_used_out);
+int me_mbar_solve_newton(me_engine *engine, double tolerance, int32_t max_iterations, double *f_out, int32_t *iterations,
+                         double *residual, double *gradient, int32_t *newton_steps, int32_t *fallback_steps, int64_t *n_used_out);
+int me_mbar_solve_newton_samples(int32_t device_id, const double *energies, const int32_t *rungs, int64_t n_samples,
+                                 const double *ladder_temps, int32_t n_rungs, double tolerance, int32_t max_iterations,
+                                 double *f_out, int32_t *iterations, double *residual, double *gradient, int32_t *newton_steps,
+                                 int32_t *fallback_steps, int64_t *n_used_out);
 int me_mbar_reweight(me_engine *engine, const double *f, const double *temps, int32_t n, double *ln_z, double *mean_e,
                      double *var_e, double *neff_fraction);
 int me_mbar_solve_samples(int32_t device_id, const double *energies, const int32_t *rungs, int64_t n_samples,

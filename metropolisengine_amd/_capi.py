@@ -129,6 +129,13 @@ SYMBOLS = {
     "me_energy_samples_set": (ctypes.c_int, [_H, ctypes.c_int64, _dp]),
     "me_mbar_solve": (ctypes.c_int, [_H, ctypes.c_double, ctypes.c_int32, _dp, ctypes.POINTER(ctypes.c_int32), _dp,
                                      ctypes.POINTER(ctypes.c_int64)]),
+    "me_mbar_solve_newton": (ctypes.c_int, [_H, ctypes.c_double, ctypes.c_int32, _dp, ctypes.POINTER(ctypes.c_int32), _dp, _dp,
+                                            ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                            ctypes.POINTER(ctypes.c_int64)]),
+    "me_mbar_solve_newton_samples": (ctypes.c_int, [ctypes.c_int32, _dp, ctypes.POINTER(ctypes.c_int32), ctypes.c_int64, _dp,
+                                                    ctypes.c_int32, ctypes.c_double, ctypes.c_int32, _dp,
+                                                    ctypes.POINTER(ctypes.c_int32), _dp, _dp, ctypes.POINTER(ctypes.c_int32),
+                                                    ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64)]),
     "me_mbar_reweight": (ctypes.c_int, [_H, _dp, _dp, ctypes.c_int32, _dp, _dp, _dp, _dp]),
     "me_mbar_solve_samples": (ctypes.c_int, [ctypes.c_int32, _dp, ctypes.POINTER(ctypes.c_int32), ctypes.c_int64, _dp,
                                              ctypes.c_int32, ctypes.c_double, ctypes.c_int32, _dp,

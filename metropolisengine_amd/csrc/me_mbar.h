@@ -1,4 +1,4 @@
-// What the MBAR units share (me_mbar.hip: samples, solve, reweighting; me_mbar_cov.hip: the Gram matrix of the weight matrix
+// What the MBAR units share (me_mbar.hip: samples, solve, reweighting; me_mbar_newton.hip: the Newton solve; me_mbar_cov.hip: the Gram matrix of the weight matrix
 // for the asymptotic covariance; me_mbar_obs.hip: recorded observables and their reweighting; me_mbar_hist.hip: reweighted
 // histograms along an observable; me_mbar_hist_cov.hip: the slot Gram sums behind their error bars; me_mbar_hist2d.hip: joint
 // histograms along two): the tile policy, the
@@ -70,7 +70,8 @@ __device__ __forceinline__ long long obs_offset(const ObsColumns &oc, long long 
 // both from prepare.  Operations with target temperatures: `inv_temps` (double, 1 / T_t) and `out` (double), both sized by
 // upload_targets; `out` holds 4 doubles per target behind reweight_enqueue (me_mbar.hip, me_mbar_cov.hip) and [mean | var |
 // cov][target][column], then neff[target], in me_mbar_obs.hip.  reweight_enqueue alone: `moments` (Moments [block][kTargets]).
-// The solve alone: `partials` (double [block][rung]) and `control` (MbarControl).
+// The solve alone: `partials` (double [block][rung]) and `control` (MbarControl); the Newton solve (me_mbar_newton.hip) keeps its
+// own partials [block][K + K (K + 1) / 2] and control words, which begin with an MbarControl, in the same two.
 struct Work {
   DeviceBuffer table, partials, inv_temps, out, moments, counts, control;
 };

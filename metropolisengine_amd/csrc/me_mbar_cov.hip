@@ -60,21 +60,19 @@
 // registers (2 where the LDS of 16 observables decides), no scratch; no other kernel of this file uses scratch.
 #include "me_launch.h"
 #include "me_mbar.h"
+#include "me_mbar_gram_tiles.h"
 
 namespace me {
 namespace mbar {
 namespace {
 
 constexpr int kMaxCols = 128;                   // columns of W per launch
-constexpr int kSub = 16;                        // samples per sub-tile in LDS
 constexpr int kSlots = 9;                       // 16 x 16 tiles of G per wavefront: 36 lower-triangle tiles / 4
 constexpr int kColB = 0, kColG = kMaxCols, kColMean = 2 * kMaxCols, kColShift = 3 * kMaxCols, kColDoubles = 3 * kMaxCols + 1;
 // the observable form's column constants: [b | g | normaliser | shift of the column | observable of the column, -1: none], then S_q
 constexpr int kColOwnShift = 3 * kMaxCols, kColWhich = 4 * kMaxCols, kColShifts = 5 * kMaxCols;
 constexpr int kObsColDoubles = 5 * kMaxCols + ME_MAX_RECORDED_OBSERVABLES;
 constexpr int kObsStride = kThreads + 1;        // doubles between two observables of the parked samples (odd: see the header)
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 // counts[tile] = the finite energies of the tile
 __global__ void __launch_bounds__(kThreads) k_mbar_used_tiles(const double *__restrict__ energies, long long n, unsigned int *counts) {
@@ -269,7 +267,8 @@ __global__ void __launch_bounds__(kThreads) k_mbar_gram(const double *__restrict
   __shared__ int c_which[kObs ? kMaxCols : 1];
   double *const s_a = w_lds + 2 * kSub * cp;
   const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int h4 = lane >> 4, j16 = lane & 15;                     // the MFMA's (k, i / j) of this lane
+  const Fragment fr = fragment_of(lane);                         // the MFMA's (k, i / j) of this lane
+  const int j16 = fr.j16;
   const int tn = (n_cols + 15) >> 4, n_pairs = tn * (tn + 1) / 2;
   if (t < kMaxCols) {
     c_b[t] = cols[kColB + t];
@@ -285,12 +284,7 @@ __global__ void __launch_bounds__(kThreads) k_mbar_gram(const double *__restrict
   int off_i[kSlots], off_j[kSlots];
 #pragma unroll
   for (int s = 0; s < kSlots; ++s) {
-    const int p = wave + kWaves * s;
-    int I = 0;
-#pragma unroll
-    for (int q = 1; q < kMaxCols / 16; ++q) I = p >= q * (q + 1) / 2 ? q : I;
-    off_i[s] = 16 * I;
-    off_j[s] = 16 * (p - I * (I + 1) / 2);
+    pair_offsets(wave + kWaves * s, kMaxCols / 16, off_i[s], off_j[s]);
   }
   f64x4 acc[kSlots];
 #pragma unroll
@@ -346,11 +340,11 @@ __global__ void __launch_bounds__(kThreads) k_mbar_gram(const double *__restrict
         __syncthreads();
 #pragma unroll 2
         for (int ks = 0; ks < kSub / 4; ++ks) {
-          const double *src = buf + (4 * ks + h4) * cp + j16;
+          const double *src = fragment_source(buf, ks, cp, fr);
 #pragma unroll
           for (int s = 0; s < kSlots; ++s)
             if (wave + kWaves * s < n_pairs)                      // (wave-uniform)
-              acc[s] = __builtin_amdgcn_mfma_f64_16x16x4f64(src[off_i[s]], src[off_j[s]], acc[s], 0, 0, 0);
+              acc[s] = gram_mfma(src[off_i[s]], src[off_j[s]], acc[s]);
         }
         parity ^= 1;                                             // the next fill goes to the other buffer: no second barrier
       }
@@ -360,11 +354,7 @@ __global__ void __launch_bounds__(kThreads) k_mbar_gram(const double *__restrict
 #pragma unroll
   for (int s = 0; s < kSlots; ++s) {
     if (wave + kWaves * s >= n_pairs) continue;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int gi = off_i[s] + h4 + 4 * r, gj = off_j[s] + j16;
-      if (gi < n_cols && gj <= gi) dst[gi * (gi + 1) / 2 + gj] = acc[s][r];
-    }
+    store_lower_tile(dst, off_i[s], off_j[s], fr, n_cols, acc[s]);
   }
 }
 
@@ -382,11 +372,6 @@ __global__ void __launch_bounds__(kMaxCols) k_mbar_gram_finish(const double *__r
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------
-int padded_row(int n_cols) {
-  const int cpad = (n_cols + 15) / 16 * 16;
-  return cpad % 32 == 0 ? cpad + 16 : cpad;
-}
-
 // The used samples of a problem alone, in their order, with their observable columns (the rungs are in the counts already):
 // the problem's own arrays when every energy is finite, a packed copy otherwise.
 struct UsedSamples {

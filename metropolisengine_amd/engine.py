@@ -667,16 +667,22 @@ class MetropolisEngine:
             raise ValueError("samples must be (records, n_chains = %d)" % self.n_chains)
         self._check(self._lib.me_energy_samples_set(self._handle, a.shape[0], _as_double_ptr(a)))
 
-    def ladder_free_energies(self, tol=1e-10, max_iter=10000):
+    def ladder_free_energies(self, tol=1e-10, max_iter=10000, method="self-consistent"):
         """MBAR over the recorded energies of a ladder engine (``me_mbar_solve``, on the device): ``{"f", "ln_z",
         "iterations", "residual", "converged", "n_samples"}`` with ``f[k] = -ln Z(T_k) / Z(T_0)``, ``ln_z = -f``, the
         iterations taken, the last largest change of an ``f[k]``, whether it met ``tol``, and the finite samples of every
         rung (non-finite energies are skipped).  Bitwise reproducible.  ``ValueError`` unless ``tol > 0`` and ``max_iter >=
-        1``; raises without a ladder, without records, or when a rung has no finite sample."""
+        1``; raises without a ladder, without records, or when a rung has no finite sample.  ``method="newton"`` takes
+        Newton steps after two self-consistent ones (``me_mbar_solve_newton``: quadratic convergence; every pass over the
+        samples is an iteration) and adds ``gradient`` (``max_k |S_k / N_k - 1|`` at the last pass), ``newton_steps`` and
+        ``fallback_steps``; any other ``method`` is a ``ValueError``."""
         from . import statistics
+        method = statistics.validate_mbar_method(method)
         tol, max_iter = statistics.validate_mbar_solve(tol, max_iter)
         k = ctypes.c_int32()
         self._check(self._lib.me_temperature_ladder(self._handle, None, 0, ctypes.byref(k)))
+        if method == "newton":
+            return statistics._solve_newton(self._lib.me_mbar_solve_newton, (self._handle,), max(k.value, 1), tol, max_iter)
         return statistics._solve(self._lib.me_mbar_solve, (self._handle,), max(k.value, 1), tol, max_iter)
 
     def _ladder_f(self, f, finite):

@@ -93,6 +93,16 @@ def validate_mbar_solve(tol, max_iter):
     return tol, int(max_iter)
 
 
+MBAR_METHODS = ("self-consistent", "newton")
+
+
+def validate_mbar_method(method):
+    """``method`` of an MBAR solve; ``ValueError`` unless it is one of ``MBAR_METHODS``.  Runs before the library is touched."""
+    if method not in MBAR_METHODS:
+        raise ValueError("method must be one of %s, not %r" % (", ".join(repr(m) for m in MBAR_METHODS), method))
+    return method
+
+
 def validate_mbar_temps(temps, what="temps"):
     """Temperatures as a contiguous 1-D float64 array: non-empty, finite and > 0 (``ValueError`` otherwise)."""
     t = np.ascontiguousarray(np.atleast_1d(np.asarray(temps, dtype=np.float64)))
@@ -152,6 +162,19 @@ def _solve(fn, lead, n_rungs, tol, max_iter):
     return _solve_result(f, its.value, res.value, n_used, tol)
 
 
+def _solve_newton(fn, lead, n_rungs, tol, max_iter):
+    """``_solve`` through ``me_mbar_solve_newton`` / ``_samples``: the same dictionary with ``gradient`` (``max_k |S_k / N_k -
+    1|`` at the last pass), ``newton_steps`` and ``fallback_steps`` added."""
+    f, n_used = np.zeros(n_rungs), np.zeros(n_rungs, dtype=np.int64)
+    its, res, grad = ctypes.c_int32(), ctypes.c_double(), ctypes.c_double()
+    newton, fallback = ctypes.c_int32(), ctypes.c_int32()
+    _call(fn, lead, tol, max_iter, _capi.double_ptr(f), ctypes.byref(its), ctypes.byref(res), ctypes.byref(grad), ctypes.byref(newton),
+          ctypes.byref(fallback), _capi.int64_ptr(n_used))
+    out = _solve_result(f, its.value, res.value, n_used, tol)
+    out.update(gradient=float(grad.value), newton_steps=int(newton.value), fallback_steps=int(fallback.value))
+    return out
+
+
 def _reweight_result(temps, ln_z, mean, var, neff):
     return {"temps": temps, "ln_z": ln_z, "energy_mean": mean, "energy_var": var, "heat_capacity": var / (temps * temps),
             "neff_fraction": neff}
@@ -163,14 +186,19 @@ def _reweight(fn, lead, f, targets):
     return _reweight_result(targets, *out)
 
 
-def mbar_free_energies(energies, rungs, temps, tol=1e-10, max_iter=10000, device=0):
+def mbar_free_energies(energies, rungs, temps, tol=1e-10, max_iter=10000, device=0, method="self-consistent"):
     """MBAR free energies of a temperature ladder from samples on the host (``me_mbar_solve_samples``; the engine form is
     ``MetropolisEngine.ladder_free_energies``).  ``energies[i]`` was sampled at ``temps[rungs[i]]``.  Returns
     ``{"f", "ln_z", "iterations", "residual", "converged", "n_samples"}``: ``f[k] = -ln Z(T_k) / Z(T_0)``, ``ln_z = -f``,
     ``n_samples[k]`` the finite energies of rung ``k`` (the others are skipped).  For samples gathered from several GPU
-    shards and for subsets of a run; a rung without a finite sample raises."""
+    shards and for subsets of a run; a rung without a finite sample raises.  ``method="newton"`` solves by Newton's method
+    (``me_mbar_solve_newton_samples``: quadratic convergence, every pass over the samples an iteration) and adds ``gradient``,
+    ``newton_steps`` and ``fallback_steps`` to the dictionary; any other ``method`` is a ``ValueError``."""
+    method = validate_mbar_method(method)
     tol, max_iter = validate_mbar_solve(tol, max_iter)
     e, r, t = validate_mbar_samples(energies, rungs, temps)
+    if method == "newton":
+        return _solve_newton(_capi.load().me_mbar_solve_newton_samples, _host_samples(device, e, r, t), t.size, tol, max_iter)
     return _solve(_capi.load().me_mbar_solve_samples, _host_samples(device, e, r, t), t.size, tol, max_iter)
 
 

@@ -13,6 +13,8 @@
                                                      profiles/mbar_profile_uncertainty.txt)
     python tools/bench_mbar.py --surface            (joint histograms along two observables on 8 x 8, 16 x 16 and 33 x 33 bins
                                                      beside the 1-D histograms, profiles/mbar_surface.txt)
+    python tools/bench_mbar.py --newton             (the Newton solver beside the self-consistent one: one pass and the whole
+                                                     solve, profiles/mbar_newton.txt)
 
 Per ladder size K: synthetic energies of a 16-dimensional quadratic form (E / T Gamma(8) distributed) on T_k = 0.5 r^k with
 r chosen so that the ladder spans the same range for every K, injected with set_energy_samples; one warm-up solve, then a
@@ -344,6 +346,61 @@ def time_surface(k, log2_chains, records, n_targets=8, grids=(8, 16, 33), bins=(
                      ", ".join("%.2f x the %d-bin profile" % (ms / plain[b], b) for b in bins)), flush=True)
 
 
+def time_newton(k, log2_chains, records, dim=DIM, ratio=None):
+    """One pass and the whole solve of me_mbar_solve_newton (csrc/me_mbar_newton.hip) beside me_mbar_solve on the same samples
+    in the same run.  A pass = (wall time of a solve limited to b passes - one limited to a passes) / (b - a) at a tolerance no
+    iterate meets, which leaves the counting pass, the allocations and the read-backs out: for Newton the pass kernel, the sum
+    of the block partials and the one-wavefront update (a = 3: Newton passes only), for the self-consistent solver
+    k_mbar_weights and k_mbar_update.  Beside them me_mbar_gram without targets (k_mbar_gram over the K ladder columns), a
+    WHOLE call: its counting pass, minimum pass, k_mbar_gram, the finish kernel and the copy of G; the pair "k_mbar_weights plus
+    a ladder-only k_mbar_gram pass" is the self-consistent pass plus this call.  ``ratio``: T_k = 0.5 ratio^k instead of the
+    ladder that spans 0.5 ... 0.5 1.3^7."""
+    import ctypes
+    n = 1 << log2_chains
+    temps = ladder(k) if ratio is None else 0.5 * ratio ** np.arange(k)
+    eng = me.MetropolisEngine(me.IsoQuadratic(1.0), None, [0.1], None, n_chains=n, seed=3, dtype="f64", temperatures=temps)
+    eng.record_energies(records)
+    rng = np.random.default_rng(1)
+    eng.set_energy_samples(rng.gamma(dim / 2.0, 1.0, size=(records, n)) * np.repeat(temps, n // k)[None, :])
+
+    def best(call, repeats=3):
+        call()                                                  # warm-up: allocations, code objects
+        times = []
+        for _ in range(repeats):
+            t0 = time.perf_counter()
+            call()
+            times.append(time.perf_counter() - t0)
+        return 1e3 * min(times)
+
+    def per_pass(method, a, b):
+        few = best(lambda: eng.ladder_free_energies(tol=1e-300, max_iter=a, method=method))
+        many = best(lambda: eng.ladder_free_energies(tol=1e-300, max_iter=b, method=method))
+        return (many - few) / (b - a)
+
+    newton_pass, plain_pass = per_pass("newton", 3, 19), per_pass("self-consistent", 1, 33)
+    f = eng.ladder_free_energies(tol=1e-10, method="newton")["f"]
+    dp = ctypes.POINTER(ctypes.c_double)
+    gram, counts = np.zeros((k, k)), np.zeros(k)
+    gram_call = best(lambda: eng._check(eng._lib.me_mbar_gram(eng._handle, f.ctypes.data_as(dp), None, 0, gram.ctypes.data_as(dp),
+                                                               counts.ctypes.data_as(dp), None, None, None)))
+    print("K = %2d, dim %d, T_k / T_k-1 = %.4f, %d samples: Newton pass %.3f ms; self-consistent pass %.3f ms; ladder-only "
+          "me_mbar_gram call %.3f ms; Newton pass / (self-consistent pass + Gram call) = %.2f, / self-consistent pass = %.2f"
+          % (k, dim, temps[1] / temps[0], records << log2_chains, newton_pass, plain_pass, gram_call,
+             newton_pass / (plain_pass + gram_call), newton_pass / plain_pass), flush=True)
+    line = "       whole solve to tol 1e-10:"
+    for method in ("newton", "self-consistent"):
+        out = eng.ladder_free_energies(tol=1e-10, method=method)
+        ms = best(lambda: eng.ladder_free_energies(tol=1e-10, method=method), repeats=2)
+        line += " %s %.2f ms, %d iterations, residual %.1e%s;" % (
+            method, ms, out["iterations"], out["residual"],
+            ", gradient %.1e, %d fallback passes" % (out["gradient"], out["fallback_steps"]) if method == "newton" else "")
+        if method == "newton":
+            newton_ms, f_newton = ms, out["f"]
+        else:
+            line += " self-consistent / Newton = %.2f; max |f - f_Newton| = %.1e" % (ms / newton_ms, np.max(np.abs(out["f"] - f_newton)))
+    print(line, flush=True)
+
+
 def time_reference(k, log2_samples):
     n = 1 << log2_samples
     temps = ladder(k)
@@ -389,10 +446,16 @@ if __name__ == "__main__":
     ap.add_argument("--profile", action="store_true")
     ap.add_argument("--profile-uncertainty", action="store_true")
     ap.add_argument("--surface", action="store_true")
+    ap.add_argument("--newton", action="store_true")
     ap.add_argument("--rows-per-pass", type=int, default=0, help="with --profile-uncertainty: the R of a -DME_HIST_COV_ROWS=R library; "
                     "with --surface: of a -DME_HIST2D_ROWS=R library")
     ap.add_argument("--grids", type=int, nargs="*", default=[8, 16, 33], help="with --surface: the bins per axis")
     cli = ap.parse_args()
+    if cli.newton:
+        for k in (8, 32, 64):
+            time_newton(k, cli.log2_chains, cli.records)
+        time_newton(16, cli.log2_chains, max(1, cli.records // 32), dim=64, ratio=1.35)     # the poorly overlapping ladder
+        sys.exit(0)
     if cli.surface:
         time_surface(8, cli.log2_chains, cli.records, grids=cli.grids, forced_rows=cli.rows_per_pass)
         sys.exit(0)
