@@ -572,6 +572,37 @@ int me_mbar_histogram_joint_samples(int32_t device_id, const double *energies, c
                                 const double *values_x, const double *values_y, const double *edges_x, int32_t n_bins_x,
                                 const double *edges_y, int32_t n_bins_y, double *mass, int64_t *counts, double *neff_fraction);
 
+/* Statistical inefficiencies of the recorded series, pooled over the chains of a rung (no reference counterpart; csrc/
+ * me_series.hip has the definition): the multiple-series estimator of Chodera et al., JCTC 3:26 (2007), the number the
+ * `inefficiency` of every MBAR error bar asks for.  A slot keeps its rung whatever configuration was swapped into it, so the
+ * records of slot c are a stationary series at the temperature of rung c / M.  For one column (column 0: the energy; column 1 +
+ * q: recorded observable q) and one rung with R records of each of its M chains, a chain is USED when all R of its values in the
+ * column are finite; over the M_u used chains, with d = a - mean:
+ *     mean = sum_c sum_n a_c[n] / (M_u R)              P(t) = sum_c sum_{n = 0}^{R - t - 1} d_c[n] d_c[n + t]
+ *     var  = P(0) / (M_u R)                            C(t) = P(t) R / (P(0) (R - t))
+ *     g    = max(1, 1 + 2 sum_{t = 1}^{stop - 1} C(t) (1 - t / R))
+ * with stop the first t > mintime at which C(t) <= 0, or max_lag + 1 when there is none up to max_lag (terms C(t) <= 0 at t <=
+ * mintime are added): for one chain this is metropolisengine_amd.statistics.statistical_inefficiency with fast=False.
+ *   me_recorded_inefficiency   over the engine's stores: K = the ladder's rungs and M = n_chains / K, or K = 1 and M = n_chains on
+ *                       an engine without a ladder; Q = the recorded observable columns.  mintime >= 0; max_lag in [1, R - 2],
+ *                       or 0 for R - 2 (ME_ERR_INVALID otherwise).  Outputs, each [1 + Q][K] and each may be NULL: g, mean, var,
+ *                       stop_lag, chains_used (M_u); acf is [1 + Q][K][max_lag + 1] with acf[t] = C(t) for t <= min(stop,
+ *                       max_lag) and NaN beyond.  A (column, rung) without a used chain (mean and var NaN as well) or with P(0) =
+ *                       0 reports g = NaN, stop_lag = 0 and acf NaN; the call still succeeds.  The lags are computed 64 at a
+ *                       time and the call ends with the batch in which the last walk stops; no result depends on that.  No
+ *                       floating-point atomics: every sum has a fixed order that depends on (R, M) alone, so a call is bitwise
+ *                       reproducible, a smaller max_lag gives the bitwise prefix, and a non-finite value changes nothing but its
+ *                       own (column, rung).  ME_ERR_STATE without an energy store or with fewer than 3 records.
+ *   me_series_inefficiency_samples   the same kernels on a host array series[n_records][n_series], one column: the groups are
+ *                       consecutive runs of group_chains series, group_chains a multiple of 64 that divides n_series
+ *                       (ME_ERR_INVALID otherwise, and for n_records < 3); outputs [n_series / group_chains] and acf
+ *                       [n_series / group_chains][max_lag + 1].  Bit for bit me_recorded_inefficiency on the same values. */
+int me_recorded_inefficiency(me_engine *engine, int32_t mintime, int32_t max_lag, double *g, double *mean, double *var,
+                             int32_t *stop_lag, int64_t *chains_used, double *acf);
+int me_series_inefficiency_samples(int32_t device_id, const double *series, int64_t n_records, int64_t n_series,
+                                   int64_t group_chains, int32_t mintime, int32_t max_lag, double *g, double *mean, double *var,
+                                   int32_t *stop_lag, int64_t *chains_used, double *acf);
+
 /* Text of the last error on this engine (or of the last failed me_create when engine is NULL). */
 int me_last_error(me_engine *engine, char *buf, size_t buf_bytes);
 

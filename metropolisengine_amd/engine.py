@@ -710,9 +710,13 @@ class MetropolisEngine:
         over the recorded samples; see :func:`metropolisengine_amd.statistics.mbar_uncertainties` for the dictionary).  The
         formula assumes independent samples: pass the statistical inefficiency of the energy series
         (:func:`metropolisengine_amd.statistics.statistical_inefficiency`) as ``inefficiency`` (finite, ``>= 1``) and every
-        variance is multiplied by it.  ``ValueError`` for invalid ``targets`` or ``inefficiency``; raises like
-        :meth:`ladder_free_energies` without a ladder or without records."""
+        variance is multiplied by it.  ``inefficiency="recorded"`` takes it from the records themselves: the largest energy
+        ``g`` over the rungs of :meth:`recorded_inefficiency` (deliberately conservative: one scalar has to serve every rung).
+        ``ValueError`` for invalid ``targets`` or ``inefficiency``; raises like :meth:`ladder_free_energies` without a ladder or
+        without records."""
         from . import statistics
+        if isinstance(inefficiency, str):
+            inefficiency = self._recorded_g(inefficiency, [()])[0]
         g = statistics.validate_mbar_inefficiency(inefficiency)
         if targets is not None:
             targets = statistics.validate_mbar_temps(targets, "targets")
@@ -841,9 +845,13 @@ class MetropolisEngine:
         :func:`metropolisengine_amd.statistics.mbar_free_energy_profile_uncertainties`: the error of a barrier height ``F_b -
         F_b'`` at temperature ``t`` is ``T sqrt(C[b, b] + C[b', b'] - 2 C[b, b'])`` with ``C = log_mass_cov[t]``.
         ``inefficiency``: the statistical inefficiency of the recorded series, a finite scalar ``>= 1`` that multiplies every
-        variance.  ``ValueError`` as :meth:`free_energy_profile` and for an invalid ``inefficiency``; raises without a ladder or
-        without records."""
+        variance, or ``"recorded"``: the largest ``g`` of :meth:`recorded_inefficiency` over the rungs and over the energy (the
+        weights depend on it) and ``which`` (the slots do); deliberately conservative.  ``ValueError`` as
+        :meth:`free_energy_profile` and for an invalid ``inefficiency``; raises without a ladder or without records."""
         from . import statistics
+        if isinstance(inefficiency, str):
+            column = self._profile_column(which)[0]
+            inefficiency = self._recorded_g(inefficiency, [() if column < 0 else (column,)])[0]
         g = statistics.validate_profile_inefficiency(inefficiency)
         temps = statistics.validate_mbar_temps(temps)
         edges = statistics.validate_histogram_edges(edges)
@@ -908,19 +916,62 @@ class MetropolisEngine:
         over the recorded samples on the matrix cores): ``{"temps", "names", "mean", "d_mean", "mean_cov", "ln_z", "d_ln_z",
         "n_samples"}``, see :func:`metropolisengine_amd.statistics.mbar_observable_uncertainties`.  ``f``: the free energies of
         :meth:`ladder_free_energies` (solved with the defaults when ``None``).  ``inefficiency``: the statistical inefficiency
-        of the recorded series, a scalar or one entry per recorded column (finite, ``>= 1``).  ``ValueError`` for invalid
-        ``temps`` or ``inefficiency`` and without an observable store; raises without a ladder or without records."""
+        of the recorded series, a scalar or one entry per recorded column (finite, ``>= 1``), or ``"recorded"``: per column the
+        largest ``g`` of :meth:`recorded_inefficiency` over the rungs and over the energy (the weights depend on it) and the
+        column itself; deliberately conservative.  ``ValueError`` for invalid ``temps`` or ``inefficiency`` and without an
+        observable store; raises without a ladder or without records."""
         from . import statistics
         temps = statistics.validate_mbar_temps(temps)
         names = self.recorded_observables
         if not names:
             raise ValueError("no observable store: call record_observables first")
+        if isinstance(inefficiency, str):
+            inefficiency = self._recorded_g(inefficiency, [(q,) for q in range(len(names))])
         g = statistics.validate_mbar_observable_inefficiency(inefficiency, len(names))
         if f is None:
             f = self.ladder_free_energies()["f"]
         f = self._ladder_f(f, finite=True)
         k = max(f.size, 1)      # (the ladder's rungs; without a ladder the library refuses before it writes)
         return statistics._observable_uncertainties(self._lib.me_mbar_gram_observables, (self._handle,), k, f, temps, names, g)
+
+    # ------------------------------------------------------------------ statistical inefficiency of the recorded series
+    def recorded_inefficiency(self, mintime=3, max_lag=None):
+        """The statistical inefficiency ``g = 1 + 2 tau`` of the recorded series, per column and rung, pooled over the chains of
+        the rung (``me_recorded_inefficiency``, on the device: the stores stay there).  The records are successive states of
+        Metropolis chains and never independent; a slot keeps its rung whatever configuration a swap put there, so the records
+        of slot ``c`` are a stationary series at ``T[c // M]``, the series MBAR's samples come from.  The estimator is the
+        multiple-series one of Chodera et al., JCTC 3:26 (2007), see
+        :func:`metropolisengine_amd.statistics.series_inefficiency` for the formulas, ``mintime`` and ``max_lag``.
+
+        Returns ``{"names": ("energy", *recorded_observables), "g", "tau" (= (g - 1) / 2), "mean", "var", "stop_lag",
+        "chains_used"}``, each ``(1 + Q, K)``, ``"acf"`` ``(1 + Q, K, max_lag + 1)`` and ``"n_records"``.  Works without a ladder
+        too: ``K = 1`` and the rung is the whole engine.  A chain with a non-finite value in a column is left out of that column
+        (``chains_used``); a (column, rung) without a chain or without variance has ``g`` NaN.  Bitwise reproducible.
+        ``ValueError`` for a bad ``mintime`` or ``max_lag``; raises without an energy store or with fewer than 3 records."""
+        from . import statistics
+        rows = self.n_energy_records
+        if rows >= 3:
+            mintime, max_lag = statistics.validate_series_lags(rows, mintime, max_lag)
+        else:                   # (the library refuses, and says why)
+            mintime, max_lag = 0, 1
+        names = ("energy",) + self.recorded_observables
+        ladder = self.temperatures
+        out = statistics._series_inefficiency(self._lib.me_recorded_inefficiency, (self._handle,), len(names),
+                                              1 if ladder is None else ladder.size, rows, mintime, max_lag)
+        out["names"] = names
+        return out
+
+    def _recorded_g(self, inefficiency, columns):
+        """``inefficiency="recorded"`` of the uncertainty methods: for each entry of ``columns`` (a tuple of recorded columns)
+        the largest ``g`` of :meth:`recorded_inefficiency` over the rungs, over the energy and over those columns."""
+        if inefficiency != "recorded":
+            raise ValueError("inefficiency must be a number or \"recorded\", not %r" % (inefficiency,))
+        g = self.recorded_inefficiency()["g"]
+        out = np.array([float(np.max(g[[0] + [1 + q for q in entry]])) for entry in columns])
+        if not np.all(np.isfinite(out)):
+            raise ValueError("inefficiency=\"recorded\": a recorded series it needs has no statistical inefficiency (no chain "
+                             "with finite values only, or no variance); see recorded_inefficiency()")
+        return out
 
     # ------------------------------------------------------------------ scalar temperature and population annealing
     def set_temp(self, temp):

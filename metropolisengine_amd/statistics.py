@@ -77,6 +77,65 @@ def detect_equilibration_batch(series, fast=True, nskip=1, device=0):
     return t0, g, neff
 
 
+def validate_series_lags(n_records, mintime, max_lag):
+    """``(mintime, max_lag)`` of a pooled inefficiency as ints: ``mintime >= 0``; ``max_lag`` in ``[1, n_records - 2]``, ``None``
+    for ``n_records - 2``.  ``ValueError`` otherwise and for fewer than 3 records.  Runs before the library is touched."""
+    if n_records < 3:
+        raise ValueError("a statistical inefficiency needs at least 3 records, got %d" % n_records)
+    if int(mintime) != mintime or int(mintime) < 0:
+        raise ValueError("mintime must be an integer >= 0")
+    if max_lag is None:
+        max_lag = n_records - 2
+    if int(max_lag) != max_lag or not 1 <= int(max_lag) <= n_records - 2:
+        raise ValueError("max_lag must be an integer in [1, records - 2 = %d]" % (n_records - 2))
+    return int(mintime), int(max_lag)
+
+
+def _series_inefficiency(fn, lead, n_columns, n_groups, n_records, mintime, max_lag):
+    """One call of either C form (``lead``: the engine's handle, or the device and the host array) and its dictionary."""
+    shape = (n_columns, n_groups)
+    g, mean, var = np.empty(shape), np.empty(shape), np.empty(shape)
+    stop, used = np.zeros(shape, dtype=np.int32), np.zeros(shape, dtype=np.int64)
+    acf = np.empty(shape + (max_lag + 1,))
+    _call(fn, lead, mintime, max_lag, _capi.double_ptr(g), _capi.double_ptr(mean), _capi.double_ptr(var), _capi.int32_ptr(stop),
+          _capi.int64_ptr(used), _capi.double_ptr(acf))
+    return {"g": g, "tau": (g - 1.0) / 2.0, "mean": mean, "var": var, "stop_lag": stop, "chains_used": used, "acf": acf,
+            "n_records": int(n_records)}
+
+
+def series_inefficiency(series, group_chains=None, mintime=3, max_lag=None, device=0):
+    """The statistical inefficiency ``g = 1 + 2 tau`` of MANY series of one stationary process, pooled over the series of a
+    group, on the GPU (``me_series_inefficiency_samples``): the multiple-series estimator of Chodera et al., JCTC 3:26 (2007),
+    pymbar's ``statisticalInefficiencyMultiple``.  ``series`` is ``(R, n_series)``, record-major like
+    :meth:`MetropolisEngine.energy_samples`; the groups are consecutive runs of ``group_chains`` series (a multiple of 64 that
+    divides ``n_series``; ``None``: one group).  A series is USED when all its ``R`` values are finite; over the ``M_u`` used
+    series of a group, with ``d = a - mean``::
+
+        mean = sum_c sum_n a_c[n] / (M_u R)            P(t) = sum_c sum_{n < R - t} d_c[n] d_c[n + t]
+        var  = P(0) / (M_u R)                          C(t) = P(t) R / (P(0) (R - t))
+        g    = max(1, 1 + 2 sum_{t = 1}^{stop - 1} C(t) (1 - t / R))
+
+    with ``stop`` the first ``t > mintime`` at which ``C(t) <= 0``, or ``max_lag + 1`` when there is none up to ``max_lag``
+    (``None``: ``R - 2``): for one series this is :func:`statistical_inefficiency` with ``fast=False``.  Returns ``{"g", "tau",
+    "mean", "var", "stop_lag", "chains_used"}``, each ``(1, groups)`` (the leading axis is the column axis of
+    :meth:`MetropolisEngine.recorded_inefficiency`), ``"acf"`` ``(1, groups, max_lag + 1)`` with ``C(t)`` up to ``min(stop,
+    max_lag)`` and NaN beyond, and ``"n_records"``.  A group without a used series or with zero variance has ``g`` NaN.  Bitwise
+    reproducible.  ``ValueError`` for fewer than 3 records and a bad ``group_chains``, ``mintime`` or ``max_lag``."""
+    a = np.ascontiguousarray(series, dtype=np.float64)
+    if a.ndim != 2 or a.shape[1] < 1:
+        raise ValueError("series must be (records, n_series)")
+    n_records, n_series = a.shape
+    mintime, max_lag = validate_series_lags(n_records, mintime, max_lag)
+    if group_chains is None:
+        group_chains = n_series
+    group_chains = int(group_chains)
+    if group_chains < 64 or group_chains % 64 or n_series % group_chains:
+        raise ValueError("group_chains must be a multiple of 64 that divides n_series = %d" % n_series)
+    return _series_inefficiency(_capi.load().me_series_inefficiency_samples,
+                                (int(device), _capi.double_ptr(a), n_records, n_series, group_chains), 1, n_series // group_chains,
+                                n_records, mintime, max_lag)
+
+
 # ---------------------------------------------------------------------------------------------- MBAR over a ladder
 # (no reference counterpart; the reference reaches for the same library family, pymbar, in its post-processing)
 MBAR_MAX_RUNGS = 64

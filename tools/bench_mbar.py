@@ -15,6 +15,8 @@
                                                      beside the 1-D histograms, profiles/mbar_surface.txt)
     python tools/bench_mbar.py --newton             (the Newton solver beside the self-consistent one: one pass and the whole
                                                      solve, profiles/mbar_newton.txt)
+    python tools/bench_mbar.py --inefficiency       (statistical inefficiencies of the recorded series with 0, 4 and 16 recorded
+                                                     columns beside the host route, profiles/mbar_inefficiency.txt)
 
 Per ladder size K: synthetic energies of a 16-dimensional quadratic form (E / T Gamma(8) distributed) on T_k = 0.5 r^k with
 r chosen so that the ladder spans the same range for every K, injected with set_energy_samples; one warm-up solve, then a
@@ -401,6 +403,62 @@ def time_newton(k, log2_chains, records, dim=DIM, ratio=None):
     print(line, flush=True)
 
 
+def time_inefficiency(k, log2_chains, records, columns=(0, 4, 16), phi=0.9):
+    """me_recorded_inefficiency (csrc/me_series.hip) over the energy store and Q recorded columns: the whole call as users make
+    it (the walks stop where the autocorrelation first turns non-positive, so only the first batches of 64 lags are computed)
+    and with every lag up to records - 2 (mintime = records: no walk stops).  Every column is an AR(1) series with coefficient
+    ``phi``.  For scale, the host route on ONE rung: energy_samples() and the pooled estimator in numpy."""
+    n = 1 << log2_chains
+    eng = me.MetropolisEngine(me.IsoQuadratic(1.0), None, [0.1], None, n_chains=n, seed=3, dtype="f64", temperatures=ladder(k))
+    eng.record_energies(records)
+    rng = np.random.default_rng(1)
+    x = np.empty((records, n))
+    x[0] = rng.standard_normal(n)
+    for r in range(1, records):
+        x[r] = phi * x[r - 1] + np.sqrt(1.0 - phi * phi) * rng.standard_normal(n)
+
+    def best(call, repeats=3):
+        call()                                                  # warm-up: allocations, code objects
+        times = []
+        for _ in range(repeats):
+            t0 = time.perf_counter()
+            call()
+            times.append(time.perf_counter() - t0)
+        return 1e3 * min(times)
+
+    for q in columns:
+        eng.record_observables([j % 4 for j in range(q)] if q else None)
+        eng.set_energy_samples(x)
+        if q:
+            eng.set_observable_samples(np.repeat(x[:, None, :], q, axis=1) * (1.0 + 0.125 * np.arange(q))[None, :, None])
+        out = eng.recorded_inefficiency()
+        batches = int(out["stop_lag"].max()) // 64 + 1
+        ms = best(eng.recorded_inefficiency)
+        full_ms = best(lambda: eng.recorded_inefficiency(mintime=records), repeats=1)
+        print("K = %d, %d chains x %d records, Q = %2d: g %.2f ... %.2f (exact %.2f), largest stop lag %d: %d batch(es) of 64 lags "
+              "%.3f ms; all %d lags %.3f ms = %.3f ms per batch and column"
+              % (k, n, records, q, out["g"].min(), out["g"].max(), (1 + phi) / (1 - phi), out["stop_lag"].max(), batches, ms,
+                 records - 2, full_ms, full_ms / ((records - 2) // 64 + 1) / (1 + q)), flush=True)
+    # the host route, one rung of the energy column
+    m = n // k
+    t0 = time.perf_counter()
+    a = eng.energy_samples()[:, :m]
+    copy_ms = 1e3 * (time.perf_counter() - t0)
+    t0 = time.perf_counter()
+    d = a - a.mean()
+    p0 = np.sum(d * d)
+    g, t = 1.0, 1
+    while t < records - 1:
+        c = np.sum(d[:records - t] * d[t:]) * records / (p0 * (records - t))
+        if c <= 0.0 and t > 3:
+            break
+        g += 2.0 * c * (1.0 - t / records)
+        t += 1
+    numpy_ms = 1e3 * (time.perf_counter() - t0)
+    print("host route: energy_samples() %.1f ms (%d MB), then numpy on ONE rung of %d chains %.1f ms to stop lag %d (g = %.2f): "
+          "%.0f ms for %d rungs" % (copy_ms, records * n * 8 >> 20, m, numpy_ms, t, g, copy_ms + k * numpy_ms, k), flush=True)
+
+
 def time_reference(k, log2_samples):
     n = 1 << log2_samples
     temps = ladder(k)
@@ -450,7 +508,11 @@ if __name__ == "__main__":
     ap.add_argument("--rows-per-pass", type=int, default=0, help="with --profile-uncertainty: the R of a -DME_HIST_COV_ROWS=R library; "
                     "with --surface: of a -DME_HIST2D_ROWS=R library")
     ap.add_argument("--grids", type=int, nargs="*", default=[8, 16, 33], help="with --surface: the bins per axis")
+    ap.add_argument("--inefficiency", action="store_true")
     cli = ap.parse_args()
+    if cli.inefficiency:
+        time_inefficiency(8, cli.log2_chains, cli.records)
+        sys.exit(0)
     if cli.newton:
         for k in (8, 32, 64):
             time_newton(k, cli.log2_chains, cli.records)
