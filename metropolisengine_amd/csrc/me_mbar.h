@@ -1,14 +1,15 @@
-// What the MBAR units share (me_mbar.hip: samples, solve, reweighting; me_mbar_newton.hip: the Newton solve; me_mbar_cov.hip: the Gram matrix of the weight matrix
-// for the asymptotic covariance; me_mbar_obs.hip: recorded observables and their reweighting; me_mbar_hist.hip: reweighted
-// histograms along an observable; me_mbar_hist_cov.hip: the slot Gram sums behind their error bars; me_mbar_hist2d.hip: joint
-// histograms along two): the tile policy, the
-// device table of a ladder, the per-sample sums, and the host scaffolding of an entry point, which me_mbar.hip defines: where
-// the samples come from (Source), the prepared problem (Problem, prepare) and the argument checks.  Private to the host side,
-// like me_engine.h.
+// What the MBAR units share (me_mbar.hip: samples, solve, reweighting; me_mbar_newton.hip: the Newton solve; me_mbar_cov.hip:
+// the Gram matrix of the weight matrix for the asymptotic covariance; me_mbar_obs.hip: recorded observables and their
+// reweighting; me_mbar_hist.hip: reweighted histograms along an observable; me_mbar_hist_cov.hip: the slot Gram sums behind
+// their error bars; me_mbar_hist2d.hip: joint histograms along two -- three policies of one pass kernel, me_mbar_slots.h, behind
+// one host driver, histogram_slots): the tile policy, the device table of a ladder, the per-sample sums, and the host
+// scaffolding of an entry point, which me_mbar.hip defines: where the samples come from (Source), the prepared problem (Problem,
+// prepare) and the argument checks.  Private to the host side, like me_engine.h.
 #pragma once
 
 #include <algorithm>
 #include <cmath>
+#include <functional>
 #include <vector>
 
 #include "me_device.h"
@@ -171,14 +172,33 @@ struct Histogram {
   int64_t *counts;
   double *neff;
 };
-// what a histogram leaves on the device for a pass that follows it: d_n of every sample (log_denominator_enqueue), the edges, and
-// `top` of slot_of (me_mbar_slots.h)
+// what a histogram leaves on the device for a pass that follows it: d_n of every sample (log_denominator_enqueue), the edges (of
+// both axes, one after the other, for a joint histogram), and `top` of slot_of (me_mbar_slots.h) for the one or two edge arrays
 struct HistogramScratch {
   DeviceBuffer d, edges;
-  int top = 1;
+  int top = 1, top_y = 1;
 };
-// Prepares `p`, reweights to temps[0 .. n_temps) (afterwards p.w.inv_temps and p.w.out are reweight_enqueue's), fills the
-// histogram of the one column `values` (n_columns = 1) and waits for the stream.  With an empty rung nothing else is computed.
+// A table of n_slots columns for histogram_slots: the host edges (n_edges of them, as the pass kernel reads them), the
+// temperatures per pass, the host outputs mass[n_temps][n_slots], counts[n_slots], neff[n_temps] (each may be nullptr), and
+// `launch`, which enqueues on the problem's stream the unit's pass kernel (slot_pass, me_mbar_slots.h) for the n_rows <= rows
+// temperatures from t0 on (p.w.inv_temps + t0, p.w.out + 4 t0) into partials[block][rows][n_slots]; the pass of t0 = 0 is the
+// one whose count_partials[block][n_slots] are read
+struct SlotTable {
+  const double *edges;
+  int n_edges, n_slots, rows;
+  double *mass;
+  int64_t *counts;
+  double *neff;
+  std::function<void(int t0, int n_rows, double *partials, unsigned long long *count_partials)> launch;
+};
+// The driver of the histogram units: prepares `p`, reweights to temps[0 .. n_temps) (afterwards p.w.inv_temps and p.w.out are
+// reweight_enqueue's), writes d_n and the edges into `keep`, runs one pass per chunk of `rows` temperatures, each followed by the
+// sum of its block partials and the normalisation of its rows, copies back and waits for the stream.  `keep` is filled before
+// the first launch, so `launch` may refer to it.  With an empty rung nothing else is computed and `keep` holds no buffers.
+hipError_t histogram_slots(Problem &p, const Source &src, const double *f, const double *temps, int n_temps, const SlotTable &table,
+                           HistogramScratch &keep);
+// histogram_slots for the one column `values` (n_columns = 1).  keep.top is set from the bin count before anything else,
+// whether or not a rung turns out empty.
 hipError_t histogram(Problem &p, const Source &src, const ObsColumns &values, const double *f, const double *temps, int n_temps,
                      const Histogram &h, HistogramScratch &keep);
 // ME_ERR_INVALID unless 1 <= n_bins <= ME_MAX_HISTOGRAM_BINS and edges[0 .. n_bins] is there, finite and strictly increasing

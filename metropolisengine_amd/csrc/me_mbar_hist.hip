@@ -1,5 +1,6 @@
 // Reweighted histograms of a ladder's samples along one observable (me_mbar_histogram and its engine-less twin in the public
 // header): the distribution p(A; T) at any temperature, from which the free-energy profile F(A; T) = -T ln p(A; T) follows.
+// Also the host driver that the three histogram units share (histogram_slots).
 //
 // Definition.  With the weights of me_mbar_reweight (me_mbar.hip: d_n = m_n + ln s_n, l_nt = -E_n / T_t - d_n; a sample is USED
 // when its ENERGY is finite) every used sample falls into exactly one of n_bins + 3 slots by its value A_n and the n_bins + 1
@@ -15,39 +16,14 @@
 // rounding; the division by the total over ALL slots makes the masses sum to 1 by construction.
 //
 // Kernels.  d_n comes from me_mbar_obs.hip's scratch pass (log_denominator_enqueue: 8 bytes per sample, NaN when unused).
-//   k_mbar_hist          one pass per chunk of kHistTargets = 4 temperatures: reads E_n, d_n, A_n (24 bytes per sample), ONE
-//                        exponential per (sample, temperature).  The edges sit in LDS; a lane finds its slot by a branch-free
-//                        binary search (at most 9 steps for 257 edges).  Each wavefront owns a private LDS table
-//                        [4][n_bins + 3] of doubles and [n_bins + 3] counts; nothing is shared between wavefronts before the
-//                        end, and NO atomic touches a floating-point number.
+//   k_mbar_hist          slot_pass (me_mbar_slots.h, which describes the scheme and the summation order) with Slots1d and
+//                        TemperatureRows<kHistTargets = 4>: one pass per chunk of 4 temperatures reads E_n, d_n, A_n (24 bytes
+//                        per sample), ONE exponential per (sample, temperature).  It counts in every pass (the kernel has no
+//                        switch; k_mbar_hist_sum reads the counts of the first chunk only).
 //   k_mbar_hist_sum      block (slot, t): the block partials of one cell in a fixed order; the integer counts.
 //   k_mbar_hist_normalise  block t: the total over the slots in a fixed order, then the division.
-// (slot_of, steps 1 to 3 below as slot_accumulate, k_mbar_hist_sum and k_mbar_hist_normalise live in me_mbar_slots.h:
-// me_mbar_hist_cov.hip and me_mbar_hist2d.hip fill their tables by the same code.)
-// How a wavefront adds the 64 weights of one item of the tile into its table, all lanes active throughout (the loop condition
-// is a ballot, wave-uniform; no cross-lane operation ever runs under a partial lane mask):
-//   0. every lane adds 1 to its slot's count with an integer LDS atomic (integers: exact in any order);
-//   1. the groups of lanes that share a slot are found one by one: the lowest lane not yet matched names the slot (readlane
-//      with a wave-uniform lane number), a ballot gives the group and its popcount the group's size;
-//   2. a group of more than kDense = 8 lanes is summed at once: wave_sum over the wavefront with +0.0 from the other lanes
-//      (exact), lane 0 adds the four sums to the table.  At most 7 such groups exist among 64 lanes;
-//   3. a lane of a smaller group keeps its rank r inside the group (popcount of the group's lower lanes).  After the match loop
-//      round r = 1 .. (largest such group) lets the lanes of rank r add their own weights to the table themselves: they all
-//      hold DIFFERENT slots, so the plain read-add-write of a round touches every address at most once.
-// The worst cases are bounded: 64 lanes in one bin cost one match round and four wave_sums; 64 lanes in 64 bins cost 64 match
-// rounds (readlane, compare, ballot, popcount, two selects) and ONE round of step 3, not 64 x 4 wave_sums.  Measured at 2^25
-// samples, 8 temperatures, 64 bins (profiles/mbar_profile.txt): 3.2 ms with every value in one bin and 4.2 ms with 64
-// different bins per wavefront; summing EVERY group by wave_sum (kDense = 0) takes 3.3 and 40.3 ms, letting every lane add for
-// itself (kDense = 64) 7.2 and 3.6 ms.
-// Summation order, fixed by the samples' values and order alone: per item the large groups in order of their lowest lane, then
-// the small groups' lanes by rank (lane order inside a group); the items and tiles of a block in order; the block's wavefront
-// tables in wavefront order -> partials[block][t][slot] -> k_mbar_hist_sum, in which lane l adds blocks l, l + 256, ... in
-// order, then the butterfly and the wavefronts in order.  Neither the slots nor the order depend on the temperature, and a
-// temperature's weights are formed by the same instructions at every position of a chunk (`fp contract(off)`, the fused
-// multiply-add spelled out): mass[t][slot] is bit for bit the same run to run, alone or among any number of temperatures, and
-// through the engine's store or host arrays of the same samples in the same order (the values are addressed through strides).
-// Registers and LDS (hipcc -O3, gfx950): see profiles/mbar_profile.txt; no kernel uses scratch.  LDS per workgroup: (n_bins +
-// 1) 8 + 4 (n_bins + 3)(4 x 8 + 4) bytes, 39 352 at 256 bins.
+// Registers and LDS (hipcc -O3, gfx950): see profiles/mbar_profile.txt and profiles/mbar_slot_skeleton.txt; no kernel uses
+// scratch.  LDS per workgroup: (n_bins + 1) 8 + 4 (n_bins + 3)(4 x 8 + 4) bytes, 39 352 at 256 bins.
 #include "me_mbar_slots.h"
 
 #pragma clang fp contract(off)
@@ -57,105 +33,44 @@ namespace mbar {
 namespace {
 
 constexpr int kHistTargets = 4;                 // temperatures per pass
+static_assert(slot_pass_lds(kHistTargets, 256 + 3, 256 + 1, true) == 39352, "the LDS of the header comment");
 
-// values: sample i = record * n_chains + chain sits at values[record * record_stride + chain] (a column of the engine's store:
-// n_chains, Q n_chains; a host array or the energies themselves: n, 0).  `d` is padded to whole tiles.  ln_z has stride 4
-// (reweight_enqueue's out).  Dynamic LDS: [edges | mass[kWaves][kHistTargets][n_slots] | count[kWaves][n_slots]].
+// values: the one value column (slot_pass); ln_z has stride 4 (reweight_enqueue's out)
 __global__ void __launch_bounds__(kThreads) k_mbar_hist(const double *__restrict__ energies, const double *__restrict__ d,
                                                         const double *__restrict__ values, long long n_chains,
                                                         long long record_stride, const double *__restrict__ edges, int n_bins,
                                                         int top, const double *__restrict__ inv_temps,
                                                         const double *__restrict__ ln_z, int n_targets, long long n_tiles,
                                                         double *partials, unsigned long long *count_partials) {
-  extern __shared__ double lds[];
-  const int n_edges = n_bins + 1, n_slots = n_bins + 3;
-  double *s_edges = lds, *s_mass = lds + n_edges;
-  unsigned int *s_count = reinterpret_cast<unsigned int *>(s_mass + kWaves * kHistTargets * n_slots);
-  for (int i = threadIdx.x; i < n_edges; i += kThreads) s_edges[i] = edges[i];
-  for (int i = threadIdx.x; i < kWaves * kHistTargets * n_slots; i += kThreads) s_mass[i] = 0.0;
-  for (int i = threadIdx.x; i < kWaves * n_slots; i += kThreads) s_count[i] = 0u;
-  __syncthreads();
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  double *my_mass = s_mass + wave * kHistTargets * n_slots;
-  unsigned int *my_count = s_count + wave * n_slots;
-  const unsigned long long below_me = (1ull << lane) - 1ull;
-  double inv[kHistTargets], lz[kHistTargets];
-#pragma unroll
-  for (int t = 0; t < kHistTargets; ++t) {
-    inv[t] = t < n_targets ? inv_temps[t] : 0.0;
-    lz[t] = t < n_targets ? ln_z[4 * t] : 0.0;
-  }
-  for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    const long long base = tile * kTile + threadIdx.x;
-    long long record = base / n_chains, chain = base - record * n_chains;
-#pragma unroll 1
-    for (int r = 0; r < kItems; ++r) {
-      const long long i = base + (long long)r * kThreads;
-      const double dn = d[i];                   // (padded: in bounds; NaN beyond n and for an unused sample)
-      int slot = -1;
-      double w[kHistTargets];
-#pragma unroll
-      for (int t = 0; t < kHistTargets; ++t) w[t] = 0.0;
-      if (dn == dn) {
-        const double e = energies[i];
-        slot = slot_of(s_edges, n_edges, top, values[record * record_stride + chain]);
-#pragma unroll
-        for (int t = 0; t < kHistTargets; ++t)
-          if (t < n_targets) w[t] = math64::exp_nonpos(fmin(__builtin_fma(-e, inv[t], -dn) - lz[t], 0.0));
-      }
-      chain += kThreads;
-      while (chain >= n_chains) {
-        chain -= n_chains;
-        record += 1;
-      }
-      if (slot >= 0) atomicAdd(&my_count[slot], 1u);          // (integers: exact in any order)
-      // every lane is active from here on (me_mbar_slots.h)
-      slot_accumulate<kHistTargets>(my_mass, n_slots, n_targets, slot, w, lane, below_me);
-    }
-  }
-  __syncthreads();
-  slot_tables_store(s_mass, kHistTargets, n_targets, n_slots, partials);
-  for (int c = threadIdx.x; c < n_slots; c += kThreads) {
-    unsigned long long sum = 0;
-    for (int k = 0; k < kWaves; ++k) sum += s_count[k * n_slots + c];
-    count_partials[(size_t)blockIdx.x * n_slots + c] = sum;
-  }
+  const Slots1d where{values, n_bins, top};
+  const TemperatureRows<kHistTargets> rows(inv_temps, ln_z, n_targets);
+  slot_pass<kHistTargets, true>(energies, d, n_chains, record_stride, edges, where, rows, 1, n_tiles, partials, count_partials);
 }
 
 }  // namespace
 
-// `values`: one column (n_columns = 1) that goes with the problem's samples
-hipError_t histogram(Problem &p, const Source &src, const ObsColumns &values, const double *f, const double *temps, int n_temps,
-                     const Histogram &h, HistogramScratch &keep) {
+hipError_t histogram_slots(Problem &p, const Source &src, const double *f, const double *temps, int n_temps, const SlotTable &table,
+                           HistogramScratch &keep) {
   ME_MBAR_HIP(prepare(p, src, f));
   if (p.empty_rung >= 0) return hipSuccess;
   Work &w = p.w;
-  const int n_edges = h.n_bins + 1, n_slots = h.n_bins + 3, n_blocks = blocks_of(p.sm.n_samples);
-  const long long n_tiles = tiles_of(p.sm.n_samples);
-  int top = 1;
-  while (2 * top <= n_edges) top *= 2;
-  keep.top = top;
+  const int n_slots = table.n_slots, rows = table.rows, n_blocks = blocks_of(p.sm.n_samples);
   std::vector<double> inv;
-  DeviceBuffer &d = keep.d, &edges = keep.edges;
   DeviceBuffer partials, count_partials, mass, counts;
   ME_MBAR_HIP(reweight_enqueue(p, p.sm, temps, n_temps, inv));      // ln_z and neff_fraction of every target into w.out
-  ME_MBAR_HIP(log_denominator_enqueue(p, p.sm, d));
-  ME_MBAR_HIP(edges.resize((size_t)n_edges * sizeof(double)));
-  ME_MBAR_HIP(partials.resize((size_t)n_blocks * kHistTargets * n_slots * sizeof(double)));
+  ME_MBAR_HIP(log_denominator_enqueue(p, p.sm, keep.d));
+  ME_MBAR_HIP(keep.edges.resize((size_t)table.n_edges * sizeof(double)));
+  ME_MBAR_HIP(partials.resize((size_t)n_blocks * rows * n_slots * sizeof(double)));
   ME_MBAR_HIP(count_partials.resize((size_t)n_blocks * n_slots * sizeof(unsigned long long)));
   ME_MBAR_HIP(mass.resize((size_t)n_temps * n_slots * sizeof(double)));
   ME_MBAR_HIP(counts.resize((size_t)n_slots * sizeof(long long)));
-  ME_MBAR_HIP(hipMemcpyAsync(edges.get(), h.edges, edges.bytes(), hipMemcpyHostToDevice, p.stream));
-  const size_t lds = (size_t)n_edges * sizeof(double) + (size_t)kWaves * n_slots * (kHistTargets * sizeof(double) + sizeof(unsigned int));
-  for (int t0 = 0; t0 < n_temps; t0 += kHistTargets) {
-    const int nt = std::min(kHistTargets, n_temps - t0);
+  ME_MBAR_HIP(hipMemcpyAsync(keep.edges.get(), table.edges, keep.edges.bytes(), hipMemcpyHostToDevice, p.stream));
+  for (int t0 = 0; t0 < n_temps; t0 += rows) {
+    const int nt = std::min(rows, n_temps - t0);
     double *sums = mass.get<double>() + (size_t)t0 * n_slots;
-    hipLaunchKernelGGL(k_mbar_hist, dim3(n_blocks), dim3(kThreads), lds, p.stream, p.sm.energies, d.get<const double>(), values.data,
-                       values.n_chains, values.record_stride, edges.get<const double>(), h.n_bins, top,
-                       w.inv_temps.get<const double>() + t0, w.out.get<const double>() + 4 * (size_t)t0, nt, n_tiles,
-                       partials.get<double>(), count_partials.get<unsigned long long>());
+    table.launch(t0, nt, partials.get<double>(), count_partials.get<unsigned long long>());
     hipLaunchKernelGGL(k_mbar_hist_sum, dim3(n_slots, nt), dim3(kThreads), 0, p.stream, partials.get<const double>(),
-                       count_partials.get<const unsigned long long>(), n_blocks, kHistTargets, n_slots, sums,
+                       count_partials.get<const unsigned long long>(), n_blocks, rows, n_slots, sums,
                        t0 == 0 ? counts.get<long long>() : nullptr);
     hipLaunchKernelGGL(k_mbar_hist_normalise, dim3(nt), dim3(kThreads), 0, p.stream, n_slots, sums);
   }
@@ -165,11 +80,27 @@ hipError_t histogram(Problem &p, const Source &src, const ObsColumns &values, co
   ME_MBAR_HIP(hipMemcpyAsync(out.data(), w.out.get(), out.size() * sizeof(double), hipMemcpyDeviceToHost, p.stream));
   ME_MBAR_HIP(hipMemcpyAsync(mass_host.data(), mass.get(), mass.bytes(), hipMemcpyDeviceToHost, p.stream));
   ME_MBAR_HIP(hipMemcpyAsync(counts_host.data(), counts.get(), counts.bytes(), hipMemcpyDeviceToHost, p.stream));
-  ME_MBAR_HIP(hipStreamSynchronize(p.stream));    // (also: `inv` and the scratch buffers but `keep` leave scope)
-  unpack_targets(out, n_temps, nullptr, nullptr, nullptr, h.neff);
-  if (h.mass) std::copy(mass_host.begin(), mass_host.end(), h.mass);
-  if (h.counts) std::copy(counts_host.begin(), counts_host.end(), h.counts);
+  ME_MBAR_HIP(hipStreamSynchronize(p.stream));    // (also: `inv`, the host edges and the scratch buffers but `keep` leave scope)
+  unpack_targets(out, n_temps, nullptr, nullptr, nullptr, table.neff);
+  if (table.mass) std::copy(mass_host.begin(), mass_host.end(), table.mass);
+  if (table.counts) std::copy(counts_host.begin(), counts_host.end(), table.counts);
   return hipSuccess;
+}
+
+// `values`: one column (n_columns = 1) that goes with the problem's samples
+hipError_t histogram(Problem &p, const Source &src, const ObsColumns &values, const double *f, const double *temps, int n_temps,
+                     const Histogram &h, HistogramScratch &keep) {
+  const int n_edges = h.n_bins + 1, n_slots = h.n_bins + 3;
+  keep.top = top_of(n_edges);
+  const size_t lds = slot_pass_lds(kHistTargets, n_slots, n_edges, true);
+  const auto launch = [&](int t0, int nt, double *partials, unsigned long long *count_partials) {     // (counts in every pass)
+    hipLaunchKernelGGL(k_mbar_hist, dim3(blocks_of(p.sm.n_samples)), dim3(kThreads), lds, p.stream, p.sm.energies,
+                       keep.d.get<const double>(), values.data, values.n_chains, values.record_stride,
+                       keep.edges.get<const double>(), h.n_bins, keep.top, p.w.inv_temps.get<const double>() + t0,
+                       p.w.out.get<const double>() + 4 * (size_t)t0, nt, tiles_of(p.sm.n_samples), partials, count_partials);
+  };
+  return histogram_slots(p, src, f, temps, n_temps,
+                         SlotTable{h.edges, n_edges, n_slots, kHistTargets, h.mass, h.counts, h.neff, launch}, keep);
 }
 
 int check_edges(me_engine *e, const double *edges, int n_bins) {

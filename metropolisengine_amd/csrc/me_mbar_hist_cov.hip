@@ -14,23 +14,19 @@
 // targets.  The host assembles the matrix (statistics.py), at most 64 + 1 + 259 columns per temperature.
 //
 // Kernels.  The masses, counts, ln_z_t and d_n are those of histogram() (me_mbar_hist.hip), called first: the same code, the
-// same bits.  k_mbar_hist_cov<R> is k_mbar_hist with the table's temperature axis replaced by a chunk of R rows j of ONE
-// temperature: one pass per (t, chunk), n ceil((K + 1) / R) passes, each reading 24 bytes per sample, finding the slot and
-// forming w_nt once and one more exponential per ladder row; the accumulation into the wavefront-private LDS table is
-// slot_accumulate (me_mbar_slots.h), so no atomic touches a floating-point number and no cross-lane operation runs under a
-// partial lane mask.  k_mbar_hist_sum (the same header) adds the block partials of every (row, slot) in a fixed order.
-// Summation order of one H[t][j][s]: that of a mass in me_mbar_hist.hip, fixed by the samples' slots and order alone.  It
-// depends neither on t, nor on j, nor on R, nor on which chunk a row falls into, and a row's terms are formed by the same
-// instructions at every position of a chunk (`fp contract(off)`): H[t][j][s] is bit for bit the same run to run, whatever
-// other targets are asked for, and through the engine's store or host arrays of the same samples in the same order.
+// same bits.  k_mbar_hist_cov<R> is slot_pass (me_mbar_slots.h, which describes the scheme and the summation order) with
+// k_mbar_hist's Slots1d and GramRows<R>: a chunk of R rows j of ONE temperature, one pass per (t, chunk), n ceil((K + 1) / R)
+// passes, each reading 24 bytes per sample, finding the slot and forming w_nt (state_weight, as k_mbar_hist does) once and
+// one more exponential per ladder row.  It keeps no counts.  k_mbar_hist_sum adds the block partials of every (row, slot) in
+// a fixed order.  H[t][j][s] depends neither on t, nor on j, nor on R, nor on which chunk a row falls into.
 // Rows per pass: R is a pure cost choice, passes against LDS (occupancy): the widest of 16, 8, 4 whose table leaves
 // kMinBlocksPerCu = 4 workgroups on a CU (rows_per_pass): 16 up to 75 bins, 8 up to 152, 4 beyond.  Measured at 2^25 samples,
 // 8 targets, K = 32, R = 4 / 8 / 16 forced (profiles/mbar_profile_uncertainty.txt), milliseconds for all passes: 64 bins, every
 // value in one bin 39.8 / 34.5 / 34.9, 64 different bins per wavefront 97.0 / 58.4 / 47.1 (a wide R shares the match loop, the
 // slot search and w_nt among its rows); 256 bins 46.5 / 57.5 / 86.6 and 109.8 / 103.4 / 129.1 (R = 16 leaves ONE workgroup per
 // CU, one wavefront per SIMD, and nothing hides the LDS round trips of the table).  LDS per workgroup: (n_bins + 1) 8 + 4 R
-// (n_bins + 3) 8 bytes: 34 824 at 64 bins with R = 16, 35 208 at 256 bins with R = 4.  Registers (hipcc -O3, gfx950): 56 / 73 /
-// 113 VGPRs for R = 4 / 8 / 16, 7 / 6 / 4 wavefronts per SIMD, no AGPRs; no kernel uses scratch.
+// (n_bins + 3) 8 bytes: 34 824 at 64 bins with R = 16, 35 208 at 256 bins with R = 4.  Registers (hipcc -O3, gfx950):
+// profiles/mbar_slot_skeleton.txt; no AGPRs, no kernel uses scratch.
 #include "me_launch.h"
 #include "me_mbar_slots.h"
 
@@ -49,23 +45,22 @@ constexpr int kMaxRows = 16;
 constexpr size_t kCuLds = 160 * 1024;           // LDS of a CU
 constexpr int kMinBlocksPerCu = 4;              // 4 wavefronts per SIMD, k_mbar_hist's own occupancy at 256 bins
 
-constexpr size_t lds_bytes(int rows, int n_bins) {
-  return (size_t)(n_bins + 1) * sizeof(double) + (size_t)kWaves * rows * (n_bins + 3) * sizeof(double);
-}
+static_assert(slot_pass_lds(16, 64 + 3, 64 + 1, false) == 34824 && slot_pass_lds(4, 256 + 3, 256 + 1, false) == 35208,
+              "the LDS of the header comment");
 
 // R of a launch: the widest of 16, 8, 4 with which kMinBlocksPerCu workgroups fit a CU's LDS (R = 4 always does).
-// tools/bench_mbar.py (time_profile_uncertainty) restates this rule to print its pass counts: change both together.
-int rows_per_pass(int n_bins) {
-  if (kForcedRows) return kForcedRows;
+// tools/bench_mbar.py (gram_rows) restates this rule to print its pass counts: change both together.
+constexpr int rule_rows(int n_bins) {
   for (int rows = kMaxRows; rows > 4; rows /= 2)
-    if (kMinBlocksPerCu * lds_bytes(rows, n_bins) <= kCuLds) return rows;
+    if (kMinBlocksPerCu * slot_pass_lds(rows, n_bins + 3, n_bins + 1, false) <= kCuLds) return rows;
   return 4;
 }
+static_assert(rule_rows(75) == 16 && rule_rows(76) == 8 && rule_rows(152) == 8 && rule_rows(153) == 4,
+              "the thresholds of the header comment");
+int rows_per_pass(int n_bins) { return kForcedRows ? kForcedRows : rule_rows(n_bins); }
 
-// One pass: rows j0 .. j0 + n_rows (n_rows <= kRows, j0 + n_rows <= n_rungs + 1) of target *inv_temp, *ln_z.  Row j < n_rungs
-// is ladder column j (beta_j, f_j from the ladder table), row n_rungs the state column itself.  Samples and values are
-// addressed as in k_mbar_hist; `d` is padded to whole tiles.  Dynamic LDS: [edges | table[kWaves][kRows][n_slots]];
-// partials[block][kRows][n_slots].
+// One pass: rows j0 .. j0 + n_rows (n_rows <= kRows, j0 + n_rows <= n_rungs + 1) of target *inv_temp, *ln_z (GramRows).
+// Samples and values are addressed as in k_mbar_hist.
 template <int kRows>
 __global__ void __launch_bounds__(kThreads) k_mbar_hist_cov(const double *__restrict__ energies, const double *__restrict__ d,
                                                             const double *__restrict__ values, long long n_chains,
@@ -73,77 +68,22 @@ __global__ void __launch_bounds__(kThreads) k_mbar_hist_cov(const double *__rest
                                                             int top, const double *__restrict__ table, int n_rungs,
                                                             const double *__restrict__ inv_temp, const double *__restrict__ ln_z,
                                                             int j0, int n_rows, long long n_tiles, double *partials) {
-  extern __shared__ double lds[];
-  const int n_edges = n_bins + 1, n_slots = n_bins + 3;
-  double *s_edges = lds, *s_table = lds + n_edges;
-  for (int i = threadIdx.x; i < n_edges; i += kThreads) s_edges[i] = edges[i];
-  for (int i = threadIdx.x; i < kWaves * kRows * n_slots; i += kThreads) s_table[i] = 0.0;
-  __syncthreads();
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  double *my_table = s_table + wave * kRows * n_slots;
-  const unsigned long long below_me = (1ull << lane) - 1ull;
-  const double inv = inv_temp[0], lz = ln_z[0];
-  double beta[kRows], g[kRows];
-#pragma unroll
-  for (int r = 0; r < kRows; ++r) {
-    const bool ladder = j0 + r < n_rungs;       // (wave-uniform)
-    beta[r] = ladder ? table[kBeta + j0 + r] : 0.0;
-    g[r] = ladder ? table[kF + j0 + r] : 0.0;
-  }
-  for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    const long long base = tile * kTile + threadIdx.x;
-    long long record = base / n_chains, chain = base - record * n_chains;
-#pragma unroll 1
-    for (int it = 0; it < kItems; ++it) {
-      const long long i = base + (long long)it * kThreads;
-      const double dn = d[i];                   // (padded: in bounds; NaN beyond n and for an unused sample)
-      int slot = -1;
-      double w[kRows];
-#pragma unroll
-      for (int r = 0; r < kRows; ++r) w[r] = 0.0;
-      if (dn == dn) {
-        const double e = energies[i];
-        slot = slot_of(s_edges, n_edges, top, values[record * record_stride + chain]);
-        const double wt = math64::exp_nonpos(fmin(__builtin_fma(-e, inv, -dn) - lz, 0.0));      // k_mbar_hist's weight
-#pragma unroll
-        for (int r = 0; r < kRows; ++r)
-          if (r < n_rows) {
-            // k_mbar_gram's ladder column; the last row of all pairs the state column with itself
-            const double col = j0 + r < n_rungs ? math64::exp_nonpos(fmin(__builtin_fma(-beta[r], e, g[r]) - dn, 0.0)) : wt;
-            w[r] = col * wt;
-          }
-      }
-      chain += kThreads;
-      while (chain >= n_chains) {
-        chain -= n_chains;
-        record += 1;
-      }
-      // every lane is active from here on (me_mbar_slots.h)
-      slot_accumulate<kRows>(my_table, n_slots, n_rows, slot, w, lane, below_me);
-    }
-  }
-  __syncthreads();
-  slot_tables_store(s_table, kRows, n_rows, n_slots, partials);
+  const Slots1d where{values, n_bins, top};
+  const GramRows<kRows> rows(table, n_rungs, inv_temp, ln_z, j0, n_rows);
+  slot_pass<kRows, false>(energies, d, n_chains, record_stride, edges, where, rows, 0, n_tiles, partials, nullptr);
 }
 
-struct PassArgs {
-  const MbarSamples *sm;
-  const ObsColumns *values;
-  const HistogramScratch *keep;
-  const double *table, *inv_temp, *ln_z;
-  int n_bins, n_rungs, j0, n_rows, n_blocks;
-  long long n_tiles;
-  double *partials;
-};
-
+// enqueues rows j0 .. j0 + n_rows of target t of a problem whose histogram() left `keep`
 template <int kRows>
-hipError_t launch_pass(const PassArgs &a, hipStream_t stream) {
-  constexpr size_t most = lds_bytes(kRows, ME_MAX_HISTOGRAM_BINS);
+hipError_t launch_pass(const Problem &p, const ObsColumns &values, const HistogramScratch &keep, int n_bins, int t, int j0,
+                       int n_rows, double *partials) {
+  constexpr size_t most = slot_pass_lds(kRows, ME_MAX_HISTOGRAM_BINS + 3, ME_MAX_HISTOGRAM_BINS + 1, false);
   if (most > 64 * 1024) ME_MBAR_HIP(raise_lds_limit<k_mbar_hist_cov<kRows>>(most));
-  hipLaunchKernelGGL(k_mbar_hist_cov<kRows>, dim3(a.n_blocks), dim3(kThreads), lds_bytes(kRows, a.n_bins), stream, a.sm->energies,
-                     a.keep->d.get<const double>(), a.values->data, a.values->n_chains, a.values->record_stride,
-                     a.keep->edges.get<const double>(), a.n_bins, a.keep->top, a.table, a.n_rungs, a.inv_temp, a.ln_z, a.j0, a.n_rows,
-                     a.n_tiles, a.partials);
+  hipLaunchKernelGGL(k_mbar_hist_cov<kRows>, dim3(blocks_of(p.sm.n_samples)), dim3(kThreads),
+                     slot_pass_lds(kRows, n_bins + 3, n_bins + 1, false), p.stream, p.sm.energies, keep.d.get<const double>(),
+                     values.data, values.n_chains, values.record_stride, keep.edges.get<const double>(), n_bins, keep.top,
+                     p.w.table.get<const double>(), p.n_rungs, p.w.inv_temps.get<const double>() + t,
+                     p.w.out.get<const double>() + 4 * (size_t)t, j0, n_rows, tiles_of(p.sm.n_samples), partials);
   return hipSuccess;
 }
 
@@ -155,16 +95,14 @@ hipError_t slot_gram(Problem &p, const ObsColumns &values, const HistogramScratc
   DeviceBuffer partials, sums;
   ME_MBAR_HIP(partials.resize((size_t)n_blocks * rows * n_slots * sizeof(double)));
   ME_MBAR_HIP(sums.resize(cells * sizeof(double)));
-  PassArgs a{&p.sm, &values, &keep, p.w.table.get<const double>(), nullptr, nullptr, n_bins, p.n_rungs, 0, 0, n_blocks,
-             tiles_of(p.sm.n_samples), partials.get<double>()};
+  double *part = partials.get<double>();
   for (int t = 0; t < n_temps; ++t)
     for (int j0 = 0; j0 < n_cols; j0 += rows) {
-      a.inv_temp = p.w.inv_temps.get<const double>() + t;
-      a.ln_z = p.w.out.get<const double>() + 4 * (size_t)t;
-      a.j0 = j0;
-      a.n_rows = std::min(rows, n_cols - j0);
-      ME_MBAR_HIP(rows == 16 ? launch_pass<16>(a, p.stream) : rows == 8 ? launch_pass<8>(a, p.stream) : launch_pass<4>(a, p.stream));
-      hipLaunchKernelGGL(k_mbar_hist_sum, dim3(n_slots, a.n_rows), dim3(kThreads), 0, p.stream, partials.get<const double>(),
+      const int n_rows = std::min(rows, n_cols - j0);
+      ME_MBAR_HIP(rows == 16  ? launch_pass<16>(p, values, keep, n_bins, t, j0, n_rows, part)
+                  : rows == 8 ? launch_pass<8>(p, values, keep, n_bins, t, j0, n_rows, part)
+                              : launch_pass<4>(p, values, keep, n_bins, t, j0, n_rows, part));
+      hipLaunchKernelGGL(k_mbar_hist_sum, dim3(n_slots, n_rows), dim3(kThreads), 0, p.stream, partials.get<const double>(),
                          (const unsigned long long *)nullptr, n_blocks, rows, n_slots,
                          sums.get<double>() + ((size_t)t * n_cols + j0) * n_slots, (long long *)nullptr);
     }

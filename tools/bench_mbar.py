@@ -39,6 +39,27 @@ import mbar_reference as ref  # noqa: E402
 DIM = 16
 
 
+def times_ms(call, repeats=3):
+    """Milliseconds of ``repeats`` calls after one warm-up call (allocations, code objects)."""
+    call()
+    times = []
+    for _ in range(repeats):
+        t0 = time.perf_counter()
+        call()
+        times.append(time.perf_counter() - t0)
+    return [1e3 * t for t in times]
+
+
+def best(call, repeats=3):
+    return min(times_ms(call, repeats))
+
+
+def lane_patterns(n_chains):
+    """The two inputs of the histogram timings as one bin index per chain (edges 0, 1, 2, ...; the value is the index + 0.5):
+    every chain in bin 0 (a wavefront's 64 lanes share a slot) and consecutive chains in 64 DIFFERENT bins."""
+    return np.zeros(n_chains, dtype=np.int64), np.arange(n_chains) % 64
+
+
 def ladder(k):
     return 0.5 * (1.3 ** 7) ** (np.arange(k) / (k - 1.0))
 
@@ -113,15 +134,6 @@ def time_observables(k, log2_chains, records, n_targets=8, columns=(1, 4, 16)):
     f = eng.ladder_free_energies(tol=1e-8)["f"]
     targets = np.geomspace(0.5, 3.0, n_targets)
 
-    def best(call, repeats=3):
-        call()                                                  # warm-up: allocations, code objects
-        times = []
-        for _ in range(repeats):
-            t0 = time.perf_counter()
-            call()
-            times.append(time.perf_counter() - t0)
-        return 1e3 * min(times)
-
     energy_ms = best(lambda: eng.reweight(targets, f))
     print("K = %d, %d samples, %d targets: energy-only reweighting (me_mbar_reweight) %.3f ms" % (k, n, n_targets, energy_ms),
           flush=True)
@@ -154,15 +166,6 @@ def time_observable_gram(k, log2_chains, records, n_targets=8, columns=(1, 4, 16
     targets = np.geomspace(0.5, 3.0, n_targets)
     energies = eng.energy_samples()
 
-    def best(call, repeats=3):
-        call()                                                  # warm-up: allocations, code objects
-        times = []
-        for _ in range(repeats):
-            t0 = time.perf_counter()
-            call()
-            times.append(time.perf_counter() - t0)
-        return 1e3 * min(times), 1e3 * max(times)
-
     def launched(per_target, nt):
         per_chunk = (128 - k) // per_target
         return [k + per_target * min(per_chunk, nt - t0) for t0 in range(0, nt, per_chunk)]
@@ -175,17 +178,19 @@ def time_observable_gram(k, log2_chains, records, n_targets=8, columns=(1, 4, 16
         eng.set_observable_samples(energies[:, None, :] * scale[None, :, None])
         c = k + n_targets * (1 + q)
         gram, counts = np.zeros((c, c)), np.zeros(c)
-        obs_ms, obs_max = best(lambda: eng._check(eng._lib.me_mbar_gram_observables(
+        obs = times_ms(lambda: eng._check(eng._lib.me_mbar_gram_observables(
             eng._handle, f.ctypes.data_as(dp), targets.ctypes.data_as(dp), n_targets, gram.ctypes.data_as(dp), counts.ctypes.data_as(dp),
             None, None, None, None)))
-        rw_ms, _ = best(lambda: eng.reweight_observables(targets, f))
+        obs_ms, obs_max = min(obs), max(obs)
+        rw_ms = best(lambda: eng.reweight_observables(targets, f))
         nt_e = max(1, (n_targets * (1 + q) + 1) // 2)
         targets_e = np.geomspace(0.5, 3.0, nt_e)
         ce = k + 2 * nt_e
         gram_e, counts_e = np.zeros((ce, ce)), np.zeros(ce)
-        e_ms, e_max = best(lambda: eng._check(eng._lib.me_mbar_gram(
+        plain = times_ms(lambda: eng._check(eng._lib.me_mbar_gram(
             eng._handle, f.ctypes.data_as(dp), targets_e.ctypes.data_as(dp), nt_e, gram_e.ctypes.data_as(dp), counts_e.ctypes.data_as(dp),
             None, None, None)))
+        e_ms, e_max = min(plain), max(plain)
         cols_o, cols_e = launched(1 + q, n_targets), launched(2, nt_e)
         print("    Q = %2d: me_mbar_gram_observables %.3f ms (slowest of 3: %.3f), launches of %s columns; of that the observables' "
               "reweighting alone %.3f ms; me_mbar_gram with %d targets %.3f ms (slowest of 3: %.3f), launches of %s columns; ratio "
@@ -207,22 +212,12 @@ def time_profile(k, log2_chains, records, n_targets=8, bins=(64, 256)):
     f = eng.ladder_free_energies(tol=1e-8)["f"]
     targets = np.geomspace(0.5, 3.0, n_targets)
 
-    def best(call, repeats=3):
-        call()                                                  # warm-up: allocations, code objects
-        times = []
-        for _ in range(repeats):
-            t0 = time.perf_counter()
-            call()
-            times.append(time.perf_counter() - t0)
-        return 1e3 * min(times)
-
     energy_ms = best(lambda: eng.reweight(targets, f))
     energies = eng.energy_samples()
     eng.record_observables([0])
     eng.set_energy_samples(energies)
-    chain = np.arange(eng.n_chains)
-    inputs = (("every value in one bin", np.full(eng.n_chains, 0.5)),
-              ("consecutive samples in 64 different bins", (chain % 64) + 0.5))
+    one_bin, many_bins = lane_patterns(eng.n_chains)
+    inputs = (("every value in one bin", one_bin + 0.5), ("consecutive samples in 64 different bins", many_bins + 0.5))
     print("K = %d, %d samples, %d targets: energy-only reweighting (me_mbar_reweight) %.3f ms" % (k, n, n_targets, energy_ms),
           flush=True)
     for label, row in inputs:
@@ -253,28 +248,18 @@ def time_profile_uncertainty(k, log2_chains, records, n_targets=8, bins=(64, 256
     targets = np.geomspace(0.5, 3.0, n_targets)
     dp = ctypes.POINTER(ctypes.c_double)
 
-    def best(call, repeats=3):
-        call()                                                  # warm-up: allocations, code objects
-        times = []
-        for _ in range(repeats):
-            t0 = time.perf_counter()
-            call()
-            times.append(time.perf_counter() - t0)
-        return 1e3 * min(times)
-
     energies = eng.energy_samples()
     eng.record_observables([0])
     eng.set_energy_samples(energies)
-    chain = np.arange(eng.n_chains)
-    inputs = (("every value in one bin", np.full(eng.n_chains, 0.5)),
-              ("consecutive samples in 64 different bins", (chain % 64) + 0.5))
+    one_bin, many_bins = lane_patterns(eng.n_chains)
+    inputs = (("every value in one bin", one_bin + 0.5), ("consecutive samples in 64 different bins", many_bins + 0.5))
     print("K = %d, %d samples, %d targets" % (k, n, n_targets), flush=True)
     for label, row in inputs:
         eng.set_observable_samples(np.broadcast_to(row[None, None, :], (records, 1, eng.n_chains)))
         print("    %s" % label, flush=True)
         for b in bins:
             edges = np.linspace(0.0, float(b), b + 1)
-            rows = forced_rows or next((r for r in (16, 8) if 4 * (8 * (b + 1) + 32 * r * (b + 3)) <= 160 * 1024), 4)   # rows_per_pass
+            rows = forced_rows or gram_rows(b)
             out = eng.free_energy_profile_uncertainties(0, edges, targets, f)
             assert out["counts"].sum() == n and np.all(np.isfinite(out["d_mass"]))
             h = np.zeros((n_targets, k + 1, b + 3))
@@ -287,6 +272,12 @@ def time_profile_uncertainty(k, log2_chains, records, n_targets=8, bins=(64, 256
             print("        %3d bins: free_energy_profile %.3f ms (%d passes); slot Gram sums %.3f ms (R = %d: %d more passes) = %.2f x, "
                   "%.3f ms per added pass; free_energy_profile_uncertainties %.3f ms = %.2f x"
                   % (b, plain, plain_passes, sums, rows, passes, sums / plain, (sums - plain) / passes, whole, whole / plain), flush=True)
+
+
+def gram_rows(n_bins):
+    """rule_rows of csrc/me_mbar_hist_cov.hip: the rows per pass, the widest of 16, 8, 4 whose LDS (slot_pass_lds of
+    csrc/me_mbar_slots.h without counts) leaves four workgroups on a CU."""
+    return next((r for r in (16, 8) if 4 * (8 * (n_bins + 1) + 32 * r * (n_bins + 3)) <= 160 * 1024), 4)
 
 
 def surface_rows(n_cells):
@@ -307,22 +298,12 @@ def time_surface(k, log2_chains, records, n_targets=8, grids=(8, 16, 33), bins=(
     f = eng.ladder_free_energies(tol=1e-8)["f"]
     targets = np.geomspace(0.5, 3.0, n_targets)
 
-    def best(call, repeats=3):
-        call()                                                  # warm-up: allocations, code objects
-        times = []
-        for _ in range(repeats):
-            t0 = time.perf_counter()
-            call()
-            times.append(time.perf_counter() - t0)
-        return 1e3 * min(times)
-
     energies = eng.energy_samples()
     eng.record_observables([0, 1, 2])                           # columns: x, y, and the 1-D call's value
     eng.set_energy_samples(energies)
-    chain = np.arange(eng.n_chains)
-    half = np.full(eng.n_chains, 0.5)
-    inputs = (("every sample in one cell", np.stack([half, half, half])),
-              ("consecutive samples in 64 different cells", np.stack([(chain % 64) // 8 + 0.5, (chain % 8) + 0.5, (chain % 64) + 0.5])))
+    one_bin, many_bins = lane_patterns(eng.n_chains)           # (the 64 bins as an 8 x 8 block of the grid)
+    inputs = (("every sample in one cell", np.stack([one_bin + 0.5] * 3)),
+              ("consecutive samples in 64 different cells", np.stack([many_bins // 8 + 0.5, many_bins % 8 + 0.5, many_bins + 0.5])))
     print("K = %d, %d samples, %d targets" % (k, n, n_targets), flush=True)
     for label, rows in inputs:
         eng.set_observable_samples(np.broadcast_to(rows[None, :, :], (records, 3, eng.n_chains)))
@@ -364,15 +345,6 @@ def time_newton(k, log2_chains, records, dim=DIM, ratio=None):
     eng.record_energies(records)
     rng = np.random.default_rng(1)
     eng.set_energy_samples(rng.gamma(dim / 2.0, 1.0, size=(records, n)) * np.repeat(temps, n // k)[None, :])
-
-    def best(call, repeats=3):
-        call()                                                  # warm-up: allocations, code objects
-        times = []
-        for _ in range(repeats):
-            t0 = time.perf_counter()
-            call()
-            times.append(time.perf_counter() - t0)
-        return 1e3 * min(times)
 
     def per_pass(method, a, b):
         few = best(lambda: eng.ladder_free_energies(tol=1e-300, max_iter=a, method=method))
@@ -416,15 +388,6 @@ def time_inefficiency(k, log2_chains, records, columns=(0, 4, 16), phi=0.9):
     x[0] = rng.standard_normal(n)
     for r in range(1, records):
         x[r] = phi * x[r - 1] + np.sqrt(1.0 - phi * phi) * rng.standard_normal(n)
-
-    def best(call, repeats=3):
-        call()                                                  # warm-up: allocations, code objects
-        times = []
-        for _ in range(repeats):
-            t0 = time.perf_counter()
-            call()
-            times.append(time.perf_counter() - t0)
-        return 1e3 * min(times)
 
     for q in columns:
         eng.record_observables([j % 4 for j in range(q)] if q else None)
