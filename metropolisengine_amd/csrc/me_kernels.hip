@@ -191,8 +191,16 @@ hipError_t step_with(const StepLaunch &l, const Energy &en, hipStream_t stream) 
   const int threads = (l.n_sweeps >= kFusedSweepsThreshold || (ME_PER_CHAIN == 2 && per_chain)) ? kFusedStepThreads : kStepThreads;
   const dim3 grid(grid_for(l.n, l.grid_blocks, threads)), block(threads);
   if (l.ladder) {
-    // a temperature ladder (me_set_temperature_ladder): the LADDER kernels; no replay hook, no matrix-core dense-64 form
-    if (l.inj_normals) return hipErrorNotSupported;
+    // a temperature ladder (me_set_temperature_ladder): the LADDER kernels; no matrix-core dense-64 form.  The replay hook
+    // exists for step_all with the identity shape in float64 only (one instantiation: it is there so that the accept rule can
+    // be probed at its threshold on every rung, tests/test_gpu_draw_conformance.py)
+    if (l.inj_normals) {
+      if constexpr (std::is_same<R, double>::value) {
+        if (l.group != GROUP_ALL || l.cov_kind != CK_IDENTITY) return hipErrorNotSupported;
+        hipLaunchKernelGGL((k_step<R, NR, NC, Energy, CK_IDENTITY, true, GROUP_ALL, false, true>), grid, block, 0, stream, a, en);
+        return hipGetLastError();
+      } else return hipErrorNotSupported;
+    }
 #if ME_DENSE && !defined(ME_USER_SOURCE)
     if constexpr (NR == 64 && NC == 0 && std::is_same<Energy, EnergyDense<R, 64, 0>>::value) return hipErrorNotSupported;
     else

@@ -298,7 +298,8 @@ class MetropolisEngine:
     def step_injected(self, normals, uniforms, kind=_capi.STEP_ALL):
         """Test hook (float64 engines): step with caller-supplied draws instead of the Philox stream
         (``me_step_injected``): ``normals[sweep, chain, D]`` and ``uniforms[sweep, chain]`` for the Gaussian kinds,
-        ``normals[sweep, chain, nc]`` and ``uniforms[sweep, chain, nc + 2]`` for the magnitude-phase pair."""
+        ``normals[sweep, chain, nc]`` and ``uniforms[sweep, chain, nc + 2]`` for the magnitude-phase pair.  On a ladder
+        engine: step_all with the identity proposal shape only."""
         normals = np.ascontiguousarray(normals, dtype=np.float64)
         uniforms = np.ascontiguousarray(uniforms, dtype=np.float64)
         nc = self.num_complex_params
