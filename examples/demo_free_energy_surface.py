@@ -2,10 +2,12 @@
 (-1, 1/2) and (1, 1/2) are joined by a curved valley y = x^2 / 2 through the saddle at the origin,
 E = 4 (x^2 - 1)^2 + 4 (y - x^2 / 2)^2, sampled by parallel tempering with x and y of every chain recorded next to its energy.
 MBAR (``free_energy_surface``, on the GPU; the samples never leave it) turns the eight rungs into the joint reweighted
-histogram p(x, y; T) on 13 x 9 bins and F(x, y; T) = -T ln p(x, y; T).  Neither the path between the wells nor the saddle
-follows from the two 1-D profiles: the valley is curved.  The surface is printed at the coldest of three temperatures, at
-which the plain samples of that temperature alone hardly ever see the saddle, next to the exact value of every cell,
--T ln (integral over the cell of exp(-E / T) dx dy / (area Z(T))), from a numerical quadrature.
+histogram p(x, y; T) on 13 x 9 bins and F(x, y; T) = -T ln p(x, y; T); ``free_energy_surface_uncertainties`` adds the
+asymptotic standard error of every cell and of the saddle height, a difference of two cells of the same correlated samples.
+Neither the path between the wells nor the saddle follows from the two 1-D profiles: the valley is curved.  The surface is
+printed at the coldest of three temperatures, at which the plain samples of that temperature alone hardly ever see the
+saddle, next to the exact value of every cell, -T ln (integral over the cell of exp(-E / T) dx dy / (area Z(T))), from a
+numerical quadrature.
 
     python examples/demo_free_energy_surface.py [--quick]        (needs an MI355X and the built library)
 """
@@ -77,6 +79,18 @@ def cell_of(out, point):
             int(np.searchsorted(out["edges_y"], point[1], side="right")) - 1)
 
 
+def saddle_height(out, t):
+    """``(height, error, saddle cell, well cell)`` at temperature index ``t`` of a result of
+    ``free_energy_surface_uncertainties``: ``F(saddle) - F(right well)`` and its standard error from the covariance of the two
+    log masses, ``T sqrt(C_ss + C_ww - 2 C_sw)`` (cell index ``bx * By + by``)."""
+    saddle, well = cell_of(out, SADDLE), cell_of(out, WELL)
+    by = out["edges_y"].size - 1
+    s, w = saddle[0] * by + saddle[1], well[0] * by + well[1]
+    c = out["log_mass_cov"][t]
+    f = out["free_energy"][t]
+    return f[saddle] - f[well], float(out["temps"][t]) * np.sqrt(max(c[s, s] + c[w, w] - 2.0 * c[s, w], 0.0)), saddle, well
+
+
 def _grid(title, out, values, counts, least):
     print(title)
     print("     x \\ y" + "".join("%9.3f" % y for y in out["centers_y"]))
@@ -101,7 +115,15 @@ def main(temps=TEMPS, edges_x=EDGES_X, edges_y=EDGES_Y, least=20, **kw):
     print("largest |MBAR - quadrature| over those %d cells: %.4f" % (seen.sum(), np.max(np.abs(f[seen] - exact[seen]))))
     print("T = %.2f: F(saddle) - F(right well) = %.4f, F(saddle) - F(left well) = %.4f; exact %.4f"
           % (t, f[saddle] - f[well], f[saddle] - f[left], exact[saddle] - exact[well]))
-    return {"result": out, "exact": exact, "engine": engine}
+    # the same surface with its error bars (every key above is the same, bit for bit); the records are successive states of
+    # Metropolis chains, so every variance carries the statistical inefficiency of the recorded series
+    bars = engine.free_energy_surface_uncertainties("real_0", edges_x, "real_1", edges_y, temps, inefficiency="recorded")
+    _grid("standard error of F(x, y; %.2f) (asymptotic MBAR covariance, recorded inefficiency)" % t, bars, bars["d_free_energy"][0],
+          bars["counts"], least)
+    height, error, _, _ = saddle_height(bars, 0)
+    print("T = %.2f: F(saddle) - F(right well) = %.4f +- %.4f; exact %.4f, %.2f standard errors away"
+          % (t, height, error, exact[saddle] - exact[well], (height - (exact[saddle] - exact[well])) / error))
+    return {"result": out, "exact": exact, "engine": engine, "uncertainties": bars}
 
 
 if __name__ == "__main__":

@@ -530,7 +530,21 @@ int me_mbar_energy_shift(me_engine *engine, double *shift);
  *                       free-energy surface is F(A, B; T) = -T ln(mass / (bin width x) (bin width y)).  Errors as for
  *                       me_mbar_histogram.
  *   me_mbar_histogram_joint_samples  the same kernels on host arrays; values_x[n_samples] and values_y[n_samples] hold A and B of
- *                       every sample. */
+ *                       every sample.
+ *   me_mbar_histogram_joint_gram   me_mbar_histogram_joint with what the asymptotic error bars of its masses need (csrc/
+ *                       me_mbar_hist2d_cov.hip has the definition): me_mbar_histogram_gram with "cell" for "slot".  mass, counts
+ *                       and neff_fraction are me_mbar_histogram_joint's, bit for bit (the same code).  With K = n_rungs, S =
+ *                       (n_bins_x + 3)(n_bins_y + 3), and W_nj, w_nt as in me_mbar_histogram_gram, cell_gram is [n][K + 1][S]:
+ *                           cell_gram[t][j][c] = sum over the used samples of cell c of W_nj w_nt     (j < K)
+ *                           cell_gram[t][K][c] = sum over the used samples of cell c of w_nt^2.
+ *                       The Gram matrix of [K ladder columns | state column | one column per cell] follows from cell_gram,
+ *                       mass and ladder_gram as there.  ladder_gram [K][K] and column_counts [K] are the ladder block and the
+ *                       counts of me_mbar_gram with n_targets = 0 (that pass itself); *n_used the used samples.  Every output
+ *                       may be NULL.  A cell without a sample has cell_gram exactly 0.  No floating-point atomics: all sums have
+ *                       a fixed order, and cell_gram[t][j][c] is bit for bit the same run to run, whatever other temperatures
+ *                       are asked for, and through me_mbar_histogram_joint_gram_samples on the same samples in the same order.
+ *                       Arguments are checked and errors reported exactly as by me_mbar_histogram_joint.
+ *   me_mbar_histogram_joint_gram_samples  the same on host arrays, like me_mbar_histogram_joint_samples. */
 #define ME_MAX_RECORDED_OBSERVABLES 16
 #define ME_MAX_HISTOGRAM_BINS 256
 #define ME_MAX_HISTOGRAM2D_SLOTS 1296
@@ -571,6 +585,16 @@ int me_mbar_histogram_joint_samples(int32_t device_id, const double *energies, c
                                 const double *ladder_temps, int32_t n_rungs, const double *f, const double *temps, int32_t n,
                                 const double *values_x, const double *values_y, const double *edges_x, int32_t n_bins_x,
                                 const double *edges_y, int32_t n_bins_y, double *mass, int64_t *counts, double *neff_fraction);
+int me_mbar_histogram_joint_gram(me_engine *engine, const double *f, const double *temps, int32_t n, int32_t column_x,
+                                 const double *edges_x, int32_t n_bins_x, int32_t column_y, const double *edges_y,
+                                 int32_t n_bins_y, double *cell_gram, double *ladder_gram, double *column_counts, double *mass,
+                                 int64_t *counts, double *neff_fraction, int64_t *n_used);
+int me_mbar_histogram_joint_gram_samples(int32_t device_id, const double *energies, const int32_t *rungs, int64_t n_samples,
+                                         const double *ladder_temps, int32_t n_rungs, const double *f, const double *temps,
+                                         int32_t n, const double *values_x, const double *values_y, const double *edges_x,
+                                         int32_t n_bins_x, const double *edges_y, int32_t n_bins_y, double *cell_gram,
+                                         double *ladder_gram, double *column_counts, double *mass, int64_t *counts,
+                                         double *neff_fraction, int64_t *n_used);
 
 /* Statistical inefficiencies of the recorded series, pooled over the chains of a rung (no reference counterpart; csrc/
  * me_series.hip has the definition): the multiple-series estimator of Chodera et al., JCTC 3:26 (2007), the number the

@@ -176,6 +176,13 @@ SYMBOLS = {
     "me_mbar_histogram_joint_samples": (ctypes.c_int, [ctypes.c_int32, _dp, ctypes.POINTER(ctypes.c_int32), ctypes.c_int64, _dp,
                                                    ctypes.c_int32, _dp, _dp, ctypes.c_int32, _dp, _dp, _dp, ctypes.c_int32, _dp,
                                                    ctypes.c_int32, _dp, ctypes.POINTER(ctypes.c_int64), _dp]),
+    "me_mbar_histogram_joint_gram": (ctypes.c_int, [_H, _dp, _dp, ctypes.c_int32, ctypes.c_int32, _dp, ctypes.c_int32, ctypes.c_int32,
+                                                    _dp, ctypes.c_int32, _dp, _dp, _dp, _dp, ctypes.POINTER(ctypes.c_int64), _dp,
+                                                    ctypes.POINTER(ctypes.c_int64)]),
+    "me_mbar_histogram_joint_gram_samples": (ctypes.c_int, [ctypes.c_int32, _dp, ctypes.POINTER(ctypes.c_int32), ctypes.c_int64, _dp,
+                                                            ctypes.c_int32, _dp, _dp, ctypes.c_int32, _dp, _dp, _dp, ctypes.c_int32,
+                                                            _dp, ctypes.c_int32, _dp, _dp, _dp, _dp,
+                                                            ctypes.POINTER(ctypes.c_int64), _dp, ctypes.POINTER(ctypes.c_int64)]),
     "me_recorded_inefficiency": (ctypes.c_int, [_H, ctypes.c_int32, ctypes.c_int32, _dp, _dp, _dp, ctypes.POINTER(ctypes.c_int32),
                                                 ctypes.POINTER(ctypes.c_int64), _dp]),
     "me_series_inefficiency_samples": (ctypes.c_int, [ctypes.c_int32, _dp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,

@@ -1,10 +1,11 @@
 // What the MBAR units share (me_mbar.hip: samples, solve, reweighting; me_mbar_newton.hip: the Newton solve; me_mbar_cov.hip:
 // the Gram matrix of the weight matrix for the asymptotic covariance; me_mbar_obs.hip: recorded observables and their
 // reweighting; me_mbar_hist.hip: reweighted histograms along an observable; me_mbar_hist_cov.hip: the slot Gram sums behind
-// their error bars; me_mbar_hist2d.hip: joint histograms along two -- three policies of one pass kernel, me_mbar_slots.h, behind
-// one host driver, histogram_slots): the tile policy, the device table of a ladder, the per-sample sums, and the host
-// scaffolding of an entry point, which me_mbar.hip defines: where the samples come from (Source), the prepared problem (Problem,
-// prepare) and the argument checks.  Private to the host side, like me_engine.h.
+// their error bars; me_mbar_hist2d.hip: joint histograms along two; me_mbar_hist2d_cov.hip: the cell Gram sums behind theirs --
+// four pairings of the policies of one pass kernel, me_mbar_slots.h, behind one host driver, histogram_slots): the tile policy,
+// the device table of a ladder, the per-sample sums, and the host scaffolding of an entry point, which me_mbar.hip defines:
+// where the samples come from (Source), the prepared problem (Problem, prepare) and the argument checks.  Private to the host
+// side, like me_engine.h.
 #pragma once
 
 #include <algorithm>
@@ -206,6 +207,37 @@ int check_edges(me_engine *e, const double *edges, int n_bins);
 // `values` = the column of an engine's Source that a histogram entry point names: a recorded column (ME_ERR_STATE without an
 // observable store, ME_ERR_INVALID beyond the recorded columns) or, for -1, the energies themselves
 int histogram_column(const Source &src, int column, ObsColumns &values);
+
+// ---- defined in me_mbar_hist2d.hip --------------------------------------------------------------------------------------
+// A joint histogram request: the edges of both axes and the host outputs mass[n_temps][Bx + 3][By + 3], counts[Bx + 3][By + 3],
+// neff[n_temps] (each may be nullptr)
+struct Histogram2d {
+  const double *edges_x;
+  int n_bins_x;
+  const double *edges_y;
+  int n_bins_y;
+  double *mass;
+  int64_t *counts;
+  double *neff;
+};
+// The two value columns that go with the problem's samples: x and y share n_chains and record_stride; nullptr = the energy
+struct ValuePair {
+  const double *x, *y;
+  long long n_chains, record_stride;
+};
+// histogram_slots for the S cells of the grid and the concatenated edges; R, the edges and both `top` are worked out from the
+// request before the problem is prepared.  `keep` as histogram()'s: d_n and [edges_x | edges_y] for a pass that follows.
+hipError_t histogram2d(Problem &p, const Source &src, const ValuePair &values, const double *f, const double *temps, int n_temps,
+                       const Histogram2d &h, HistogramScratch &keep);
+// the argument checks of a joint histogram entry point, in their order: both edge arrays (check_edges), the cell cap
+// ME_MAX_HISTOGRAM2D_SLOTS, then check_f_and_targets with at least one target
+int check_histogram2d(const Source &src, const double *f, const double *temps, int n, const Histogram2d &h);
+// `values` = the two columns of an engine's Source that a joint entry point names (histogram_column for each; recorded columns
+// share the store's strides, and the energy is read as the energy, nullptr, whatever the other axis is)
+int joint_columns(const Source &src, int column_x, int column_y, ValuePair &values);
+// `values` = the host columns values_x, values_y [n_samples] of a host-form Source (after from_host), put on the device in
+// src.columns_dev for the length of the call
+int joint_upload(Source &src, const double *values_x, const double *values_y, int64_t n_samples, ValuePair &values);
 
 }  // namespace mbar
 }  // namespace me

@@ -36,6 +36,8 @@
 // ME_MAX_HISTOGRAM2D_SLOTS = 1296 keeps the whole table under 64 KiB of LDS (no dynamic-LDS attribute) and two workgroups, 2
 // wavefronts per SIMD, on a CU.  -DME_HIST2D_ROWS=4 / 2 / 1 forces that R wherever its table fits 64 KiB (to be measured
 // against).
+// histogram2d(), the argument checks and the two ways to a ValuePair are declared in me_mbar.h: me_mbar_hist2d_cov.hip runs them
+// first and takes its d_n and edges from the HistogramScratch they leave.
 // Registers (hipcc -O3, gfx950): profiles/mbar_slot_skeleton.txt; no AGPRs, no scratch, and the registers allow more
 // wavefronts per SIMD than the LDS (4 to 2 workgroups of 4 wavefronts), which is what limits the occupancy.
 #include "me_mbar_slots.h"
@@ -84,33 +86,15 @@ __global__ void __launch_bounds__(kThreads) k_mbar_hist2d(const double *__restri
   slot_pass<kRows, true>(energies, d, n_chains, record_stride, edges, where, rows, with_counts, n_tiles, partials, count_partials);
 }
 
-// A joint histogram request: the edges of both axes and the host outputs mass[n_temps][Bx + 3][By + 3], counts[Bx + 3][By + 3],
-// neff[n_temps] (each may be nullptr)
-struct Histogram2d {
-  const double *edges_x;
-  int n_bins_x;
-  const double *edges_y;
-  int n_bins_y;
-  double *mass;
-  int64_t *counts;
-  double *neff;
-};
+}  // namespace
 
-// The two value columns that go with the problem's samples: x and y share n_chains and record_stride; nullptr = the energy
-struct ValuePair {
-  const double *x, *y;
-  long long n_chains, record_stride;
-};
-
-// histogram_slots (me_mbar_hist.hip) for the S cells of the grid and the concatenated edges; R, the edges and both `top` are
-// worked out from the request before the problem is prepared
+// histogram_slots (me_mbar_hist.hip) for the S cells of the grid and the concatenated edges (me_mbar.h)
 hipError_t histogram2d(Problem &p, const Source &src, const ValuePair &values, const double *f, const double *temps, int n_temps,
-                       const Histogram2d &h) {
+                       const Histogram2d &h, HistogramScratch &keep) {
   const int n_edges_x = h.n_bins_x + 1, n_edges_y = h.n_bins_y + 1, n_cells = (h.n_bins_x + 3) * (h.n_bins_y + 3);
   const int rows = rows_per_pass(n_cells);
   std::vector<double> edges(h.edges_x, h.edges_x + n_edges_x);
   edges.insert(edges.end(), h.edges_y, h.edges_y + n_edges_y);
-  HistogramScratch keep;
   keep.top = top_of(n_edges_x);
   keep.top_y = top_of(n_edges_y);
   const size_t lds = slot_pass_lds(rows, n_cells, n_edges_x + n_edges_y, true);
@@ -126,18 +110,47 @@ hipError_t histogram2d(Problem &p, const Source &src, const ValuePair &values, c
                          SlotTable{edges.data(), n_edges_x + n_edges_y, n_cells, rows, h.mass, h.counts, h.neff, launch}, keep);
 }
 
-// the two forms of me_mbar_histogram_joint behind their Source
-int histogram2d_common(const Source &src, const ValuePair &values, const double *f, const double *temps, int n, const Histogram2d &h) {
+int check_histogram2d(const Source &src, const double *f, const double *temps, int n, const Histogram2d &h) {
   int rc = check_edges(src.e, h.edges_x, h.n_bins_x);
   if (rc) return rc;
   rc = check_edges(src.e, h.edges_y, h.n_bins_y);
   if (rc) return rc;
   if ((h.n_bins_x + 3) * (h.n_bins_y + 3) > ME_MAX_HISTOGRAM2D_SLOTS)
     return fail(src.e, ME_ERR_INVALID, "(n_bins_x + 3) (n_bins_y + 3) must not exceed " + std::to_string(ME_MAX_HISTOGRAM2D_SLOTS));
-  rc = check_f_and_targets(src.e, f, src.n_rungs, temps, n, 1);
+  return check_f_and_targets(src.e, f, src.n_rungs, temps, n, 1);
+}
+
+int joint_columns(const Source &src, int column_x, int column_y, ValuePair &values) {
+  ObsColumns x{}, y{};
+  int rc = histogram_column(src, column_x, x);
+  if (rc) return rc;
+  rc = histogram_column(src, column_y, y);
+  if (rc) return rc;
+  // recorded columns share the store's strides; the energy is read as the energy (nullptr), whatever the other axis is
+  const ObsColumns &strides = column_x >= 0 ? x : y;
+  values = ValuePair{column_x >= 0 ? x.data : nullptr, column_y >= 0 ? y.data : nullptr, strides.n_chains, strides.record_stride};
+  return ME_OK;
+}
+
+int joint_upload(Source &src, const double *values_x, const double *values_y, int64_t n_samples, ValuePair &values) {
+  const size_t column_bytes = sizeof(double) * (size_t)n_samples;
+  ME_HIP(nullptr, src.columns_dev.resize(2 * column_bytes));
+  double *columns = src.columns_dev.get<double>();
+  ME_HIP(nullptr, hipMemcpy(columns, values_x, column_bytes, hipMemcpyHostToDevice));
+  ME_HIP(nullptr, hipMemcpy(columns + n_samples, values_y, column_bytes, hipMemcpyHostToDevice));
+  values = ValuePair{columns, columns + n_samples, n_samples, 0};
+  return ME_OK;
+}
+
+namespace {
+
+// the two forms of me_mbar_histogram_joint behind their Source
+int histogram2d_common(const Source &src, const ValuePair &values, const double *f, const double *temps, int n, const Histogram2d &h) {
+  const int rc = check_histogram2d(src, f, temps, n, h);
   if (rc) return rc;
   Problem p;
-  return mbar_check_common(src.e, p, histogram2d(p, src, values, f, temps, n, h));
+  HistogramScratch keep;
+  return mbar_check_common(src.e, p, histogram2d(p, src, values, f, temps, n, h, keep));
 }
 
 }  // namespace
@@ -155,14 +168,9 @@ int me_mbar_histogram_joint(me_engine *e, const double *f, const double *temps, 
   Source src;
   int rc = src.from_engine(e);
   if (rc) return rc;
-  ObsColumns x{}, y{};
-  rc = histogram_column(src, column_x, x);
+  ValuePair values{};
+  rc = joint_columns(src, column_x, column_y, values);
   if (rc) return rc;
-  rc = histogram_column(src, column_y, y);
-  if (rc) return rc;
-  // recorded columns share the store's strides; the energy is read as the energy (nullptr), whatever the other axis is
-  const ObsColumns &strides = column_x >= 0 ? x : y;
-  const ValuePair values{column_x >= 0 ? x.data : nullptr, column_y >= 0 ? y.data : nullptr, strides.n_chains, strides.record_stride};
   return histogram2d_common(src, values, f, temps, n, Histogram2d{edges_x, n_bins_x, edges_y, n_bins_y, mass, counts, neff_fraction});
 }
 
@@ -172,14 +180,11 @@ int me_mbar_histogram_joint_samples(int32_t device_id, const double *energies, c
                                 const double *edges_y, int32_t n_bins_y, double *mass, int64_t *counts, double *neff_fraction) {
   if (!values_x || !values_y) return fail(nullptr, ME_ERR_INVALID, "null pointer");
   Source src;
-  const int rc = src.from_host(device_id, energies, rungs, n_samples, ladder_temps, n_rungs);
+  int rc = src.from_host(device_id, energies, rungs, n_samples, ladder_temps, n_rungs);
   if (rc) return rc;
-  const size_t column_bytes = sizeof(double) * (size_t)n_samples;
-  ME_HIP(nullptr, src.columns_dev.resize(2 * column_bytes));
-  double *columns = src.columns_dev.get<double>();
-  ME_HIP(nullptr, hipMemcpy(columns, values_x, column_bytes, hipMemcpyHostToDevice));
-  ME_HIP(nullptr, hipMemcpy(columns + n_samples, values_y, column_bytes, hipMemcpyHostToDevice));
-  const ValuePair values{columns, columns + n_samples, n_samples, 0};
+  ValuePair values{};
+  rc = joint_upload(src, values_x, values_y, n_samples, values);
+  if (rc) return rc;
   return src.finish(
       histogram2d_common(src, values, f, temps, n, Histogram2d{edges_x, n_bins_x, edges_y, n_bins_y, mass, counts, neff_fraction}));
 }

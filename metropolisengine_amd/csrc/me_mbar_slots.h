@@ -1,6 +1,7 @@
 // The device side that the histogram units share (me_mbar_hist.hip: the reweighted masses; me_mbar_hist_cov.hip: the slot
 // Gram sums behind their error bars; me_mbar_hist2d.hip: the joint masses of two quantities, whose "slot" is a cell of the
-// grid): ONE pass kernel body, slot_pass, and what it is made of.  A unit's kernel builds two small policies and calls it:
+// grid; me_mbar_hist2d_cov.hip: the cell Gram sums behind the error bars of those): ONE pass kernel body, slot_pass, and what
+// it is made of.  A unit's kernel builds two small policies and calls it:
 //   where a sample falls   Slots1d (one edge array, one value column, slot_of) or Slots2d (two of each; the slot is the cell
 //                          slot_x (By + 3) + slot_y; a value column that is nullptr is the energy itself);
 //   what the rows are      TemperatureRows<R> (row t = the state weight of temperature t of the chunk: the masses) or

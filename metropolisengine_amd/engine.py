@@ -893,6 +893,39 @@ class MetropolisEngine:
         out["names"] = (name_x, name_y)
         return out
 
+    def free_energy_surface_uncertainties(self, which_x, edges_x, which_y, edges_y, temps, f=None, inefficiency=1.0,
+                                          covariance=True):
+        """:meth:`free_energy_surface` with the asymptotic standard errors of the masses and of the surface
+        (``me_mbar_histogram_joint_gram``, on the device: ``K + 1`` weighted joint histograms per temperature and the ladder
+        block of the Gram matrix; the samples stay there).  Arguments as there.  Returns every key of
+        :meth:`free_energy_surface`, bit for bit, and ``{"d_mass", "d_mass_slots", "d_outside", "d_free_energy", "lowest",
+        "d_free_energy_from_lowest", "n_samples"}`` and, with ``covariance=True``, ``"log_mass_cov"`` ``(T, Bx By, Bx By)``, see
+        :func:`metropolisengine_amd.statistics.mbar_free_energy_surface_uncertainties`: the error of a saddle height ``F_c -
+        F_c'`` at temperature ``t`` is ``T sqrt(C[c, c] + C[c', c'] - 2 C[c, c'])`` with ``C = log_mass_cov[t]`` and the cell
+        index ``bx * By + by``.  ``covariance=False`` leaves that matrix out (9.5 MB per temperature at 33 x 33 bins).
+        ``inefficiency``: the statistical inefficiency of the recorded series, a finite scalar ``>= 1`` that multiplies every
+        variance, or ``"recorded"``: the largest ``g`` of :meth:`recorded_inefficiency` over the rungs and over the energy (the
+        weights depend on it), ``which_x`` and ``which_y`` (the cells do); deliberately conservative.  ``ValueError`` as
+        :meth:`free_energy_surface` and for an invalid ``inefficiency`` or ``covariance``; raises without a ladder or without
+        records."""
+        from . import statistics
+        covariance = statistics.validate_surface_covariance(covariance)
+        if isinstance(inefficiency, str):
+            columns = tuple(sorted({c for c in (self._profile_column(which_x)[0], self._profile_column(which_y)[0]) if c >= 0}))
+            inefficiency = self._recorded_g(inefficiency, [columns])[0]
+        g = statistics.validate_profile_inefficiency(inefficiency)
+        temps = statistics.validate_mbar_temps(temps)
+        edges_x, edges_y = statistics.validate_histogram2d_edges(edges_x, edges_y)
+        (column_x, name_x), (column_y, name_y) = self._profile_column(which_x), self._profile_column(which_y)
+        if f is None:
+            f = self.ladder_free_energies()["f"]
+        f = self._ladder_f(f, finite=False)
+        k = max(f.size, 1)      # (the ladder's rungs; without a ladder the library refuses before it writes)
+        out = statistics._free_energy_surface_uncertainties(self._lib.me_mbar_histogram_joint_gram, (self._handle,), k, f, temps,
+                                                            (column_x,), edges_x, (column_y,), edges_y, g, covariance)
+        out["names"] = (name_x, name_y)
+        return out
+
     def _profile_column(self, which):
         """``(column of the C ABI, name)`` of the quantity a profile runs along: -1 for ``"energy"``."""
         if isinstance(which, str) and which == "energy":

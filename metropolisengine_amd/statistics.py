@@ -763,6 +763,170 @@ def mbar_free_energy_profile_uncertainties(energies, rungs, temps, f, targets, v
                                               targets, (_capi.double_ptr(a),), edges, g)
 
 
+def validate_surface_covariance(covariance):
+    """The ``covariance`` switch of the surface's error bars: ``True`` or ``False`` (``bool`` or ``np.bool_``; ``ValueError``
+    for anything else, so that a misplaced positional argument is not read as a truth value)."""
+    if not isinstance(covariance, (bool, np.bool_)):
+        raise ValueError("covariance must be True or False, not %r" % (covariance,))
+    return bool(covariance)
+
+
+def _ladder_response(ladder_gram, column_counts):
+    """``M = N^{1/2} (I - N^{1/2} G_KK N^{1/2})^+ N^{1/2}`` (K x K; the pseudo-inverse cut at ``rcond = 1e-10`` as in
+    :func:`mbar_theta`): what is left of MBAR's asymptotic covariance for columns of the weight matrix that have no samples of
+    their own.  For two such columns ``a``, ``b`` with Gram entries ``G_ab`` and ``G_Ka``, ``G_Kb`` against the ladder,
+    ``Theta_ab = G_ab + G_Ka^T M G_Kb``."""
+    root = np.sqrt(np.asarray(column_counts, dtype=np.float64))
+    g = np.asarray(ladder_gram, dtype=np.float64)
+    inner = np.eye(root.size) - root[:, None] * g * root[None, :]
+    return root[:, None] * np.linalg.pinv(inner, rcond=1e-10) * root[None, :]
+
+
+def _surface_uncertainty_result(temps, edges_x, edges_y, mass, counts, neff, cell_gram, ladder_gram, column_counts, n_used,
+                                inefficiency, covariance):
+    """The dictionary of :func:`mbar_free_energy_surface_uncertainties` from what ``me_mbar_histogram_joint_gram`` returns
+    (``mass`` ``(T, Bx + 3, By + 3)``, ``cell_gram`` ``(T, K + 1, S)``).  The ``(K + 1 + S)``-column Gram matrix of
+    :func:`_profile_uncertainty_result` is NOT assembled: the state and cell columns have no samples of their own, so with ``M``
+    of :func:`_ladder_response`, ``H = cell_gram[t]``, ``p`` the masses and
+        ``u_c = H[:K, c] / p_c - sum_c' H[:K, c']``,   ``h_c = H[K][c] / p_c``,
+    ``Cov(ln p_c, ln p_c') = delta_cc' H[K][c] / p_c^2 - h_c - h_c' + sum_c'' H[K][c''] + u_c^T M u_c'``.  (``N^{1/2} u_c`` is
+    orthogonal to the null vector ``N^{1/2} 1`` of the bracket because ``sum_j N_j W_nj = 1``: the cut of the pseudo-inverse does
+    not enter.)  The diagonal, the differences from the lowest cell and the variance of a sum of masses need ``u``, ``h`` and
+    ``M u`` only, O(S K^2) work; the ``L x L`` matrix over the live inner cells is formed with ``covariance`` alone.  The rules
+    for empty and unresolved cells are :func:`_profile_uncertainty_result`'s."""
+    out = _surface_result(temps, edges_x, edges_y, mass, counts, neff)
+    k, nt = ladder_gram.shape[0], temps.size
+    bx, by = edges_x.size - 1, edges_y.size - 1
+    n_cells = (bx + 3) * (by + 3)
+    inner = np.zeros((bx + 3, by + 3), dtype=bool)
+    inner[:bx, :by] = True
+    inner = inner.ravel()
+    # flat index bx_ * by + by_ of the inner grid for every cell of the full table (-1 outside)
+    to_inner = np.full(n_cells, -1, dtype=np.intp)
+    to_inner[inner] = np.arange(bx * by)
+    d_cell = np.zeros((nt, n_cells))
+    d_free, d_lowest = np.full((nt, bx * by), np.nan), np.full((nt, bx * by), np.nan)
+    d_outside = np.zeros(nt)
+    lowest = np.zeros((nt, 2), dtype=np.int64)
+    log_cov = np.full((nt, bx * by, bx * by), np.nan) if covariance else None      # (9.5 MB per temperature at 33 x 33 bins)
+    response = _ladder_response(ladder_gram, column_counts)
+    for t in range(nt):
+        p, h = mass[t].ravel(), cell_gram[t]
+        resolved = h[k] >= np.finfo(np.float64).tiny
+        d_cell[t, (p > 0) & ~resolved] = np.nan          # (a mass, but no error bar; an empty cell keeps 0)
+        live = np.flatnonzero(resolved)
+        if live.size == 0:
+            continue
+        pl = p[live]
+        u = h[:k, live] / pl[None, :] - h[:k].sum(axis=1)[:, None]
+        to_state = h[k, live] / pl
+        own_term = h[k, live] / pl ** 2
+        state = h[k].sum()
+        mu = response @ u
+        var = (own_term - 2.0 * to_state + state + np.einsum("kc,kc->c", u, mu)) * inefficiency
+        root = np.sqrt(np.clip(var, 0.0, None))
+        d_cell[t, live] = pl * root
+        # Var sum_c p_c over the live cells outside the inner grid = sum_cc' p_c p_c' C_cc'
+        out_live = ~inner[live]
+        if out_live.any():
+            po = pl[out_live]
+            v = u[:, out_live] @ po
+            own_sum, total = h[k, live][out_live].sum(), po.sum()
+            var_out = own_sum - 2.0 * total * own_sum + total * total * state + v @ (response @ v)
+            d_outside[t] = np.sqrt(max(var_out * inefficiency, 0.0))
+        bins = inner[live]
+        own = to_inner[live[bins]]
+        if own.size == 0:
+            continue
+        d_free[t, own] = temps[t] * root[bins]
+        lowest[t] = np.unravel_index(int(np.argmax(out["density"][t])), (bx, by))
+        low = int(lowest[t, 0]) * by + int(lowest[t, 1])
+        at = np.flatnonzero(own == low)
+        if at.size:
+            at = int(np.flatnonzero(bins)[at[0]])
+            du = u[:, bins] - u[:, at][:, None]
+            diff = (own_term[bins] + own_term[at] + np.einsum("kc,kc->c", du, response @ du)) * inefficiency
+            d_lowest[t, own] = temps[t] * np.sqrt(np.clip(diff, 0.0, None))
+            d_lowest[t, low] = 0.0
+        if covariance:
+            ub = u[:, bins]
+            cov = ub.T @ mu[:, bins] - to_state[bins][:, None] - to_state[bins][None, :] + state
+            cov[np.arange(own.size), np.arange(own.size)] += own_term[bins]
+            if own.size == bx * by:                      # (every inner cell live: own is 0 .. Bx By - 1 in order)
+                log_cov[t] = cov * inefficiency
+            else:
+                log_cov[t][np.ix_(own, own)] = cov * inefficiency
+    d_slots = d_cell.reshape(nt, bx + 3, by + 3)
+    out.update({"d_mass": d_slots[:, :bx, :by].copy(), "d_mass_slots": d_slots, "d_outside": d_outside,
+                "d_free_energy": d_free.reshape(nt, bx, by), "lowest": lowest,
+                "d_free_energy_from_lowest": d_lowest.reshape(nt, bx, by), "n_samples": int(n_used)})
+    if covariance:
+        out["log_mass_cov"] = log_cov
+    return out
+
+
+def _free_energy_surface_uncertainties(fn, lead, n_rungs, f, targets, middle_x, edges_x, middle_y, edges_y, inefficiency,
+                                       covariance):
+    """``middle_x`` / ``middle_y``: as in :func:`_free_energy_surface`."""
+    bx, by, k = edges_x.size - 1, edges_y.size - 1, n_rungs
+    mass, counts = np.zeros((targets.size, bx + 3, by + 3)), np.zeros((bx + 3, by + 3), dtype=np.int64)
+    neff = np.zeros(targets.size)
+    cell_gram = np.zeros((targets.size, k + 1, (bx + 3) * (by + 3)))
+    ladder_gram, column_counts = np.zeros((k, k)), np.zeros(k)
+    n_used = ctypes.c_int64()
+    _call(fn, lead, _capi.double_ptr(f), _capi.double_ptr(targets), targets.size, *middle_x, _capi.double_ptr(edges_x), bx,
+          *middle_y, _capi.double_ptr(edges_y), by, _capi.double_ptr(cell_gram), _capi.double_ptr(ladder_gram),
+          _capi.double_ptr(column_counts), _capi.double_ptr(mass), _capi.int64_ptr(counts), _capi.double_ptr(neff),
+          ctypes.byref(n_used))
+    return _surface_uncertainty_result(targets, edges_x, edges_y, mass, counts, neff, cell_gram, ladder_gram, column_counts,
+                                       n_used.value, inefficiency, covariance)
+
+
+def mbar_free_energy_surface_uncertainties(energies, rungs, temps, f, targets, values_x, edges_x, values_y, edges_y,
+                                           inefficiency=1.0, covariance=True, device=0):
+    """:func:`mbar_free_energy_surface` with the asymptotic standard errors of its masses and of the free-energy surface
+    (``me_mbar_histogram_joint_gram_samples``; the engine form is ``MetropolisEngine.free_energy_surface_uncertainties``).  The
+    cell indicators are disjoint columns of the MBAR weight matrix, as the bins of
+    :func:`mbar_free_energy_profile_uncertainties` are: ``K + 1`` weighted joint histograms per temperature
+    (csrc/me_mbar_hist2d_cov.hip) hold everything their Gram matrix needs, and because those columns have no samples of their own
+    the algebra reduces to ONE ``K x K`` pseudo-inverse and O(S K^2) products per temperature, in float64 here; no matrix over
+    the up to 1296 cells is inverted.
+
+    Returns every key of :func:`mbar_free_energy_surface`, bit for bit, and ``d_mass`` ``(T, Bx, By)``: the standard errors ``p
+    sqrt(Var ln p)`` of the inner grid's masses; ``d_mass_slots`` ``(T, Bx + 3, By + 3)``: the same over all cells; ``d_outside``
+    ``(T,)``: the error of ``outside``, from ``Var sum p_c = sum p_c p_c' C_cc'`` over the cells outside the inner grid;
+    ``d_free_energy`` ``(T, Bx, By)``: ``T sqrt(Var ln p)``, the standard error of ``free_energy``; ``lowest`` ``(T, 2)``: the cell
+    of largest density; ``d_free_energy_from_lowest`` ``(T, Bx, By)``: the standard error of ``F - F_lowest`` (0 at ``lowest``);
+    ``n_samples``: the samples with a finite energy; and, with ``covariance=True``, ``log_mass_cov`` ``(T, Bx By, Bx By)``:
+    ``Cov(ln p_c, ln p_c')`` with the cell index ``bx * By + by``, from which the error of any difference ``F_c - F_c'`` -- a
+    saddle height -- follows as ``T sqrt(C_cc + C_c'c' - 2 C_cc')``.  At 33 x 33 bins that matrix is 9.5 MB per temperature:
+    ``covariance=False`` leaves it out and forms no matrix over the cells at all; every other key is the same, bit for bit.
+
+    A cell whose mass is exactly 0 drops out of the algebra: its ``d_mass`` is 0, its ``d_free_energy``,
+    ``d_free_energy_from_lowest`` and its row and column of ``log_mass_cov`` are NaN.  The rule goes by the MASS, not by
+    ``counts``: at a cold target the weights of a cell that only hot rungs populate can all underflow.  The same holds, with
+    ``d_mass`` NaN as well, for a cell whose mass is positive but below about 1.5e-154: the sum of its squared weights is no
+    normal float64 any more and no error bar can be formed, although ``free_energy`` is still finite there.  Every other cell and
+    temperature keeps its results (``d_outside`` sums the cells that have an error bar).
+
+    The formula assumes INDEPENDENT samples: pass the statistical inefficiency of the series as ``inefficiency`` (a finite
+    scalar ``>= 1``, ``ValueError`` otherwise) and every variance is multiplied by it.  ``ValueError`` also for a ``covariance``
+    that is not ``True`` or ``False``."""
+    g = validate_profile_inefficiency(inefficiency)
+    covariance = validate_surface_covariance(covariance)
+    e, r, t = validate_mbar_samples(energies, rungs, temps)
+    targets = validate_mbar_temps(targets, "targets")
+    f = validate_mbar_f(f, t.size)
+    edges_x, edges_y = validate_histogram2d_edges(edges_x, edges_y)
+    a = np.ascontiguousarray(np.asarray(values_x, dtype=np.float64).ravel())
+    b = np.ascontiguousarray(np.asarray(values_y, dtype=np.float64).ravel())
+    if a.size != e.size or b.size != e.size:
+        raise ValueError("values_x and values_y need one entry per sample (%d), got %d and %d" % (e.size, a.size, b.size))
+    return _free_energy_surface_uncertainties(_capi.load().me_mbar_histogram_joint_gram_samples, _host_samples(device, e, r, t),
+                                              t.size, f, targets, (_capi.double_ptr(a), _capi.double_ptr(b)), edges_x, (), edges_y,
+                                              g, covariance)
+
+
 def get_equilibration_points(df, device=None):
     """Per column ``[t0, g, Neff_max]``; constant columns are skipped and complex columns split into ``_real`` /
     ``_imag`` (statistics.py:25-48).  With ``device`` set, all columns go to the GPU in one batch."""

@@ -13,6 +13,10 @@
                                                      profiles/mbar_profile_uncertainty.txt)
     python tools/bench_mbar.py --surface            (joint histograms along two observables on 8 x 8, 16 x 16 and 33 x 33 bins
                                                      beside the 1-D histograms, profiles/mbar_surface.txt)
+    python tools/bench_mbar.py --surface-uncertainty --rungs 8 32
+                                                    (the error bars of those joint histograms beside the histograms themselves and
+                                                     the host algebra with and without the cell covariance,
+                                                     profiles/mbar_surface_uncertainty.txt)
     python tools/bench_mbar.py --newton             (the Newton solver beside the self-consistent one: one pass and the whole
                                                      solve, profiles/mbar_newton.txt)
     python tools/bench_mbar.py --inefficiency       (statistical inefficiencies of the recorded series with 0, 4 and 16 recorded
@@ -329,6 +333,76 @@ def time_surface(k, log2_chains, records, n_targets=8, grids=(8, 16, 33), bins=(
                      ", ".join("%.2f x the %d-bin profile" % (ms / plain[b], b) for b in bins)), flush=True)
 
 
+def surface_gram_rows(n_cells):
+    """rule_rows of csrc/me_mbar_hist2d_cov.hip: the rows per pass, the widest of 16, 8, 4, 2, 1 whose table, at most ``(32 R +
+    2) S`` bytes, leaves three workgroups within the 160 KiB of a CU (16 up to 106 cells, 8 to 211, 4 to 420, 2 to 827)."""
+    return next((r for r in (16, 8, 4, 2) if n_cells <= (160 * 1024 // 3) // (32 * r + 2)), 1)
+
+
+def time_surface_uncertainty(k, log2_chains, records, n_targets=8, grids=(8, 16, 33), forced_rows=0, sums_only=False):
+    """me_mbar_histogram_joint_gram (csrc/me_mbar_hist2d_cov.hip) on the two inputs of :func:`time_surface`, beside
+    me_mbar_histogram_joint on the same samples in the same run.  Whole calls.  ``sums`` is the C entry point with ladder_gram =
+    NULL: the joint histogram's own kernels and ``n_targets ceil((K + 1) / R)`` passes of the cell Gram kernel; the whole call adds
+    the Gram pass of the K ladder columns and the host algebra, which is also timed alone with and without the cell covariance.
+    ``forced_rows``: the R of a library built with ``-DME_HIST2D_COV_ROWS=R`` (selected with METROPOLIS_HIP_LIB), used wherever
+    its table fits 64 KiB, for the pass counts that are printed.  ``sums_only``: the cell Gram sums alone (the forced-R runs)."""
+    import ctypes
+    from metropolisengine_amd import statistics
+    eng, _ = loaded_engine(k, log2_chains, records)
+    n = records << log2_chains
+    f = eng.ladder_free_energies(tol=1e-8)["f"]
+    targets = np.geomspace(0.5, 3.0, n_targets)
+    dp = ctypes.POINTER(ctypes.c_double)
+
+    energies = eng.energy_samples()
+    eng.record_observables([0, 1])
+    eng.set_energy_samples(energies)
+    one_bin, many_bins = lane_patterns(eng.n_chains)           # (the 64 bins as an 8 x 8 block of the grid)
+    inputs = (("every sample in one cell", np.stack([one_bin + 0.5] * 2)),
+              ("consecutive samples in 64 different cells", np.stack([many_bins // 8 + 0.5, many_bins % 8 + 0.5])))
+    print("K = %d, %d samples, %d targets" % (k, n, n_targets), flush=True)
+    for label, rows in inputs:
+        eng.set_observable_samples(np.broadcast_to(rows[None, :, :], (records, 2, eng.n_chains)))
+        print("    %s" % label, flush=True)
+        for g in grids:
+            edges = np.linspace(0.0, float(g), g + 1)
+            cells = (g + 3) * (g + 3)
+            r = forced_rows if forced_rows and (32 * forced_rows + 2) * cells <= 64 * 1024 else surface_gram_rows(cells)
+            out = eng.free_energy_surface_uncertainties(0, edges, 1, edges, targets, f, covariance=False)
+            assert out["counts_slots"].sum() == n and np.all(np.isfinite(out["d_mass_slots"]))
+            h = np.zeros((n_targets, k + 1, cells))
+            sums = best(lambda: eng._check(eng._lib.me_mbar_histogram_joint_gram(
+                eng._handle, f.ctypes.data_as(dp), targets.ctypes.data_as(dp), n_targets, 0, edges.ctypes.data_as(dp), g, 1,
+                edges.ctypes.data_as(dp), g, h.ctypes.data_as(dp), None, None, None, None, None, None)))
+            passes = n_targets * -(-(k + 1) // r)
+            if sums_only:
+                print("        %2d x %2d bins (%4d cells): cell Gram sums %.3f ms (R = %d: %d passes)" % (g, g, cells, sums, r, passes),
+                      flush=True)
+                continue
+            plain = best(lambda: eng.free_energy_surface(0, edges, 1, edges, targets, f))
+            whole = best(lambda: eng.free_energy_surface_uncertainties(0, edges, 1, edges, targets, f))
+            lean = best(lambda: eng.free_energy_surface_uncertainties(0, edges, 1, edges, targets, f, covariance=False))
+            plain_passes = -(-n_targets // surface_rows(cells))
+            print("        %2d x %2d bins (%4d cells): free_energy_surface %.3f ms (%d passes); cell Gram sums %.3f ms (R = %d: %d more "
+                  "passes) = %.2f x, %.3f ms per added pass; free_energy_surface_uncertainties %.3f ms = %.2f x, with covariance=False "
+                  "%.3f ms" % (g, g, cells, plain, plain_passes, sums, r, passes, sums / plain, (sums - plain) / passes, whole,
+                               whole / plain, lean), flush=True)
+    # the host algebra alone on a full grid: random positive sums of the right shapes (every cell live)
+    rng = np.random.default_rng(5)
+    for g in () if sums_only else grids:
+        edges = np.linspace(0.0, float(g), g + 1)
+        cells = (g + 3) * (g + 3)
+        mass = rng.random((n_targets, g + 3, g + 3)) + 0.1
+        mass /= mass.reshape(n_targets, -1).sum(axis=1)[:, None, None]
+        w = rng.random((4 * k, k)) / (4 * k)
+        args = (targets, edges, edges, mass, np.ones((g + 3, g + 3), dtype=np.int64), np.ones(n_targets),
+                rng.random((n_targets, k + 1, cells)) * 1e-3, w.T @ w, np.full(k, 4.0), n, 1.0)
+        with_cov = best(lambda: statistics._surface_uncertainty_result(*args, True))
+        without = best(lambda: statistics._surface_uncertainty_result(*args, False))
+        print("    host algebra, %2d x %2d bins, %d targets, all %d cells live: %.3f ms with the cell covariance, %.3f ms without"
+              % (g, g, n_targets, cells, with_cov, without), flush=True)
+
+
 def time_newton(k, log2_chains, records, dim=DIM, ratio=None):
     """One pass and the whole solve of me_mbar_solve_newton (csrc/me_mbar_newton.hip) beside me_mbar_solve on the same samples
     in the same run.  A pass = (wall time of a solve limited to b passes - one limited to a passes) / (b - a) at a tolerance no
@@ -467,10 +541,12 @@ if __name__ == "__main__":
     ap.add_argument("--profile", action="store_true")
     ap.add_argument("--profile-uncertainty", action="store_true")
     ap.add_argument("--surface", action="store_true")
+    ap.add_argument("--surface-uncertainty", action="store_true")
+    ap.add_argument("--sums-only", action="store_true", help="with --surface-uncertainty: time the cell Gram sums alone")
     ap.add_argument("--newton", action="store_true")
     ap.add_argument("--rows-per-pass", type=int, default=0, help="with --profile-uncertainty: the R of a -DME_HIST_COV_ROWS=R library; "
-                    "with --surface: of a -DME_HIST2D_ROWS=R library")
-    ap.add_argument("--grids", type=int, nargs="*", default=[8, 16, 33], help="with --surface: the bins per axis")
+                    "with --surface: of a -DME_HIST2D_ROWS=R library; with --surface-uncertainty: of a -DME_HIST2D_COV_ROWS=R library")
+    ap.add_argument("--grids", type=int, nargs="*", default=[8, 16, 33], help="with --surface and --surface-uncertainty: the bins per axis")
     ap.add_argument("--inefficiency", action="store_true")
     cli = ap.parse_args()
     if cli.inefficiency:
@@ -480,6 +556,11 @@ if __name__ == "__main__":
         for k in (8, 32, 64):
             time_newton(k, cli.log2_chains, cli.records)
         time_newton(16, cli.log2_chains, max(1, cli.records // 32), dim=64, ratio=1.35)     # the poorly overlapping ladder
+        sys.exit(0)
+    if cli.surface_uncertainty:
+        for k in cli.rungs:
+            time_surface_uncertainty(k, cli.log2_chains, cli.records, grids=cli.grids, forced_rows=cli.rows_per_pass,
+                                     sums_only=cli.sums_only)
         sys.exit(0)
     if cli.surface:
         time_surface(8, cli.log2_chains, cli.records, grids=cli.grids, forced_rows=cli.rows_per_pass)
