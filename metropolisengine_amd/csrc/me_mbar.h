@@ -2,7 +2,8 @@
 // the Gram matrix of the weight matrix for the asymptotic covariance; me_mbar_obs.hip: recorded observables and their
 // reweighting; me_mbar_hist.hip: reweighted histograms along an observable; me_mbar_hist_cov.hip: the slot Gram sums behind
 // their error bars; me_mbar_hist2d.hip: joint histograms along two; me_mbar_hist2d_cov.hip: the cell Gram sums behind theirs --
-// four pairings of the policies of one pass kernel, me_mbar_slots.h, behind one host driver, histogram_slots): the tile policy,
+// four pairings of the policies of one pass kernel, me_mbar_slots.h, behind two host drivers, histogram_slots for the masses and
+// slot_gram_passes for the Gram sums): the tile policy,
 // the device table of a ladder, the per-sample sums, and the host scaffolding of an entry point, which me_mbar.hip defines:
 // where the samples come from (Source), the prepared problem (Problem, prepare) and the argument checks.  Private to the host
 // side, like me_engine.h.
@@ -207,6 +208,33 @@ int check_edges(me_engine *e, const double *edges, int n_bins);
 // `values` = the column of an engine's Source that a histogram entry point names: a recorded column (ME_ERR_STATE without an
 // observable store, ME_ERR_INVALID beyond the recorded columns) or, for -1, the energies themselves
 int histogram_column(const Source &src, int column, ObsColumns &values);
+
+// ---- defined in me_mbar_hist_cov.hip ------------------------------------------------------------------------------------
+// The slot Gram sums of n_slots columns for slot_gram_passes: the rows per pass, the host output gram[n_temps][n_rungs + 1]
+// [n_slots] (nullptr: not asked for), and `launch`, which enqueues on the problem's stream the unit's pass kernel (slot_pass
+// with GramRows<rows>) for rows j0 .. j0 + n_rows, n_rows <= rows, of target t (p.w.inv_temps + t, p.w.out + 4 t) into
+// partials[block][rows][n_slots]
+struct SlotGramTable {
+  int n_slots, rows;
+  double *gram;
+  std::function<hipError_t(int t, int j0, int n_rows, double *partials)> launch;
+};
+// The driver of the Gram units, for a problem whose histogram_slots has just run (p.w.inv_temps and p.w.out hold its targets):
+// one pass per (t, chunk of `rows` rows), each followed by the sum of its block partials, then one copy to table.gram.  Waits
+// for the stream.
+hipError_t slot_gram_passes(Problem &p, const SlotGramTable &table, int n_temps);
+// The stages of a *_gram entry point behind its argument checks: `histogram` (the unit's histogram into `keep`) in a problem of
+// its own, in which the sums of `gram_table` follow when their output is asked for; then, with that problem's device scratch
+// and d_n freed, the ladder block ladder_gram[K][K] and column_counts[K] (mbar_gram with no targets, me_mbar_cov.hip) in a
+// second problem when either is asked for, and *n_used.  `gram_table` may refer to the problem and to `keep`.
+struct LadderGram {
+  double *ladder_gram, *column_counts;
+  int64_t *n_used;
+};
+int histogram_gram_stages(const Source &src, const double *f, int n_temps,
+                          const std::function<hipError_t(Problem &, HistogramScratch &)> &histogram,
+                          const std::function<SlotGramTable(const Problem &, const HistogramScratch &)> &gram_table,
+                          const LadderGram &out);
 
 // ---- defined in me_mbar_hist2d.hip --------------------------------------------------------------------------------------
 // A joint histogram request: the edges of both axes and the host outputs mass[n_temps][Bx + 3][By + 3], counts[Bx + 3][By + 3],

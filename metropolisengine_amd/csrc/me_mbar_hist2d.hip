@@ -53,23 +53,17 @@ namespace {
 #endif
 // 0: the rule of rows_per_pass; 4, 2, 1: that R wherever its table fits 64 KiB (to be measured against)
 constexpr int kForcedRows = ME_HIST2D_ROWS;
-constexpr size_t kCuLds = 160 * 1024;           // LDS of a CU
+constexpr int kMaxRows = 4;
 constexpr int kMinBlocksPerCu = 3;              // 3 wavefronts per SIMD: the measured choice (the header comment)
 
-// the most LDS a workgroup needs for S cells at R temperatures per pass, whatever the two bin counts: the tables and at most
-// 2 S bytes of edges
-constexpr size_t lds_bound(int rows, int n_cells) { return slot_pass_lds(rows, n_cells, 0, true) + 2 * (size_t)n_cells; }
-constexpr int cells_at(int rows) { return (int)(kCuLds / kMinBlocksPerCu / lds_bound(rows, 1)); }
-constexpr int kCells4 = cells_at(4), kCells2 = cells_at(2);
-static_assert(kCells4 == 374 && kCells2 == 666, "the thresholds of the header comment");
-static_assert(lds_bound(1, ME_MAX_HISTOGRAM2D_SLOTS) <= 64 * 1024, "the largest table needs no dynamic-LDS attribute");
+// the joint rule (me_mbar_slots.h) for tables WITH counts: S (32 R + 18) bytes at most
+constexpr int cells_at(int rows) { return joint_cells_at(rows, true, kMinBlocksPerCu); }
+static_assert(cells_at(4) == 374 && cells_at(2) == 666, "the thresholds of the header comment");
+static_assert(joint_lds_bound(1, ME_MAX_HISTOGRAM2D_SLOTS, true) <= 64 * 1024, "the largest table needs no dynamic-LDS attribute");
 
 // R of a launch, from the number of cells alone.  tools/bench_mbar.py (surface_rows) restates this rule to print its pass
 // counts: change both together.
-int rows_per_pass(int n_cells) {
-  if (kForcedRows && lds_bound(kForcedRows, n_cells) <= 64 * 1024) return kForcedRows;
-  return n_cells <= kCells4 ? 4 : n_cells <= kCells2 ? 2 : 1;
-}
+int rows_per_pass(int n_cells) { return joint_rows_per_pass(n_cells, kMaxRows, true, kMinBlocksPerCu, kForcedRows); }
 
 // values_x / values_y: the two value columns (Slots2d; nullptr: the axis is the energy itself); edges = [edges_x | edges_y];
 // ln_z has stride 4 (reweight_enqueue's out); with_counts: this pass also counts

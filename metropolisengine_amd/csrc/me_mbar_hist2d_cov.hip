@@ -9,7 +9,9 @@
 // with W_nj k_mbar_gram's fill and w_nt state_weight (me_mbar_slots.h).  The indicator columns of one target are disjoint, so
 // every entry of the Gram matrix that involves them follows from H, the masses and the ladder block exactly as in the 1-D
 // unit.  The host never assembles the (K + 1 + S)-column matrix: the state and cell columns have no samples of their own, so
-// the covariance of the log masses reduces to a K x K problem (statistics.py, _surface_uncertainty_result).
+// the covariance of the log masses reduces to a K x K problem (statistics.py, _SlotLogCovariance, for bins and cells alike).
+// The host driver and the stages of the entry points are the 1-D unit's (slot_gram_passes, histogram_gram_stages, me_mbar.h):
+// this file keeps its kernel, its choice of R and its launch.
 //
 // Kernels.  The masses, counts, ln_z_t and d_n are those of histogram2d() (me_mbar_hist2d.hip), called first: the same code,
 // the same bits.  k_mbar_hist2d_cov<R> is slot_pass (me_mbar_slots.h, which describes the scheme and the summation order) with
@@ -49,15 +51,15 @@ namespace {
 // 0: the rule of rows_per_pass; 16, 8, 4, 2, 1: that R wherever its table fits 64 KiB (to be measured against)
 constexpr int kForcedRows = ME_HIST2D_COV_ROWS;
 constexpr int kMaxRows = 16;
-constexpr size_t kCuLds = 160 * 1024;           // LDS of a CU
 constexpr int kMinBlocksPerCu = 3;              // 3 wavefronts per SIMD: me_mbar_hist2d.hip's measured choice (the header comment)
 static_assert(kForcedRows == 0 || kForcedRows == 1 || kForcedRows == 2 || kForcedRows == 4 || kForcedRows == 8 || kForcedRows == 16,
               "ME_HIST2D_COV_ROWS must be one of the kernel's instantiations");
 
-// the most LDS a workgroup needs for S cells at R rows per pass, whatever the two bin counts: the tables and at most 2 S bytes
-// of edges
-constexpr size_t lds_bound(int rows, int n_cells) { return slot_pass_lds(rows, n_cells, 0, false) + 2 * (size_t)n_cells; }
-constexpr int cells_at(int rows) { return (int)(kCuLds / kMinBlocksPerCu / lds_bound(rows, 1)); }
+// The joint rule (me_mbar_slots.h) for tables WITHOUT counts: R of a launch, from the number of cells alone.
+// tools/bench_mbar.py (surface_gram_rows) restates this rule to print its pass counts: change both together.
+constexpr size_t lds_bound(int rows, int n_cells) { return joint_lds_bound(rows, n_cells, false); }
+constexpr int cells_at(int rows) { return joint_cells_at(rows, false, kMinBlocksPerCu); }
+constexpr int rule_rows(int n_cells) { return joint_rule_rows(n_cells, kMaxRows, false, kMinBlocksPerCu); }
 static_assert(lds_bound(16, 1) == 514 && lds_bound(1, 1) == 34, "32 R S + 2 S bytes");
 static_assert(cells_at(16) == 106 && cells_at(8) == 211 && cells_at(4) == 420 && cells_at(2) == 827,
               "the thresholds of the header comment");
@@ -65,21 +67,10 @@ static_assert(lds_bound(16, cells_at(16)) <= 64 * 1024 && lds_bound(8, cells_at(
                   lds_bound(4, cells_at(4)) <= 64 * 1024 && lds_bound(2, cells_at(2)) <= 64 * 1024 &&
                   lds_bound(1, ME_MAX_HISTOGRAM2D_SLOTS) <= 64 * 1024,
               "no table of the rule needs the dynamic-LDS attribute");
-
-// R of a launch, from the number of cells alone.  tools/bench_mbar.py (surface_gram_rows) restates this rule to print its pass
-// counts: change both together.
-constexpr int rule_rows(int n_cells) {
-  for (int rows = kMaxRows; rows > 1; rows /= 2)
-    if (n_cells <= cells_at(rows)) return rows;
-  return 1;
-}
 static_assert(rule_rows(106) == 16 && rule_rows(107) == 8 && rule_rows(212) == 4 && rule_rows(421) == 2 && rule_rows(828) == 1 &&
                   rule_rows(ME_MAX_HISTOGRAM2D_SLOTS) == 1,
               "the thresholds of the header comment");
-int rows_per_pass(int n_cells) {
-  if (kForcedRows && lds_bound(kForcedRows, n_cells) <= 64 * 1024) return kForcedRows;
-  return rule_rows(n_cells);
-}
+int rows_per_pass(int n_cells) { return joint_rows_per_pass(n_cells, kMaxRows, false, kMinBlocksPerCu, kForcedRows); }
 
 // One pass: rows j0 .. j0 + n_rows (n_rows <= kRows, j0 + n_rows <= n_rungs + 1) of target *inv_temp, *ln_z (GramRows).
 // Samples and values are addressed as in k_mbar_hist2d.
@@ -108,70 +99,37 @@ void launch_pass(const Problem &p, const ValuePair &values, const HistogramScrat
                      tiles_of(p.sm.n_samples), partials);
 }
 
-// cell_gram[n_temps][n_rungs + 1][S] (host) of a problem whose histogram2d() has just run: p.w.inv_temps and p.w.out hold its
-// targets, `keep` its d_n and edges.  Waits for the stream.
-hipError_t cell_gram(Problem &p, const ValuePair &values, const HistogramScratch &keep, const Histogram2d &h, int n_temps,
-                     double *cell_gram) {
-  const int n_cells = (h.n_bins_x + 3) * (h.n_bins_y + 3), n_blocks = blocks_of(p.sm.n_samples), n_cols = p.n_rungs + 1;
-  const int rows = rows_per_pass(n_cells);
-  const size_t entries = (size_t)n_temps * n_cols * n_cells;
-  DeviceBuffer partials, sums;
-  ME_MBAR_HIP(partials.resize((size_t)n_blocks * rows * n_cells * sizeof(double)));
-  ME_MBAR_HIP(sums.resize(entries * sizeof(double)));
-  double *part = partials.get<double>();
-  for (int t = 0; t < n_temps; ++t)
-    for (int j0 = 0; j0 < n_cols; j0 += rows) {
-      const int n_rows = std::min(rows, n_cols - j0);
-      switch (rows) {
-        case 16: launch_pass<16>(p, values, keep, h, t, j0, n_rows, part); break;
-        case 8: launch_pass<8>(p, values, keep, h, t, j0, n_rows, part); break;
-        case 4: launch_pass<4>(p, values, keep, h, t, j0, n_rows, part); break;
-        case 2: launch_pass<2>(p, values, keep, h, t, j0, n_rows, part); break;
-        default: launch_pass<1>(p, values, keep, h, t, j0, n_rows, part); break;
-      }
-      hipLaunchKernelGGL(k_mbar_hist_sum, dim3(n_cells, n_rows), dim3(kThreads), 0, p.stream, partials.get<const double>(),
-                         (const unsigned long long *)nullptr, n_blocks, rows, n_cells,
-                         sums.get<double>() + ((size_t)t * n_cols + j0) * n_cells, (long long *)nullptr);
-    }
-  ME_MBAR_HIP(hipGetLastError());
-  ME_MBAR_HIP(hipMemcpyAsync(cell_gram, sums.get(), entries * sizeof(double), hipMemcpyDeviceToHost, p.stream));
-  return hipStreamSynchronize(p.stream);
+// the Gram table of a problem whose histogram2d() left `keep`: R and its kernel from the number of cells
+SlotGramTable cell_gram_table(const Problem &p, const ValuePair &values, const HistogramScratch &keep, const Histogram2d &h,
+                              double *cell_gram) {
+  const int n_cells = (h.n_bins_x + 3) * (h.n_bins_y + 3), rows = rows_per_pass(n_cells);
+  return SlotGramTable{n_cells, rows, cell_gram, [=, &p, &keep, &h](int t, int j0, int n_rows, double *partials) {
+                         switch (rows) {
+                           case 16: launch_pass<16>(p, values, keep, h, t, j0, n_rows, partials); break;
+                           case 8: launch_pass<8>(p, values, keep, h, t, j0, n_rows, partials); break;
+                           case 4: launch_pass<4>(p, values, keep, h, t, j0, n_rows, partials); break;
+                           case 2: launch_pass<2>(p, values, keep, h, t, j0, n_rows, partials); break;
+                           default: launch_pass<1>(p, values, keep, h, t, j0, n_rows, partials); break;
+                         }
+                         return hipSuccess;
+                       }};
 }
 
 struct Histogram2dGram {
   Histogram2d h;
-  double *cell_gram, *ladder_gram, *column_counts;
-  int64_t *n_used;
+  double *cell_gram;
+  LadderGram ladder;
 };
 
 // the two forms of me_mbar_histogram_joint_gram behind their Source; the checks and their order are histogram2d_common's
 int histogram2d_gram_common(const Source &src, const ValuePair &values, const double *f, const double *temps, int n,
                             const Histogram2dGram &hg) {
-  int rc = check_histogram2d(src, f, temps, n, hg.h);
+  const int rc = check_histogram2d(src, f, temps, n, hg.h);
   if (rc) return rc;
-  long long n_used = 0;
-  {
-    Problem p;
-    HistogramScratch keep;
-    rc = mbar_check_common(src.e, p, histogram2d(p, src, values, f, temps, n, hg.h, keep));
-    if (rc) return rc;
-    if (hg.cell_gram) {
-      rc = mbar_check_common(src.e, p, cell_gram(p, values, keep, hg.h, n, hg.cell_gram));
-      if (rc) return rc;
-    }
-    n_used = p.n_used_ll;
-  }                                                                // (the problem's device scratch and d_n go before the next pass)
-  if (hg.ladder_gram || hg.column_counts) {
-    // The Gram pass with no targets (me_mbar_cov.hip), reused whole in a problem of its own, as in me_mbar_hist_cov.hip
-    Problem ladder;
-    std::vector<double> gram((size_t)src.n_rungs * src.n_rungs), column_counts((size_t)src.n_rungs);
-    rc = mbar_check_common(src.e, ladder, mbar_gram(ladder, src, f, nullptr, 0, gram.data(), column_counts.data(), nullptr, nullptr));
-    if (rc) return rc;
-    if (hg.ladder_gram) std::copy(gram.begin(), gram.end(), hg.ladder_gram);
-    if (hg.column_counts) std::copy(column_counts.begin(), column_counts.end(), hg.column_counts);
-  }
-  if (hg.n_used) *hg.n_used = n_used;
-  return ME_OK;
+  return histogram_gram_stages(
+      src, f, n, [&](Problem &p, HistogramScratch &keep) { return histogram2d(p, src, values, f, temps, n, hg.h, keep); },
+      [&](const Problem &p, const HistogramScratch &keep) { return cell_gram_table(p, values, keep, hg.h, hg.cell_gram); },
+      hg.ladder);
 }
 
 }  // namespace
@@ -195,7 +153,7 @@ int me_mbar_histogram_joint_gram(me_engine *e, const double *f, const double *te
   if (rc) return rc;
   return histogram2d_gram_common(src, values, f, temps, n,
                                  Histogram2dGram{Histogram2d{edges_x, n_bins_x, edges_y, n_bins_y, mass, counts, neff_fraction},
-                                                 cell_gram, ladder_gram, column_counts, n_used});
+                                                 cell_gram, LadderGram{ladder_gram, column_counts, n_used}});
 }
 
 int me_mbar_histogram_joint_gram_samples(int32_t device_id, const double *energies, const int32_t *rungs, int64_t n_samples,
@@ -213,8 +171,8 @@ int me_mbar_histogram_joint_gram_samples(int32_t device_id, const double *energi
   if (rc) return rc;
   return src.finish(histogram2d_gram_common(
       src, values, f, temps, n,
-      Histogram2dGram{Histogram2d{edges_x, n_bins_x, edges_y, n_bins_y, mass, counts, neff_fraction}, cell_gram, ladder_gram,
-                      column_counts, n_used}));
+      Histogram2dGram{Histogram2d{edges_x, n_bins_x, edges_y, n_bins_y, mass, counts, neff_fraction}, cell_gram,
+                      LadderGram{ladder_gram, column_counts, n_used}}));
 }
 
 }  // extern "C"

@@ -11,7 +11,13 @@
 //     H[t][j][s] = sum_{n used, slot_n = s} W_nj w_nt   (j < K),       H[t][K][s] = sum_{n used, slot_n = s} w_nt^2:
 // ladder_j x slot_s = H[t][j][s] / p_ts, state x slot_s = H[t][K][s] / p_ts, slot_s x slot_s' = delta_ss' H[t][K][s] / p_ts^2,
 // ladder_j x state = sum_s H[t][j][s], state x state = sum_s H[t][K][s]; the ladder x ladder block is mbar_gram's with no
-// targets.  The host assembles the matrix (statistics.py), at most 64 + 1 + 259 columns per temperature.
+// targets.  The host never assembles the matrix: the state and slot columns have no samples of their own, so the covariance of
+// the log masses reduces to one K x K pseudo-inverse and O(S K^2) products (statistics.py, _SlotLogCovariance, which the
+// joint unit's cells share).
+//
+// Host.  slot_gram_passes is the driver of both Gram units (this one and me_mbar_hist2d_cov.hip), as histogram_slots is of the
+// mass units, and histogram_gram_stages the body of their entry points behind the argument checks; a unit keeps its kernel, its
+// choice of R and its launch (SlotGramTable, me_mbar.h).
 //
 // Kernels.  The masses, counts, ln_z_t and d_n are those of histogram() (me_mbar_hist.hip), called first: the same code, the
 // same bits.  k_mbar_hist_cov<R> is slot_pass (me_mbar_slots.h, which describes the scheme and the summation order) with
@@ -42,13 +48,14 @@ namespace {
 // 0: the rule of rows_per_pass; 4, 8, 16: that R at every bin count (to be measured against: profiles/mbar_profile_uncertainty.txt)
 constexpr int kForcedRows = ME_HIST_COV_ROWS;
 constexpr int kMaxRows = 16;
-constexpr size_t kCuLds = 160 * 1024;           // LDS of a CU
 constexpr int kMinBlocksPerCu = 4;              // 4 wavefronts per SIMD, k_mbar_hist's own occupancy at 256 bins
 
 static_assert(slot_pass_lds(16, 64 + 3, 64 + 1, false) == 34824 && slot_pass_lds(4, 256 + 3, 256 + 1, false) == 35208,
               "the LDS of the header comment");
 
-// R of a launch: the widest of 16, 8, 4 with which kMinBlocksPerCu workgroups fit a CU's LDS (R = 4 always does).
+// R of a launch: the widest of 16, 8, 4 with which kMinBlocksPerCu workgroups fit a CU's LDS (R = 4 always does), by the EXACT
+// bytes of the n_bins + 1 edges.  The joint units' rule (joint_rule_rows, me_mbar_slots.h) bounds the edges by 2 bytes per cell
+// and would put the thresholds at 76 and 155 bins, not at the measured 75 and 152: this rule stays its own.
 // tools/bench_mbar.py (gram_rows) restates this rule to print its pass counts: change both together.
 constexpr int rule_rows(int n_bins) {
   for (int rows = kMaxRows; rows > 4; rows /= 2)
@@ -87,34 +94,20 @@ hipError_t launch_pass(const Problem &p, const ObsColumns &values, const Histogr
   return hipSuccess;
 }
 
-// slot_gram[n_temps][n_rungs + 1][n_bins + 3] (host) of a problem whose histogram() has just run: p.w.inv_temps and p.w.out
-// hold its targets, `keep` its d_n and edges.  Waits for the stream.
-hipError_t slot_gram(Problem &p, const ObsColumns &values, const HistogramScratch &keep, int n_bins, int n_temps, double *slot_gram) {
-  const int n_slots = n_bins + 3, n_blocks = blocks_of(p.sm.n_samples), n_cols = p.n_rungs + 1, rows = rows_per_pass(n_bins);
-  const size_t cells = (size_t)n_temps * n_cols * n_slots;
-  DeviceBuffer partials, sums;
-  ME_MBAR_HIP(partials.resize((size_t)n_blocks * rows * n_slots * sizeof(double)));
-  ME_MBAR_HIP(sums.resize(cells * sizeof(double)));
-  double *part = partials.get<double>();
-  for (int t = 0; t < n_temps; ++t)
-    for (int j0 = 0; j0 < n_cols; j0 += rows) {
-      const int n_rows = std::min(rows, n_cols - j0);
-      ME_MBAR_HIP(rows == 16  ? launch_pass<16>(p, values, keep, n_bins, t, j0, n_rows, part)
-                  : rows == 8 ? launch_pass<8>(p, values, keep, n_bins, t, j0, n_rows, part)
-                              : launch_pass<4>(p, values, keep, n_bins, t, j0, n_rows, part));
-      hipLaunchKernelGGL(k_mbar_hist_sum, dim3(n_slots, n_rows), dim3(kThreads), 0, p.stream, partials.get<const double>(),
-                         (const unsigned long long *)nullptr, n_blocks, rows, n_slots,
-                         sums.get<double>() + ((size_t)t * n_cols + j0) * n_slots, (long long *)nullptr);
-    }
-  ME_MBAR_HIP(hipGetLastError());
-  ME_MBAR_HIP(hipMemcpyAsync(slot_gram, sums.get(), cells * sizeof(double), hipMemcpyDeviceToHost, p.stream));
-  return hipStreamSynchronize(p.stream);
+// the Gram table of a problem whose histogram() left `keep`: R and its kernel from the bin count
+SlotGramTable slot_gram_table(const Problem &p, const ObsColumns &values, const HistogramScratch &keep, int n_bins, double *slot_gram) {
+  const int rows = rows_per_pass(n_bins);
+  return SlotGramTable{n_bins + 3, rows, slot_gram, [=, &p, &keep](int t, int j0, int n_rows, double *partials) {
+                         return rows == 16  ? launch_pass<16>(p, values, keep, n_bins, t, j0, n_rows, partials)
+                                : rows == 8 ? launch_pass<8>(p, values, keep, n_bins, t, j0, n_rows, partials)
+                                            : launch_pass<4>(p, values, keep, n_bins, t, j0, n_rows, partials);
+                       }};
 }
 
 struct HistogramGram {
   Histogram h;
-  double *slot_gram, *ladder_gram, *column_counts;
-  int64_t *n_used;
+  double *slot_gram;
+  LadderGram ladder;
 };
 
 // the two forms of me_mbar_histogram_gram behind their Source; the checks and their order are histogram_common's
@@ -124,33 +117,65 @@ int histogram_gram_common(const Source &src, const ObsColumns &values, const dou
   if (rc) return rc;
   rc = check_f_and_targets(src.e, f, src.n_rungs, temps, n, 1);
   if (rc) return rc;
+  return histogram_gram_stages(
+      src, f, n, [&](Problem &p, HistogramScratch &keep) { return histogram(p, src, values, f, temps, n, hg.h, keep); },
+      [&](const Problem &p, const HistogramScratch &keep) { return slot_gram_table(p, values, keep, hg.h.n_bins, hg.slot_gram); },
+      hg.ladder);
+}
+
+}  // namespace
+
+hipError_t slot_gram_passes(Problem &p, const SlotGramTable &table, int n_temps) {
+  const int n_slots = table.n_slots, rows = table.rows, n_blocks = blocks_of(p.sm.n_samples), n_cols = p.n_rungs + 1;
+  const size_t entries = (size_t)n_temps * n_cols * n_slots;
+  DeviceBuffer partials, sums;
+  ME_MBAR_HIP(partials.resize((size_t)n_blocks * rows * n_slots * sizeof(double)));
+  ME_MBAR_HIP(sums.resize(entries * sizeof(double)));
+  for (int t = 0; t < n_temps; ++t)
+    for (int j0 = 0; j0 < n_cols; j0 += rows) {
+      const int n_rows = std::min(rows, n_cols - j0);
+      ME_MBAR_HIP(table.launch(t, j0, n_rows, partials.get<double>()));
+      hipLaunchKernelGGL(k_mbar_hist_sum, dim3(n_slots, n_rows), dim3(kThreads), 0, p.stream, partials.get<const double>(),
+                         (const unsigned long long *)nullptr, n_blocks, rows, n_slots,
+                         sums.get<double>() + ((size_t)t * n_cols + j0) * n_slots, (long long *)nullptr);
+    }
+  ME_MBAR_HIP(hipGetLastError());
+  ME_MBAR_HIP(hipMemcpyAsync(table.gram, sums.get(), entries * sizeof(double), hipMemcpyDeviceToHost, p.stream));
+  return hipStreamSynchronize(p.stream);
+}
+
+int histogram_gram_stages(const Source &src, const double *f, int n_temps,
+                          const std::function<hipError_t(Problem &, HistogramScratch &)> &histogram,
+                          const std::function<SlotGramTable(const Problem &, const HistogramScratch &)> &gram_table,
+                          const LadderGram &out) {
+  int rc;
   long long n_used = 0;
   {
     Problem p;
     HistogramScratch keep;
-    rc = mbar_check_common(src.e, p, histogram(p, src, values, f, temps, n, hg.h, keep));
+    rc = mbar_check_common(src.e, p, histogram(p, keep));
     if (rc) return rc;
-    if (hg.slot_gram) {
-      rc = mbar_check_common(src.e, p, slot_gram(p, values, keep, hg.h.n_bins, n, hg.slot_gram));
+    const SlotGramTable table = gram_table(p, keep);
+    if (table.gram) {
+      rc = mbar_check_common(src.e, p, slot_gram_passes(p, table, n_temps));
       if (rc) return rc;
     }
     n_used = p.n_used_ll;
   }                                                                // (the problem's device scratch and d_n go before the next pass)
-  if (hg.ladder_gram || hg.column_counts) {
+  if (out.ladder_gram || out.column_counts) {
     // The Gram pass with no targets (me_mbar_cov.hip), reused whole: it prepares a problem of its own (a second counting pass
     // over the samples) because it packs the used samples before anything else.
     Problem ladder;
     std::vector<double> gram((size_t)src.n_rungs * src.n_rungs), column_counts((size_t)src.n_rungs);
     rc = mbar_check_common(src.e, ladder, mbar_gram(ladder, src, f, nullptr, 0, gram.data(), column_counts.data(), nullptr, nullptr));
     if (rc) return rc;
-    if (hg.ladder_gram) std::copy(gram.begin(), gram.end(), hg.ladder_gram);
-    if (hg.column_counts) std::copy(column_counts.begin(), column_counts.end(), hg.column_counts);
+    if (out.ladder_gram) std::copy(gram.begin(), gram.end(), out.ladder_gram);
+    if (out.column_counts) std::copy(column_counts.begin(), column_counts.end(), out.column_counts);
   }
-  if (hg.n_used) *hg.n_used = n_used;
+  if (out.n_used) *out.n_used = n_used;
   return ME_OK;
 }
 
-}  // namespace
 }  // namespace mbar
 }  // namespace me
 
@@ -169,8 +194,8 @@ int me_mbar_histogram_gram(me_engine *e, const double *f, const double *temps, i
   rc = histogram_column(src, column, values);
   if (rc) return rc;
   return histogram_gram_common(src, values, f, temps, n,
-                               HistogramGram{Histogram{edges, n_bins, mass, counts, neff_fraction}, slot_gram, ladder_gram,
-                                             column_counts, n_used});
+                               HistogramGram{Histogram{edges, n_bins, mass, counts, neff_fraction}, slot_gram,
+                                             LadderGram{ladder_gram, column_counts, n_used}});
 }
 
 int me_mbar_histogram_gram_samples(int32_t device_id, const double *energies, const int32_t *rungs, int64_t n_samples,
@@ -183,7 +208,7 @@ int me_mbar_histogram_gram_samples(int32_t device_id, const double *energies, co
   return rc ? rc
             : src.finish(histogram_gram_common(src, src.columns, f, temps, n,
                                                HistogramGram{Histogram{edges, n_bins, mass, counts, neff_fraction}, slot_gram,
-                                                             ladder_gram, column_counts, n_used}));
+                                                             LadderGram{ladder_gram, column_counts, n_used}}));
 }
 
 }  // extern "C"

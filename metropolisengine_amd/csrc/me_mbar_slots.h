@@ -212,6 +212,28 @@ constexpr size_t slot_pass_lds(int rows, int n_slots, int n_edges, bool counts) 
   return (size_t)n_edges * sizeof(double) + (size_t)kWaves * n_slots * (rows * sizeof(double) + (counts ? sizeof(unsigned int) : 0));
 }
 
+// ---- the rows per pass of the two joint units (host), from the number of cells S ALONE, so that a cell's sums do not depend
+// on the two bin counts behind S.  joint_lds_bound: the most LDS a workgroup needs for S cells at R rows, whatever the bin
+// counts: the tables and at most 2 S bytes of edges (one axis of a single bin).  joint_cells_at: the most cells with which
+// blocks_per_cu workgroups of R rows fit a CU's LDS.  joint_rule_rows: the widest R of `widest`, widest / 2, ..., 1 that allows
+// n_cells.  joint_rows_per_pass: `forced` (a unit's forcing macro; 0: none) wherever its table fits 64 KiB, otherwise the rule.
+constexpr size_t kCuLds = 160 * 1024;           // LDS of a CU
+constexpr size_t joint_lds_bound(int rows, int n_cells, bool counts) {
+  return slot_pass_lds(rows, n_cells, 0, counts) + 2 * (size_t)n_cells;
+}
+constexpr int joint_cells_at(int rows, bool counts, int blocks_per_cu) {
+  return (int)(kCuLds / blocks_per_cu / joint_lds_bound(rows, 1, counts));
+}
+constexpr int joint_rule_rows(int n_cells, int widest, bool counts, int blocks_per_cu) {
+  for (int rows = widest; rows > 1; rows /= 2)
+    if (n_cells <= joint_cells_at(rows, counts, blocks_per_cu)) return rows;
+  return 1;
+}
+constexpr int joint_rows_per_pass(int n_cells, int widest, bool counts, int blocks_per_cu, int forced) {
+  return forced && joint_lds_bound(forced, n_cells, counts) <= 64 * 1024 ? forced
+                                                                          : joint_rule_rows(n_cells, widest, counts, blocks_per_cu);
+}
+
 // The body of a pass kernel (the header; LDS: slot_pass_lds).  Sample i = record * n_chains + chain has its values at offset
 // record * record_stride + chain of the value columns (a column of the engine's store: n_chains, Q n_chains; a host array or
 // the energies themselves: n, 0); `d` is padded to whole tiles.  kCounts: the unit keeps integer counts, and a pass with

@@ -654,52 +654,122 @@ def mbar_observable_uncertainties(energies, rungs, temps, f, targets, observable
                                      tuple(range(a.shape[0])), g)
 
 
-def _profile_uncertainty_result(temps, edges, mass, counts, neff, slot_gram, ladder_gram, column_counts, n_used, inefficiency):
-    """The dictionary of :func:`mbar_free_energy_profile_uncertainties` from what ``me_mbar_histogram_gram`` returns.  One
-    matrix per temperature over the columns [K ladder | state | one per resolved slot], assembled from the slot Gram sums (the
-    slot columns are disjoint; include/metropolis_engine.h has the blocks), one ``mbar_theta`` each.  With ``a`` the state
-    column, ``Cov(ln p_s, ln p_s') = Theta_ss' + Theta_aa - Theta_sa - Theta_s'a``.
+def _ladder_response(ladder_gram, column_counts):
+    """``M = N^{1/2} (I - N^{1/2} G_KK N^{1/2})^+ N^{1/2}`` (K x K; the pseudo-inverse cut at ``rcond = 1e-10`` as in
+    :func:`mbar_theta`): what is left of MBAR's asymptotic covariance for columns of the weight matrix that have no samples of
+    their own.  For two such columns ``a``, ``b`` with Gram entries ``G_ab`` and ``G_Ka``, ``G_Kb`` against the ladder,
+    ``Theta_ab = G_ab + G_Ka^T M G_Kb``."""
+    root = np.sqrt(np.asarray(column_counts, dtype=np.float64))
+    g = np.asarray(ladder_gram, dtype=np.float64)
+    inner = np.eye(root.size) - root[:, None] * g * root[None, :]
+    return root[:, None] * np.linalg.pinv(inner, rcond=1e-10) * root[None, :]
 
-    A slot is RESOLVED, and has a column, when ``H[K][s]``, the sum of its squared weights, is a normal float64 (at least
-    2.2e-308).  Below that the device's sum has lost its digits or is 0 -- the weights themselves are below 1.5e-154, which a cold
-    target reaches in a bin that only the hot rungs populate -- and ``H[K][s] / p_s^2`` would be 0 / 0.  Rescaling the column
-    cannot help, the sum is gone before the host sees it; the slot is left out and the others keep their results.  For a
-    resolved slot ``p_s^2 >= H[K][s]`` (the weights are >= 0), so neither division below can underflow."""
-    out = _profile_result(temps, edges, mass, counts, neff)
-    k, b, nt = ladder_gram.shape[0], edges.size - 1, temps.size
-    d_slot = np.zeros((nt, b + 3))
-    d_free, d_lowest = np.full((nt, b), np.nan), np.full((nt, b), np.nan)
-    log_cov = np.full((nt, b, b), np.nan)
-    lowest = np.zeros(nt, dtype=np.int64)
-    for t in range(nt):
-        p, h = mass[t], slot_gram[t]
+
+class _SlotLogCovariance:
+    """The asymptotic covariance of the log masses of ONE temperature's slots (the bins of a profile with their three outer
+    slots, the cells of a surface), from the slot Gram sums ``H`` ``(K + 1, S)``, the masses ``p`` ``(S,)`` and ``M`` of
+    :func:`_ladder_response`.  The ``(K + 1 + S)``-column Gram matrix [ladder | state | one indicator column per slot] is NOT
+    assembled: the state and slot columns have no samples of their own and the slot columns are disjoint, so with
+        ``u_c = H[:K, c] / p_c - sum_c' H[:K, c']``,   ``h_c = H[K][c] / p_c``,
+    ``Cov(ln p_c, ln p_c') = delta_cc' H[K][c] / p_c^2 - h_c - h_c' + sum_c'' H[K][c''] + u_c^T M u_c'``.  (``N^{1/2} u_c`` is
+    orthogonal to the null vector ``N^{1/2} 1`` of the bracket because ``sum_j N_j W_nj = 1``: the cut of the pseudo-inverse does
+    not enter.)  Every variance is multiplied by ``inefficiency``.
+
+    A slot is RESOLVED, and in ``live`` (ascending slot indices; everything else here is indexed by position in ``live``), when
+    ``H[K][s]``, the sum of its squared weights, is a normal float64 (at least 2.2e-308).  Below that the device's sum has lost
+    its digits or is 0 -- the weights themselves are below 1.5e-154, which a cold target reaches in a slot that only the hot
+    rungs populate -- and ``H[K][s] / p_s^2`` would be 0 / 0.  Rescaling cannot help, the sum is gone before the host sees it;
+    the slot is left out (``unresolved`` when it has a mass all the same) and the others keep their results.  For a resolved
+    slot ``p_s^2 >= H[K][s]`` (the weights are >= 0), so no division here can underflow.
+
+    ``var`` is ``Var ln p_c`` of the live slots, O(S K^2) work like everything but :meth:`covariance`."""
+
+    def __init__(self, h, p, response, inefficiency):
+        k = response.shape[0]
         resolved = h[k] >= np.finfo(np.float64).tiny
-        d_slot[t, (p > 0) & ~resolved] = np.nan          # (a mass, but no error bar; an empty slot keeps 0)
-        live = np.flatnonzero(resolved)
-        c = k + 1 + live.size
-        gram = np.zeros((c, c))
-        gram[:k, :k] = ladder_gram
-        gram[:k, k] = gram[k, :k] = h[:k].sum(axis=1)
-        gram[k, k] = h[k].sum()
-        gram[:k + 1, k + 1:] = h[:, live] / p[live][None, :]
-        gram[k + 1:, :k + 1] = gram[:k + 1, k + 1:].T
-        gram[k + 1 + np.arange(live.size), k + 1 + np.arange(live.size)] = h[k, live] / p[live] ** 2
-        theta = mbar_theta(gram, np.concatenate([column_counts, np.zeros(1 + live.size)]))
-        slots, to_state = theta[k + 1:, k + 1:], theta[k + 1:, k]
-        cov = (slots + theta[k, k] - to_state[:, None] - to_state[None, :]) * inefficiency
-        d_slot[t, live] = p[live] * np.sqrt(np.clip(np.diag(cov), 0.0, None))
-        bins = live < b                                  # (live is ascending: the bins come first)
-        own = live[bins]
+        self.unresolved = (p > 0) & ~resolved
+        self.live = np.flatnonzero(resolved)
+        self.response, self.inefficiency = response, inefficiency
+        self.p = p[self.live]
+        self.u = h[:k, self.live] / self.p[None, :] - h[:k].sum(axis=1)[:, None]
+        self.own_sums = h[k, self.live]
+        self.to_state = self.own_sums / self.p
+        self.own_term = self.own_sums / self.p ** 2
+        self.state = h[k].sum()
+        self.mu = response @ self.u
+        self.var = (self.own_term - 2.0 * self.to_state + self.state + np.einsum("kc,kc->c", self.u, self.mu)) * inefficiency
+
+    def covariance(self, sel):
+        """``Cov(ln p_c, ln p_c')`` over the live slots that the mask ``sel`` picks: the only matrix over slots."""
+        n = int(np.count_nonzero(sel))
+        cov = self.u[:, sel].T @ self.mu[:, sel] - self.to_state[sel][:, None] - self.to_state[sel][None, :] + self.state
+        cov[np.arange(n), np.arange(n)] += self.own_term[sel]
+        return cov * self.inefficiency
+
+    def var_from(self, sel, at):
+        """``Var(ln p_c - ln p_at)`` of the live slots that ``sel`` picks against live slot ``at`` (the common terms cancel)."""
+        du = self.u[:, sel] - self.u[:, at][:, None]
+        return (self.own_term[sel] + self.own_term[at] + np.einsum("kc,kc->c", du, self.response @ du)) * self.inefficiency
+
+    def var_of_sum(self, sel):
+        """``Var sum_c p_c = sum_cc' p_c p_c' C_cc'`` over the live slots that ``sel`` picks."""
+        po = self.p[sel]
+        v = self.u[:, sel] @ po
+        own_sum, total = self.own_sums[sel].sum(), po.sum()
+        return (own_sum - 2.0 * total * own_sum + total * total * self.state + v @ (self.response @ v)) * self.inefficiency
+
+
+def _slot_uncertainties(temps, mass, density, slot_gram, inner, ladder_gram, column_counts, inefficiency, covariance):
+    """The error bars that a profile and a surface share, one :class:`_SlotLogCovariance` per temperature.  ``mass`` ``(T, S)``
+    and ``slot_gram`` ``(T, K + 1, S)`` over all slots; ``inner`` ``(S,)``: which of them are the ``I`` bins (cells) proper, in
+    whose order ``density`` ``(T, I)`` is.  Returns ``d_slots`` ``(T, S)``: ``p sqrt(Var ln p)``, 0 for an empty slot and NaN for an
+    unresolved one; ``d_free`` ``(T, I)``: ``T sqrt(Var ln p)``, NaN for a slot that is not live; ``lowest`` ``(T,)``: the inner slot
+    of largest density; ``d_lowest`` ``(T, I)``: ``T sqrt(Var(ln p - ln p_lowest))``, 0 at ``lowest`` and all NaN when ``lowest`` itself
+    is not live; ``d_outside`` ``(T,)``: the standard error of the summed masses of the live slots outside ``inner``; ``log_cov``
+    ``(T, I, I)``, NaN in the rows and columns of slots that are not live (``None`` without ``covariance``)."""
+    nt, n_slots, n_inner = temps.size, inner.size, int(inner.sum())
+    to_inner = np.full(n_slots, -1, dtype=np.intp)       # position among the inner slots (-1 outside)
+    to_inner[inner] = np.arange(n_inner)
+    d_slots, d_outside = np.zeros((nt, n_slots)), np.zeros(nt)
+    d_free, d_lowest = np.full((nt, n_inner), np.nan), np.full((nt, n_inner), np.nan)
+    lowest = np.zeros(nt, dtype=np.int64)
+    log_cov = np.full((nt, n_inner, n_inner), np.nan) if covariance else None
+    response = _ladder_response(ladder_gram, column_counts)
+    for t in range(nt):
+        c = _SlotLogCovariance(slot_gram[t], mass[t], response, inefficiency)
+        d_slots[t, c.unresolved] = np.nan                # (a mass, but no error bar; an empty slot keeps 0)
+        root = np.sqrt(np.clip(c.var, 0.0, None))
+        d_slots[t, c.live] = c.p * root
+        out_live = ~inner[c.live]
+        if out_live.any():
+            d_outside[t] = np.sqrt(max(c.var_of_sum(out_live), 0.0))
+        bins = inner[c.live]
+        own = to_inner[c.live[bins]]
         if own.size == 0:
             continue
-        d_free[t, own] = temps[t] * np.sqrt(np.clip(np.diag(cov)[bins], 0.0, None))
-        log_cov[np.ix_([t], own, own)] = cov[np.ix_(bins, bins)]
-        lowest[t] = int(np.argmax(out["density"][t]))
-        at = int(np.searchsorted(own, lowest[t]))
-        block = slots[np.ix_(bins, bins)]
-        diff = (np.diag(block) + block[at, at] - 2.0 * block[:, at]) * inefficiency
-        d_lowest[t, own] = temps[t] * np.sqrt(np.clip(diff, 0.0, None))
-        d_lowest[t, lowest[t]] = 0.0
+        d_free[t, own] = temps[t] * root[bins]
+        lowest[t] = int(np.argmax(density[t]))
+        at = np.flatnonzero(own == lowest[t])
+        if at.size:
+            at = int(np.flatnonzero(bins)[at[0]])
+            d_lowest[t, own] = temps[t] * np.sqrt(np.clip(c.var_from(bins, at), 0.0, None))
+            d_lowest[t, lowest[t]] = 0.0
+        if covariance:
+            if own.size == n_inner:                      # (every inner slot live: own is 0 .. I - 1 in order)
+                log_cov[t] = c.covariance(bins)
+            else:
+                log_cov[t][np.ix_(own, own)] = c.covariance(bins)
+    return d_slots, d_free, lowest, d_lowest, d_outside, log_cov
+
+
+def _profile_uncertainty_result(temps, edges, mass, counts, neff, slot_gram, ladder_gram, column_counts, n_used, inefficiency):
+    """The dictionary of :func:`mbar_free_energy_profile_uncertainties` from what ``me_mbar_histogram_gram`` returns:
+    :func:`_slot_uncertainties` over the ``B + 3`` slots, of which the ``B`` bins are the inner ones."""
+    out = _profile_result(temps, edges, mass, counts, neff)
+    b = edges.size - 1
+    inner = np.arange(b + 3) < b
+    d_slot, d_free, lowest, d_lowest, _, log_cov = _slot_uncertainties(temps, mass, out["density"], slot_gram, inner, ladder_gram,
+                                                                       column_counts, inefficiency, True)
     out.update({"d_mass": d_slot[:, :b].copy(), "d_below": d_slot[:, b].copy(), "d_above": d_slot[:, b + 1].copy(),
                 "d_not_a_number": d_slot[:, b + 2].copy(), "d_free_energy": d_free, "log_mass_cov": log_cov,
                 "d_free_energy_from_lowest": d_lowest, "lowest": lowest, "n_samples": int(n_used)})
@@ -732,8 +802,9 @@ def mbar_free_energy_profile_uncertainties(energies, rungs, temps, f, targets, v
     (``me_mbar_histogram_gram_samples``; the engine form is ``MetropolisEngine.free_energy_profile_uncertainties``).  The bin
     indicators are columns of the MBAR weight matrix like any observable (Shirts & Chodera 2008, eqs. 8, D8), but DISJOINT ones:
     the Gram matrix of [ladder | state | one column per slot] follows from ``K + 1`` weighted histograms per temperature
-    (csrc/me_mbar_hist_cov.hip), so any number of bins up to 256 costs no ``N x (K + 1 + B)`` matrix; the algebra, one matrix of at
-    most 64 + 1 + 259 columns per temperature, runs here in float64.
+    (csrc/me_mbar_hist_cov.hip), so any number of bins up to 256 costs no ``N x (K + 1 + B)`` matrix; and because those columns
+    have no samples of their own the algebra reduces to ONE ``K x K`` pseudo-inverse per call and O(B K^2) products per
+    temperature, in float64 here, the route :func:`mbar_free_energy_surface_uncertainties` takes for its cells.
 
     Returns every key of :func:`mbar_free_energy_profile`, bit for bit, and ``d_mass`` ``(T, B)``, ``d_below``, ``d_above``,
     ``d_not_a_number`` ``(T,)``: the standard errors ``p sqrt(Var ln p)`` of the masses; ``d_free_energy`` ``(T, B)``: ``T
@@ -747,7 +818,8 @@ def mbar_free_energy_profile_uncertainties(energies, rungs, temps, f, targets, v
     ``counts``: at a cold target the weights of a bin that only hot rungs populate can all underflow.  The same holds, with
     ``d_mass`` NaN as well, for a slot whose mass is positive but below about 1.5e-154: the sum of its squared weights is no
     normal float64 any more and no error bar can be formed, although ``free_energy`` is still finite there.  Every other slot and
-    temperature keeps its results.
+    temperature keeps its results, except that ``d_free_energy_from_lowest`` is NaN throughout a temperature whose ``lowest``
+    bin is itself such a slot: there is nothing to take the differences from.
 
     The formula assumes INDEPENDENT samples: pass the statistical inefficiency of the series as ``inefficiency`` (a finite
     scalar ``>= 1``, ``ValueError`` otherwise) and every variance is multiplied by it."""
@@ -771,94 +843,22 @@ def validate_surface_covariance(covariance):
     return bool(covariance)
 
 
-def _ladder_response(ladder_gram, column_counts):
-    """``M = N^{1/2} (I - N^{1/2} G_KK N^{1/2})^+ N^{1/2}`` (K x K; the pseudo-inverse cut at ``rcond = 1e-10`` as in
-    :func:`mbar_theta`): what is left of MBAR's asymptotic covariance for columns of the weight matrix that have no samples of
-    their own.  For two such columns ``a``, ``b`` with Gram entries ``G_ab`` and ``G_Ka``, ``G_Kb`` against the ladder,
-    ``Theta_ab = G_ab + G_Ka^T M G_Kb``."""
-    root = np.sqrt(np.asarray(column_counts, dtype=np.float64))
-    g = np.asarray(ladder_gram, dtype=np.float64)
-    inner = np.eye(root.size) - root[:, None] * g * root[None, :]
-    return root[:, None] * np.linalg.pinv(inner, rcond=1e-10) * root[None, :]
-
-
 def _surface_uncertainty_result(temps, edges_x, edges_y, mass, counts, neff, cell_gram, ladder_gram, column_counts, n_used,
                                 inefficiency, covariance):
     """The dictionary of :func:`mbar_free_energy_surface_uncertainties` from what ``me_mbar_histogram_joint_gram`` returns
-    (``mass`` ``(T, Bx + 3, By + 3)``, ``cell_gram`` ``(T, K + 1, S)``).  The ``(K + 1 + S)``-column Gram matrix of
-    :func:`_profile_uncertainty_result` is NOT assembled: the state and cell columns have no samples of their own, so with ``M``
-    of :func:`_ladder_response`, ``H = cell_gram[t]``, ``p`` the masses and
-        ``u_c = H[:K, c] / p_c - sum_c' H[:K, c']``,   ``h_c = H[K][c] / p_c``,
-    ``Cov(ln p_c, ln p_c') = delta_cc' H[K][c] / p_c^2 - h_c - h_c' + sum_c'' H[K][c''] + u_c^T M u_c'``.  (``N^{1/2} u_c`` is
-    orthogonal to the null vector ``N^{1/2} 1`` of the bracket because ``sum_j N_j W_nj = 1``: the cut of the pseudo-inverse does
-    not enter.)  The diagonal, the differences from the lowest cell and the variance of a sum of masses need ``u``, ``h`` and
-    ``M u`` only, O(S K^2) work; the ``L x L`` matrix over the live inner cells is formed with ``covariance`` alone.  The rules
-    for empty and unresolved cells are :func:`_profile_uncertainty_result`'s."""
+    (``mass`` ``(T, Bx + 3, By + 3)``, ``cell_gram`` ``(T, K + 1, S)``): :func:`_slot_uncertainties` over the ``S`` cells in
+    their flat order ``slot_x (By + 3) + slot_y``, of which the ``Bx By`` cells of the inner grid are the inner ones.  The ``L x L``
+    matrix over the live inner cells (9.5 MB per temperature at 33 x 33 bins) is formed with ``covariance`` alone."""
     out = _surface_result(temps, edges_x, edges_y, mass, counts, neff)
-    k, nt = ladder_gram.shape[0], temps.size
-    bx, by = edges_x.size - 1, edges_y.size - 1
-    n_cells = (bx + 3) * (by + 3)
+    nt, bx, by = temps.size, edges_x.size - 1, edges_y.size - 1
     inner = np.zeros((bx + 3, by + 3), dtype=bool)
     inner[:bx, :by] = True
-    inner = inner.ravel()
-    # flat index bx_ * by + by_ of the inner grid for every cell of the full table (-1 outside)
-    to_inner = np.full(n_cells, -1, dtype=np.intp)
-    to_inner[inner] = np.arange(bx * by)
-    d_cell = np.zeros((nt, n_cells))
-    d_free, d_lowest = np.full((nt, bx * by), np.nan), np.full((nt, bx * by), np.nan)
-    d_outside = np.zeros(nt)
-    lowest = np.zeros((nt, 2), dtype=np.int64)
-    log_cov = np.full((nt, bx * by, bx * by), np.nan) if covariance else None      # (9.5 MB per temperature at 33 x 33 bins)
-    response = _ladder_response(ladder_gram, column_counts)
-    for t in range(nt):
-        p, h = mass[t].ravel(), cell_gram[t]
-        resolved = h[k] >= np.finfo(np.float64).tiny
-        d_cell[t, (p > 0) & ~resolved] = np.nan          # (a mass, but no error bar; an empty cell keeps 0)
-        live = np.flatnonzero(resolved)
-        if live.size == 0:
-            continue
-        pl = p[live]
-        u = h[:k, live] / pl[None, :] - h[:k].sum(axis=1)[:, None]
-        to_state = h[k, live] / pl
-        own_term = h[k, live] / pl ** 2
-        state = h[k].sum()
-        mu = response @ u
-        var = (own_term - 2.0 * to_state + state + np.einsum("kc,kc->c", u, mu)) * inefficiency
-        root = np.sqrt(np.clip(var, 0.0, None))
-        d_cell[t, live] = pl * root
-        # Var sum_c p_c over the live cells outside the inner grid = sum_cc' p_c p_c' C_cc'
-        out_live = ~inner[live]
-        if out_live.any():
-            po = pl[out_live]
-            v = u[:, out_live] @ po
-            own_sum, total = h[k, live][out_live].sum(), po.sum()
-            var_out = own_sum - 2.0 * total * own_sum + total * total * state + v @ (response @ v)
-            d_outside[t] = np.sqrt(max(var_out * inefficiency, 0.0))
-        bins = inner[live]
-        own = to_inner[live[bins]]
-        if own.size == 0:
-            continue
-        d_free[t, own] = temps[t] * root[bins]
-        lowest[t] = np.unravel_index(int(np.argmax(out["density"][t])), (bx, by))
-        low = int(lowest[t, 0]) * by + int(lowest[t, 1])
-        at = np.flatnonzero(own == low)
-        if at.size:
-            at = int(np.flatnonzero(bins)[at[0]])
-            du = u[:, bins] - u[:, at][:, None]
-            diff = (own_term[bins] + own_term[at] + np.einsum("kc,kc->c", du, response @ du)) * inefficiency
-            d_lowest[t, own] = temps[t] * np.sqrt(np.clip(diff, 0.0, None))
-            d_lowest[t, low] = 0.0
-        if covariance:
-            ub = u[:, bins]
-            cov = ub.T @ mu[:, bins] - to_state[bins][:, None] - to_state[bins][None, :] + state
-            cov[np.arange(own.size), np.arange(own.size)] += own_term[bins]
-            if own.size == bx * by:                      # (every inner cell live: own is 0 .. Bx By - 1 in order)
-                log_cov[t] = cov * inefficiency
-            else:
-                log_cov[t][np.ix_(own, own)] = cov * inefficiency
+    d_cell, d_free, low, d_lowest, d_outside, log_cov = _slot_uncertainties(
+        temps, mass.reshape(nt, -1), out["density"].reshape(nt, -1), cell_gram, inner.ravel(), ladder_gram, column_counts,
+        inefficiency, covariance)
     d_slots = d_cell.reshape(nt, bx + 3, by + 3)
     out.update({"d_mass": d_slots[:, :bx, :by].copy(), "d_mass_slots": d_slots, "d_outside": d_outside,
-                "d_free_energy": d_free.reshape(nt, bx, by), "lowest": lowest,
+                "d_free_energy": d_free.reshape(nt, bx, by), "lowest": np.stack(np.unravel_index(low, (bx, by)), axis=1),
                 "d_free_energy_from_lowest": d_lowest.reshape(nt, bx, by), "n_samples": int(n_used)})
     if covariance:
         out["log_mass_cov"] = log_cov

@@ -141,10 +141,11 @@ def test_joint_matrix_against_the_single_bin_matrix():
 
 
 # ------------------------------------------------------------------------------- the host algebra of statistics.py
-@pytest.mark.parametrize("k,bins", [(8, "uneven"), (8, "fine")])
+@pytest.mark.parametrize("k,bins", ref.ASSEMBLY_CASES)
 def test_host_algebra_against_the_reference(k, bins):
-    """statistics._profile_uncertainty_result on the long-double sums (rounded to float64) against ref.derived on the SVD
-    route: variances within 4 b max |Theta|, b = ref.route_bound; the conventions for empty slots; inefficiency = 4 doubles
+    """statistics._profile_uncertainty_result (the reduced algebra: one K x K pseudo-inverse, the largest at K = 64) on the
+    long-double sums (rounded to float64) against ref.derived on the SVD route of the explicit (K + 1 + live)-column weight
+    matrix: variances within 4 b max |Theta|, b = ref.route_bound; the conventions for empty slots; inefficiency = 4 doubles
     every d_* exactly; the keys of free_energy_profile come through unchanged."""
     case = _case(k, bins)
     edges, targets = case["edges"], case["targets"]
@@ -235,6 +236,73 @@ def test_masses_whose_squared_weights_underflow_lose_their_error_bars_and_nothin
     for key in ("d_below", "d_above", "d_not_a_number", "lowest"):
         assert np.array_equal(out[key], want[key]), key
     assert np.array_equal(out["log_mass_cov"][0][np.ix_(kept, kept)], want["log_mass_cov"][0][np.ix_(kept, kept)])
+
+
+def test_an_unresolved_lowest_bin_leaves_the_differences_from_it_undefined():
+    """The bin of largest density with a mass but no sum of squared weights (it cannot happen to a bin that dominates, so it is
+    forced here): there is nothing to take F_b - F_lowest from, and d_free_energy_from_lowest is NaN for that temperature, as on
+    a surface, instead of silently referring to a neighbouring bin.  lowest still names the bin; every other key is what the
+    same input gives with the bin emptied, bit for bit, as for any unresolved bin."""
+    args = _scaled_slots({})
+    mass, h = args[2], args[5].copy()
+    low = int(np.argmax(mass[0, :4] / np.diff(args[1])))
+    h[0, :3, low], h[0, 3, low] = 1e-175, 0.0
+    out = statistics._profile_uncertainty_result(*args[:5], h, *args[6:], 1.0)
+    assert out["lowest"][0] == low and np.all(np.isnan(out["d_free_energy_from_lowest"][0]))
+    assert np.isnan(out["d_mass"][0][low]) and np.isnan(out["d_free_energy"][0][low]) and np.isfinite(out["free_energy"][0][low])
+    emptied_mass, emptied_h = mass.copy(), h.copy()
+    emptied_mass[0, low] = 0.0
+    emptied_h[0, :, low] = 0.0
+    want = statistics._profile_uncertainty_result(args[0], args[1], emptied_mass, args[3], args[4], emptied_h, *args[6:], 1.0)
+    kept = np.arange(4) != low
+    assert want["lowest"][0] != low and np.all(np.isfinite(want["d_free_energy_from_lowest"][0][kept]))
+    for key in ("d_mass", "d_free_energy"):
+        assert np.all(np.isfinite(out[key][0][kept])) and np.array_equal(out[key][0][kept], want[key][0][kept]), key
+    for key in ("d_below", "d_above", "d_not_a_number"):
+        assert np.array_equal(out[key], want[key]), key
+    assert np.array_equal(np.isnan(out["log_mass_cov"][0]), ~kept[:, None] | ~kept[None, :])
+    assert np.array_equal(out["log_mass_cov"][0][np.ix_(kept, kept)], want["log_mass_cov"][0][np.ix_(kept, kept)])
+
+
+@pytest.mark.parametrize("k,bins", [(8, "uneven"), (8, "fine")])
+def test_a_profile_is_the_surface_of_a_single_y_bin(k, bins):
+    """The B + 3 slots of a profile embedded in the (B + 3) x 4 cells of a grid whose one y bin encloses every value: the same
+    slot sums and masses at cell (slot_x, 0), zeros elsewhere.  statistics._surface_uncertainty_result on them against
+    statistics._profile_uncertainty_result: the NaN and zero patterns and lowest exactly; Var ln p, Cov(ln p, ln p') and
+    Var(ln p - ln p_lowest) within 4 b max |Theta|, b = ref.route_bound of the explicit 1-D weight matrix (the bound of
+    test_a_single_y_bin_is_the_one_dimensional_unit_bit_for_bit on the device).  Both are layers over one algebra and differ in
+    the order of their sums over the slots alone: the difference printed is a few units in the last place."""
+    case = _case(k, bins)
+    edges, targets = case["edges"], case["targets"]
+    b = edges.size - 1
+    f64 = lambda a: np.asarray(a, dtype=np.float64)     # noqa: E731
+    mass, h = f64(case["mass"]), f64(case["h"])
+    mass2, counts2, h2 = np.zeros((1, b + 3, 4)), np.zeros((b + 3, 4), dtype=np.int64), np.zeros((1, k + 1, b + 3, 4))
+    mass2[:, :, 0], counts2[:, 0], h2[:, :, :, 0] = mass, case["counts"], h
+    tail = (f64(case["ladder"]), f64(case["ladder_counts"]), uref.N_GRAM, 1.0)
+    one = statistics._profile_uncertainty_result(targets, edges, mass, case["counts"], np.ones(1), h, *tail)
+    two = statistics._surface_uncertainty_result(targets, edges, np.array([-100.0, 100.0]), mass2, counts2, np.ones(1),
+                                                 h2.reshape(1, k + 1, -1), *tail, True)
+    bound = 4.0 * ref.route_bound(case["explicit"], case["column_counts"]) * np.abs(ref.theta_svd(case["explicit"], case["column_counts"])).max()
+    assert np.array_equal(two["lowest"][:, 0], one["lowest"]) and np.all(two["lowest"][:, 1] == 0)
+    assert np.array_equal(two["d_mass_slots"][:, :, 0] == 0, mass == 0) and np.all(two["d_mass_slots"][:, :, 1:] == 0)
+    assert np.array_equal(one["d_mass"] == 0, mass[:, :b] == 0)
+    t, p = targets[0], mass[0, :b]
+    worst = 0.0
+    with np.errstate(invalid="ignore", divide="ignore"):
+        pairs = [((two["d_mass"][0, :, 0] / p) ** 2, (one["d_mass"][0] / p) ** 2),
+                 ((two["d_free_energy"][0, :, 0] / t) ** 2, (one["d_free_energy"][0] / t) ** 2),
+                 ((two["d_free_energy_from_lowest"][0, :, 0] / t) ** 2, (one["d_free_energy_from_lowest"][0] / t) ** 2),
+                 (two["log_mass_cov"][0], one["log_mass_cov"][0])]
+    outer, live = np.array([one["d_below"][0], one["d_above"][0], one["d_not_a_number"][0]]), mass[0, b:] > 0
+    assert np.array_equal(outer == 0, ~live) and live.any()
+    pairs.append(((two["d_mass_slots"][0, b:, 0][live] / mass[0, b:][live]) ** 2, (outer[live] / mass[0, b:][live]) ** 2))
+    for got, want in pairs:
+        assert np.array_equal(np.isnan(got), np.isnan(want)) and np.array_equal(got == 0, want == 0)
+        worst = max(worst, float(np.nanmax(np.abs(got - want))))
+    print("K = %d, %s bins: profile against the embedded surface, largest difference of a variance %.3e (bound %.3e, max |Var ln p| %.3e)"
+          % (k, bins, worst, bound, np.nanmax(np.abs(one["log_mass_cov"][0]))))
+    assert worst <= bound
 
 
 def test_indicator_columns_through_the_observable_route_give_the_same_errors():

@@ -215,6 +215,22 @@ def test_result_dictionary_shapes_nan_pattern_and_the_covariance_switch(k, grid)
     assert np.nanmax(np.abs(var.reshape(bx, by) - (out["d_free_energy_from_lowest"][0] / t) ** 2)) <= 1e-9 * scale
 
 
+@pytest.mark.parametrize("k,grid", [(8, "13x9"), (8, "7x5")])
+def test_the_error_bars_are_bit_for_bit_those_recorded_before_the_algebra_was_shared(k, grid):
+    """tests/golden/mbar_surface_uncertainty_result.npz holds what statistics._surface_uncertainty_result returned for these two
+    cases (_result: this file's synthetic long-double sums rounded to float64, inefficiency 1, with the covariance) when it
+    still carried the reduced algebra itself, before the profile's error bars moved onto it: the same operations in the same
+    order, so every new key is equal on its bits, NaNs included."""
+    with np.load(os.path.join(ROOT, "tests", "golden", "mbar_surface_uncertainty_result.npz")) as recorded:
+        out = _result(_case(k, grid))
+        for key in sorted(NEW_KEYS - {"n_samples"}):
+            want = recorded["K=%d %s %s" % (k, grid, key)]
+            assert out[key].shape == want.shape and out[key].dtype == want.dtype, key
+            assert np.array_equal(out[key], want, equal_nan=True), key
+            if want.dtype == np.float64:
+                assert np.array_equal(np.signbit(out[key]), np.signbit(want)), key
+
+
 def test_unresolved_cells_lose_their_error_bars_and_nothing_else():
     """A cell with positive mass whose sum of squared weights is no normal float64: NaN in d_mass too; an emptied cell: 0 and
     NaN; every other entry is what the input gives with both cells emptied, bit for bit (the algebra never sees them)."""

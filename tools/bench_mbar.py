@@ -285,7 +285,8 @@ def gram_rows(n_bins):
 
 
 def surface_rows(n_cells):
-    """rows_per_pass of csrc/me_mbar_hist2d.hip: the temperatures per pass, from the number of cells alone."""
+    """rows_per_pass of csrc/me_mbar_hist2d.hip (joint_rule_rows of csrc/me_mbar_slots.h with counts, widest R = 4): the
+    temperatures per pass, from the number of cells alone."""
     return 4 if n_cells <= 374 else 2 if n_cells <= 666 else 1
 
 
@@ -334,8 +335,9 @@ def time_surface(k, log2_chains, records, n_targets=8, grids=(8, 16, 33), bins=(
 
 
 def surface_gram_rows(n_cells):
-    """rule_rows of csrc/me_mbar_hist2d_cov.hip: the rows per pass, the widest of 16, 8, 4, 2, 1 whose table, at most ``(32 R +
-    2) S`` bytes, leaves three workgroups within the 160 KiB of a CU (16 up to 106 cells, 8 to 211, 4 to 420, 2 to 827)."""
+    """rule_rows of csrc/me_mbar_hist2d_cov.hip (joint_rule_rows of csrc/me_mbar_slots.h without counts, widest R = 16): the
+    rows per pass, the widest of 16, 8, 4, 2, 1 whose table, at most ``(32 R + 2) S`` bytes, leaves three workgroups within the
+    160 KiB of a CU (16 up to 106 cells, 8 to 211, 4 to 420, 2 to 827)."""
     return next((r for r in (16, 8, 4, 2) if n_cells <= (160 * 1024 // 3) // (32 * r + 2)), 1)
 
 

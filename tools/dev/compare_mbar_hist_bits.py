@@ -1,5 +1,5 @@
-"""Dev tool: the three histogram units (csrc/me_mbar_hist.hip, me_mbar_hist_cov.hip, me_mbar_hist2d.hip) of two builds of
-the library, bit for bit (profiles/mbar_slot_skeleton.txt).
+"""Dev tool: the four histogram units (csrc/me_mbar_hist.hip, me_mbar_hist_cov.hip, me_mbar_hist2d.hip,
+me_mbar_hist2d_cov.hip) of two builds of the library, bit for bit (profiles/mbar_slot_skeleton.txt, profiles/mbar_gram_driver.txt).
 
     python tools/dev/compare_mbar_hist_bits.py LIB_A.so LIB_B.so     (one fresh process per library, then the comparison)
     python tools/dev/compare_mbar_hist_bits.py --dump OUT.npz        (the library that METROPOLIS_HIP_LIB selects)
@@ -8,7 +8,8 @@ Engine-less entry points on the same seeded host arrays: K = 8 and 33 rungs (and
 problem); 1, 2047, 2049, 3 * 2048 + 5 and 2048 * 2048 + 5 samples (a count below K leaves a rung empty: the return code is
 compared); a few non-finite energies; values below, above, on the first and on the last edge, infinite and NaN, all 64 lanes
 in one slot, 64 distinct slots; 1, 64, 256 bins (masses), 64, 100, 256 bins with 5 temperatures (Gram sums: R = 16, 8, 4), grids
-12 x 7, 20 x 20, 33 x 33 with 9 temperatures (R = 4, 2, 1).  An axis that IS the energy exists in the engine form only
+12 x 7, 20 x 20, 33 x 33 with 9 temperatures (R = 4, 2, 1) and, for the cell Gram sums, with 5 (R = 8, 2, 1) besides 4 x 12 and
+6 x 9 (R = 16, 8: one grid on either side of a threshold).  An axis that IS the energy exists in the engine form only
 (me_mbar_histogram_joint with column -1): 31 records of 512 chains, 7 of 2112, a ragged eighth tile.  Every output array of every call is
 compared with np.array_equal on its bits."""
 import ctypes
@@ -24,6 +25,7 @@ sys.path.insert(0, ROOT)
 DP, IP, LP = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int64)
 SIZES = (1, 2047, 2049, 3 * 2048 + 5, 2048 * 2048 + 5)
 BINS_1D, BINS_GRAM, GRIDS = (1, 64, 256), (64, 100, 256), ((12, 7), (20, 20), (33, 33))
+GRIDS_GRAM = ((4, 12), (6, 9))          # 105 and 108 cells: either side of the cell Gram sums' step from R = 16 to 8 at 106
 
 
 def dp(a):
@@ -50,6 +52,15 @@ def value_patterns(n, top, rng):
     spread[at] = corners[:at.size]
     i = np.arange(n)
     return {"spread": spread, "one slot": np.full(n, 0.5), "64 slots": (i % 64) * (top / 64.0) + top / 128.0}
+
+
+def grid_patterns(n, bx, by, rng):
+    """:func:`value_patterns` for the two axes of a grid, with 64 consecutive samples in 64 different CELLS."""
+    xs, ys = value_patterns(n, bx, rng), value_patterns(n, by, rng)
+    i = np.arange(n)
+    per = min(by, 8)
+    xs["64 slots"], ys["64 slots"] = (i % 64) // per + 0.5, (i % 64) % per + 0.5
+    return xs, ys
 
 
 def dump(path):
@@ -87,16 +98,25 @@ def dump(path):
                              neff_fraction=neff, n_used=np.array(n_used.value))
             for bx, by in GRIDS:
                 ex, ey = np.linspace(0.0, float(bx), bx + 1), np.linspace(0.0, float(by), by + 1)
-                xs, ys = value_patterns(n, bx, rng), value_patterns(n, by, rng)
-                i = np.arange(n)
-                per = min(by, 8)
-                xs["64 slots"], ys["64 slots"] = (i % 64) // per + 0.5, (i % 64) % per + 0.5       # 64 different cells
+                xs, ys = grid_patterns(n, bx, by, rng)
                 for pattern in xs:
                     mass, counts, neff = np.zeros((9, bx + 3, by + 3)), np.zeros((bx + 3, by + 3), dtype=np.int64), np.zeros(9)
                     rc = lib.me_mbar_histogram_joint_samples(*head, dp(targets), 9, dp(xs[pattern]), dp(ys[pattern]), dp(ex), bx,
                                                              dp(ey), by, dp(mass), counts.ctypes.data_as(LP), dp(neff))
                     keep("K=%d n=%d %d x %d bins %s: joint" % (k, n, bx, by, pattern), rc, mass=mass, counts=counts,
                          neff_fraction=neff)
+            for bx, by in GRIDS + GRIDS_GRAM:
+                ex, ey = np.linspace(0.0, float(bx), bx + 1), np.linspace(0.0, float(by), by + 1)
+                xs, ys = grid_patterns(n, bx, by, rng)
+                for pattern in xs:
+                    h, ladder, cc = np.zeros((5, k + 1, (bx + 3) * (by + 3))), np.zeros((k, k)), np.zeros(k)
+                    mass, counts, neff = np.zeros((5, bx + 3, by + 3)), np.zeros((bx + 3, by + 3), dtype=np.int64), np.zeros(5)
+                    n_used = ctypes.c_int64()
+                    rc = lib.me_mbar_histogram_joint_gram_samples(*head, dp(targets), 5, dp(xs[pattern]), dp(ys[pattern]), dp(ex),
+                                                                  bx, dp(ey), by, dp(h), dp(ladder), dp(cc), dp(mass),
+                                                                  counts.ctypes.data_as(LP), dp(neff), ctypes.byref(n_used))
+                    keep("K=%d n=%d %d x %d bins %s: joint gram" % (k, n, bx, by, pattern), rc, cell_gram=h, ladder_gram=ladder,
+                         column_counts=cc, mass=mass, counts=counts, neff_fraction=neff, n_used=np.array(n_used.value))
     # the engine form, for an axis that is the energy (column -1) in either position
     for k in (8, 33):
         m, records = 64, 31 if k == 8 else 7            # 15 872 and 14 784 samples: seven tiles and a ragged eighth
