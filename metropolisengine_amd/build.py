@@ -218,6 +218,8 @@ def build_dims(n_real, n_complex, force=False):
 # the smallest streamed size; 31, 32 the full 32-lane group; 33, 63 odd sizes with two rows per lane in float32; 65 the
 # first size past the tile kernel; (20,6) a streamed complex block behind a large real block
 CHOLESKY_CONFORMANCE_DIMS = [(17, 0), (0, 12), (18, 0), (31, 0), (32, 0), (33, 0), (63, 0), (65, 0), (20, 6)]
+# (13,0) 91 packed entries: the largest float64 per-chain factor k_step still holds in registers; (14,0) 105: the first it streams
+PROPOSAL_CONFORMANCE_DIMS = [(13, 0), (14, 0)]
 
 
 def build_examples(force=False):
@@ -237,6 +239,8 @@ def build_examples(force=False):
                 pool.submit(build_dims, 100, 0, force)]    # beyond it: compiled for cov_mode="reference" (per-chain shapes)
         # the sizes tests/test_gpu_cholesky_conformance.py adds, one per edge of a factor kernel's dispatch
         jobs += [pool.submit(build_dims, nr, nc, force) for nr, nc in CHOLESKY_CONFORMANCE_DIMS]
+        # ... and the two tests/test_gpu_proposal_conformance.py adds, either side of kStreamF64Entries
+        jobs += [pool.submit(build_dims, nr, nc, force) for nr, nc in PROPOSAL_CONFORMANCE_DIMS]
         return [job.result() for job in jobs]
 
 
