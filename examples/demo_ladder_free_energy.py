@@ -2,7 +2,8 @@
 E = 4 (x^2 - 1)^2, sampled by parallel tempering with the energy of every chain recorded between swap rounds.  MBAR
 (``ladder_free_energies`` / ``reweight``, solved on the GPU) combines the eight rungs into ln Z(T) / Z(T_max) and
 C(T) = Var E / T^2 on a fine temperature grid, printed next to a numerical quadrature of
-Z(T) = integral exp(-4 (x^2 - 1)^2 / T) dx.
+Z(T) = integral exp(-4 (x^2 - 1)^2 / T) dx; the last column is C(T) of all samples with its asymptotic standard error
+(``fluctuation_uncertainties``).
 
 A swap pairs slot j of rung k with slot j of rung k+1, so the sixteen sub-ensembles {slots with j mod 16 = s} never
 exchange anything: sixteen independent estimates, whose spread is the error bar printed.
@@ -90,16 +91,18 @@ def main(grid=None, **kw):
     whole = engine.reweight(grid, engine.ladder_free_energies()["f"])
     ln_z, heat = subset_estimates(engine, grid)
     sigma = asymptotic_sigma(engine, grid)
+    # the asymptotic error of C(T) from ALL samples, taken as independent like sigma: beside the se of the sub-ensembles' mean
+    heat_sigma = engine.fluctuation_uncertainties(grid, engine.ladder_free_energies()["f"])["d_heat_capacity"]
     exact = quadrature(np.append(grid, temps[-1]))
     exact_ln_z, exact_heat = exact[0, :-1] - exact[0, -1], exact[2, :-1] / grid ** 2
     se = lambda a: a.std(axis=0, ddof=1) / np.sqrt(a.shape[0])      # noqa: E731
     print("asymptotic sigma ", end="")       # of ln Z(T)/Z(T_max), from all samples taken as independent: beside the se
-    print("     T   ln Z(T)/Z(T_max): MBAR +- se   quadrature      C(T): MBAR +- se   quadrature   neff")
+    print("     T   ln Z(T)/Z(T_max): MBAR +- se   quadrature      C(T): MBAR +- se   quadrature   neff   C(T) of all samples +- sigma")
     for i, t in enumerate(grid):
         print("     %.5f     " % sigma[i], end="")
-        print("%6.3f   %10.5f +- %.5f   %10.5f       %8.5f +- %.5f   %8.5f   %6.4f"
+        print("%6.3f   %10.5f +- %.5f   %10.5f       %8.5f +- %.5f   %8.5f   %6.4f   %8.5f +- %.5f"
               % (t, ln_z[:, i].mean(), se(ln_z)[i], exact_ln_z[i], heat[:, i].mean(), se(heat)[i], exact_heat[i],
-                 whole["neff_fraction"][i]))
+                 whole["neff_fraction"][i], whole["heat_capacity"][i], heat_sigma[i]))
     return {"temps": grid, "ln_z": ln_z, "heat_capacity": heat, "exact_ln_z": exact_ln_z, "exact_heat_capacity": exact_heat,
             "engine": engine}
 

@@ -477,6 +477,31 @@ int me_mbar_energy_shift(me_engine *engine, double *shift);
  *                       observable store.
  *   me_mbar_gram_observables_samples   the same on host arrays; observables is [n_columns][n_samples], 1 <= n_columns <=
  *                       ME_MAX_RECORDED_OBSERVABLES (ME_ERR_INVALID otherwise).
+ *   me_mbar_gram_fluctuations  me_mbar_gram for the asymptotic errors of the reweighted SECOND moments: the energy variance
+ *                       (heat capacity), and the variance and the energy covariance (d<A_q>/dT) of the Q recorded columns
+ *                       (csrc/me_mbar_cov.hip has the definition, the fluctuation form).  n_targets >= 1.  With E' = E_n - E_shift
+ *                       and A'_q = A_qn - S_q (E_shift = the least finite energy - 1, S_q as in me_mbar_gram_observables, so every
+ *                       factor is >= 1), W has C = n_rungs + n_targets (3 + 3 Q) columns: column k < n_rungs is rung k, and from
+ *                       column n_rungs + t (3 + 3 Q) on target t has its state column W_na, then W_na E' / m, W_na E'^2 / m, and
+ *                       for each q in turn W_na A'_q / m, W_na A'_q^2 / m, W_na A'_q E' / m, each with the reweighted moment m of
+ *                       its factor, formed on the device from what me_mbar_reweight and me_mbar_reweight_observables compute:
+ *                       mean_e - E_shift, var_e + (mean_e - E_shift)^2, mean_q - S_q, var_q + (mean_q - S_q)^2, cov_energy_q +
+ *                       (mean_q - S_q)(mean_e - E_shift).  moments is [n_targets][2 + 3 Q], these m in column order.  The products
+ *                       are formed in registers: nothing of size n_samples x columns is stored.  The engine form uses the
+ *                       observable store when there is one and runs with Q = 0 (the energy columns alone) otherwise.  gram is
+ *                       [C][C], full and bitwise symmetric; column_counts [C]; ln_z, mean_e, var_e [n_targets] are
+ *                       me_mbar_reweight's and mean, var, cov_energy [n_targets][Q] me_mbar_reweight_observables', bit for bit
+ *                       when every energy is finite; *energy_shift, shifts [Q] and *n_used.  Every output but gram and
+ *                       column_counts may be NULL.  Non-finite energies: packed away first as in me_mbar_gram_observables, every
+ *                       result is bit for bit the result on the arrays without those samples.  A non-finite A_q in a used sample
+ *                       gives the three columns of q at every target a NaN moment and NaN rows and columns of gram, and no other
+ *                       entry changes.  Targets go through the device in chunks of (128 - n_rungs) / (3 + 3 Q) (at least 1), every
+ *                       chunk with the ladder columns; the blocks of gram that pair targets of different chunks are NaN.  The
+ *                       entries among ladder, state and E' columns are me_mbar_gram's bit for bit, those among ladder, state
+ *                       and A'_q columns me_mbar_gram_observables'.  All sums have a fixed order.  Errors as for
+ *                       me_mbar_gram_observables, except that a missing observable store is no error.
+ *   me_mbar_gram_fluctuations_samples   the same on host arrays; observables is [n_columns][n_samples], 0 <= n_columns <=
+ *                       ME_MAX_RECORDED_OBSERVABLES (ME_ERR_INVALID otherwise); n_columns = 0: observables may be NULL.
  *   me_mbar_histogram          the reweighted histogram of one quantity A over the recorded samples at each of the n target
  *                       temperatures (finite, > 0), with the normalised weights w of me_mbar_reweight (sum over the used
  *                       samples = 1; a sample is used when its ENERGY is finite; csrc/me_mbar_hist.hip has the definition).
@@ -564,6 +589,15 @@ int me_mbar_gram_observables_samples(int32_t device_id, const double *energies, 
                                      const double *ladder_temps, int32_t n_rungs, const double *observables, int32_t n_columns,
                                      const double *f, const double *temps, int32_t n_targets, double *gram,
                                      double *column_counts, double *ln_z, double *mean, double *shifts, int64_t *n_used);
+int me_mbar_gram_fluctuations(me_engine *engine, const double *f, const double *temps, int32_t n_targets, double *gram,
+                              double *column_counts, double *ln_z, double *moments, double *energy_shift, double *shifts,
+                              double *mean_e, double *var_e, double *mean, double *var, double *cov_energy, int64_t *n_used);
+int me_mbar_gram_fluctuations_samples(int32_t device_id, const double *energies, const int32_t *rungs, int64_t n_samples,
+                                      const double *ladder_temps, int32_t n_rungs, const double *observables, int32_t n_columns,
+                                      const double *f, const double *temps, int32_t n_targets, double *gram,
+                                      double *column_counts, double *ln_z, double *moments, double *energy_shift,
+                                      double *shifts, double *mean_e, double *var_e, double *mean, double *var,
+                                      double *cov_energy, int64_t *n_used);
 int me_mbar_histogram(me_engine *engine, const double *f, const double *temps, int32_t n, int32_t column, const double *edges,
                       int32_t n_bins, double *mass, int64_t *counts, double *neff_fraction);
 int me_mbar_histogram_samples(int32_t device_id, const double *energies, const int32_t *rungs, int64_t n_samples,

@@ -152,6 +152,10 @@ SYMBOLS = {
     "me_mbar_gram_observables_samples": (ctypes.c_int, [ctypes.c_int32, _dp, ctypes.POINTER(ctypes.c_int32), ctypes.c_int64, _dp,
                                                         ctypes.c_int32, _dp, ctypes.c_int32, _dp, _dp, ctypes.c_int32, _dp, _dp,
                                                         _dp, _dp, _dp, ctypes.POINTER(ctypes.c_int64)]),
+    "me_mbar_gram_fluctuations": (ctypes.c_int, [_H, _dp, _dp, ctypes.c_int32] + [_dp] * 11 + [ctypes.POINTER(ctypes.c_int64)]),
+    "me_mbar_gram_fluctuations_samples": (ctypes.c_int, [ctypes.c_int32, _dp, ctypes.POINTER(ctypes.c_int32), ctypes.c_int64, _dp,
+                                                         ctypes.c_int32, _dp, ctypes.c_int32, _dp, _dp, ctypes.c_int32] + [_dp] * 11 +
+                                          [ctypes.POINTER(ctypes.c_int64)]),
     "me_observable_samples_enable": (ctypes.c_int, [_H, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32]),
     "me_observable_samples_info": (ctypes.c_int, [_H, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
     "me_observable_samples_get": (ctypes.c_int, [_H, ctypes.c_int64, ctypes.c_int64, _dp]),

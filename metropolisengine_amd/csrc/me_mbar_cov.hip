@@ -44,7 +44,7 @@
 // no other entry changes.  Targets go in chunks of (128 - K) / (1 + Q), at least 3, every chunk with the ladder columns.
 // Kernels: k_mbar_compact also packs the columns of the used samples ([Q][n_used]); k_mbar_min_columns (grid (blocks, Q)) is
 // k_mbar_min per column; k_mbar_gram_obs_columns (one block) is k_mbar_gram_columns with, per column of W, the observable it
-// carries (-1: none), its shift and its normaliser; k_mbar_gram<true> is k_mbar_gram<false> (the kernel of the energy form)
+// carries (-1: none), its shift and its normaliser; k_mbar_gram<Form::kObs> is k_mbar_gram<Form::kEnergy> (the energy form's)
 // with two additions: per 256 samples every lane parks the Q values of its sample in LDS beside (E_n, d_n), as [Q][257]
 // doubles -- the fill threads of a half-wavefront read 2 rows x 16 columns, that is observables q .. q + 15 of samples s, s + 1;
 // with the odd stride 257 value (q, s) lies in bank 2 (q + s) mod 64 for the 8-byte reads, so only pairs with equal q + s
@@ -52,12 +52,33 @@
 // the exponential by (A_qn - S_q) / (mean_tq - S_q).  The MFMA loop, the tile assignment and the summation order are the same
 // code, so an entry that pairs ladder and state columns has the bits the energy form gives it, and an observable column has the
 // same bits alone as among 16.
+//
+// The fluctuation form (me_mbar_gram_fluctuations and its engine-less twin): error bars for the reweighted SECOND moments, the
+// energy variance (heat capacity) and the variance and energy covariance (d<A_q>/dT) of the Q <= 16 recorded columns; Q = 0 is
+// the heat capacity alone from the energy store alone.  With E' = E_n - E_shift and A'_q = A_qn - S_q, the shifts of the two
+// forms above (every E', A'_q >= 1, so every product is >= 1 and every entry of W >= 0), C = K + n_targets (3 + 3 Q):
+//     state column of target t   W_na                                                 column K + t (3 + 3 Q)
+//     E1, E2                     W_na E' / m_E,  W_na E' E' / (var_e + m_E^2)            the next two; m_E = mean_e - E_shift
+//     A1_q, A2_q, AE_q           W_na A'_q / m_q,  W_na A'_q A'_q / (var_tq + m_q^2),  W_na A'_q E' / (cov_energy_tq + m_q m_E)
+//                                                                                     columns K + t (3 + 3 Q) + 3 + 3 q ...; m_q = mean_tq - S_q
+// The normalisers are the reweighted moments of the factors, formed in k_mbar_gram_fluct_columns (one block) from what the
+// reweighting kernels (me_mbar.hip, me_mbar_obs.hip) leave on the device, and returned as `moments`; an observable with a
+// non-finite mean, variance or covariance gets NaN for all three (its rows and columns of G are NaN, no other entry changes).
+// The host's delta method on Theta is in statistics.py.  Targets go in chunks of (128 - K) / (3 + 3 Q), at least 1.  The products
+// are formed in registers in the fill: Form::kFluct of k_mbar_gram is the observable form's kernel (the same parking of the Q
+// values, skipped when Q = 0) whose column constants also carry a kind (state, E1, E2, A1, A2, AE) and E_shift, and whose fill
+// multiplies the exponential by w * x / norm with x = E' (the energy form's expression), A' (the observable form's), E' * E',
+// A' * A' or A' * E'.  The MFMA loop, the tile assignment, the summation order, the packing and k_mbar_gram_finish are shared, so
+// the entries among ladder, state and E1 columns have the energy form's bits and those among ladder, state and A1 columns the
+// observable form's.  The machine code of the two other instantiations is the one they had before this form existed.
 // LDS per block: [2][16][Cp] sub-tile buffers (36 KiB at C = 128), 4 KiB (E_n, d_n), 3 KiB column constants; the observable form
 // adds Q x 257 x 8 bytes (32.1 KiB at Q = 16) and 1.5 KiB of column constants: 76.6 KiB at C = 128, Q = 16, which needs the
-// raised dynamic-LDS limit and lets two blocks share a CU's 160 KiB (2 wavefronts per SIMD); 46.5 KiB at Q = 1 (3 blocks).
-// Registers (hipcc -O3, gfx950, -Rpass-analysis=kernel-resource-usage): k_mbar_gram<false> 93 VGPRs + 72 AGPRs (the
-// accumulators), 3 wavefronts per SIMD, no scratch; k_mbar_gram<true> 95 VGPRs + 72 AGPRs, 3 wavefronts per SIMD by
-// registers (2 where the LDS of 16 observables decides), no scratch; no other kernel of this file uses scratch.
+// raised dynamic-LDS limit and lets two blocks share a CU's 160 KiB (2 wavefronts per SIMD); 46.5 KiB at Q = 1 (3 blocks).  The
+// fluctuation form adds 0.5 KiB of kinds to that: 77.1 KiB at C = 128, Q = 16 (still two blocks per CU), 45 KiB at Q = 0.
+// Registers (hipcc -O3, gfx950, -Rpass-analysis=kernel-resource-usage): k_mbar_gram<Form::kEnergy> 93 VGPRs + 72 AGPRs (the
+// accumulators), 3 wavefronts per SIMD, no scratch; k_mbar_gram<Form::kObs> 95 VGPRs + 72 AGPRs, 3 wavefronts per SIMD by
+// registers (2 where the LDS of 16 observables decides), no scratch; k_mbar_gram<Form::kFluct> 95 VGPRs + 72 AGPRs, 106 SGPRs,
+// 9 216 bytes of static LDS, 3 wavefronts per SIMD by registers, no scratch; no other kernel of this file uses scratch.
 #include "me_launch.h"
 #include "me_mbar.h"
 #include "me_mbar_gram_tiles.h"
@@ -73,6 +94,13 @@ constexpr int kColB = 0, kColG = kMaxCols, kColMean = 2 * kMaxCols, kColShift = 
 constexpr int kColOwnShift = 3 * kMaxCols, kColWhich = 4 * kMaxCols, kColShifts = 5 * kMaxCols;
 constexpr int kObsColDoubles = 5 * kMaxCols + ME_MAX_RECORDED_OBSERVABLES;
 constexpr int kObsStride = kThreads + 1;        // doubles between two observables of the parked samples (odd: see the header)
+// the fluctuation form's column constants: the observable form's five arrays, then the kind of the column, then S_q and E_shift
+constexpr int kColKind = 5 * kMaxCols, kFluctShifts = 6 * kMaxCols, kFluctEnergyShift = 6 * kMaxCols + ME_MAX_RECORDED_OBSERVABLES;
+constexpr int kFluctColDoubles = kFluctEnergyShift + 1;
+// the factor a column of the fluctuation form puts on the state weight: none, E', E'^2, A', A'^2, A' E'
+enum Kind : int { kState = 0, kE1, kE2, kA1, kA2, kAE };
+// the three forms of k_mbar_gram
+enum class Form { kEnergy, kObs, kFluct };
 
 // counts[tile] = the finite energies of the tile
 __global__ void __launch_bounds__(kThreads) k_mbar_used_tiles(const double *__restrict__ energies, long long n, unsigned int *counts) {
@@ -253,18 +281,79 @@ __global__ void __launch_bounds__(kMaxCols) k_mbar_gram_obs_columns(const double
   if (c < nq) cols[kColShifts + c] = shifts[c];
 }
 
-// partials[block] = the packed lower triangle of the block's part of W^T W, n_cols <= kMaxCols columns.  kObs = false: the
-// energy form, n_cols = K + 2 n_targets, `oc` unused; kObs = true: the observable form, n_cols = K + (1 + Q) n_targets, `cols` of
-// k_mbar_gram_obs_columns.  Dynamic LDS: 2 * kSub * cp doubles, cp the padded row length (see the header of this file), and
-// in the observable form oc.n_columns * kObsStride more.
-template <bool kObs>
+// The fluctuation form's cols = [b | g | normaliser | shift | observable | kind] of the K ladder columns and of the 3 + 3 nq
+// columns (state, E1, E2, then A1, A2, AE of each observable) of each of n_targets temperatures, then S_q and E_shift.  (ln_z,
+// mean_e, var_e, .) of the targets in `out`; obs = [mean | var | cov_energy], each [.][nq] from these targets on and obs_part
+// doubles after the one before, all as the reweighting kernels left them (nq = 0: never read); e_minima is [n_blocks], a_minima
+// [nq][n_blocks].  moments[n_targets][2 + 3 nq] = the normalisers in column order.  A non-finite mean, variance or covariance
+// of observable q gives its three columns a NaN normaliser.
+__global__ void __launch_bounds__(kMaxCols) k_mbar_gram_fluct_columns(const double *__restrict__ table, int n_rungs,
+                                                                      const double *__restrict__ inv_temps,
+                                                                      const double *__restrict__ out, const double *__restrict__ obs,
+                                                                      long long obs_part, int nq, int n_targets,
+                                                                      const double *__restrict__ e_minima,
+                                                                      const double *__restrict__ a_minima, int n_blocks,
+                                                                      double *cols, double *moments) {
+  __shared__ double part[kMaxCols], shifts[ME_MAX_RECORDED_OBSERVABLES];
+  const double e_shift = least_of_blocks(e_minima, n_blocks, part) - 1.0;
+  __syncthreads();                                               // (`part` is written again)
+  for (int q = 0; q < nq; ++q) {
+    const double least = least_of_blocks(a_minima + (size_t)q * n_blocks, n_blocks, part);
+    if (threadIdx.x == 0) shifts[q] = least - 1.0;
+    __syncthreads();
+  }
+  const int c = threadIdx.x, per = 3 + 3 * nq;
+  double b = 0.0, g = 0.0, norm = 0.0, shift = 0.0, which = -1.0;
+  int kind = kState;
+  if (c < n_rungs) {
+    b = table[kBeta + c];
+    g = table[kF + c];
+  } else if (c < n_rungs + per * n_targets) {
+    const int t = (c - n_rungs) / per, j = (c - n_rungs) - t * per;
+    b = inv_temps[t];
+    g = -out[4 * t];
+    const double m_e = out[4 * t + 1] - e_shift;                 // >= 1
+    if (j == 1 || j == 2) {
+      kind = j == 1 ? kE1 : kE2;
+      norm = j == 1 ? m_e : __builtin_fma(m_e, m_e, out[4 * t + 2]);
+    } else if (j >= 3) {
+      const int q = (j - 3) / 3;
+      const double mean = obs[t * nq + q], var = obs[obs_part + t * nq + q], cov = obs[2 * obs_part + t * nq + q];
+      kind = kA1 + (j - 3) - 3 * q;
+      which = (double)q;
+      shift = shifts[q];
+      const double m_q = mean - shift;
+      norm = kind == kA1 ? m_q : kind == kA2 ? __builtin_fma(m_q, m_q, var) : __builtin_fma(m_q, m_e, cov);
+      if (!(isfinite(mean) && isfinite(var) && isfinite(cov))) norm = NAN;   // (the three columns of W, their rows and columns of G)
+    }
+    if (j >= 1) moments[t * (per - 1) + j - 1] = norm;
+  }
+  cols[kColB + c] = b;
+  cols[kColG + c] = g;
+  cols[kColMean + c] = norm;
+  cols[kColOwnShift + c] = shift;
+  cols[kColWhich + c] = which;
+  cols[kColKind + c] = (double)kind;
+  if (c < nq) cols[kFluctShifts + c] = shifts[c];
+  if (c == 0) cols[kFluctEnergyShift] = e_shift;
+}
+
+// partials[block] = the packed lower triangle of the block's part of W^T W, n_cols <= kMaxCols columns.  Form::kEnergy: n_cols =
+// K + 2 n_targets, `oc` unused; Form::kObs: the observable form, n_cols = K + (1 + Q) n_targets, `cols` of
+// k_mbar_gram_obs_columns; Form::kFluct: the fluctuation form, n_cols = K + (3 + 3 Q) n_targets, `cols` of
+// k_mbar_gram_fluct_columns, Q = oc.n_columns may be 0 (`oc` and the observables' LDS are then never touched).  Dynamic LDS: 2 *
+// kSub * cp doubles, cp the padded row length (see the header of this file), and in the forms with observables oc.n_columns *
+// kObsStride more.
+template <Form kForm>
 __global__ void __launch_bounds__(kThreads) k_mbar_gram(const double *__restrict__ energies, long long n, int n_rungs,
                                                         const double *__restrict__ table, const double *__restrict__ cols,
                                                         int n_cols, int cp, long long n_tiles, double *partials, ObsColumns oc) {
+  constexpr bool kObs = kForm == Form::kObs, kFluct = kForm == Form::kFluct;
   extern __shared__ double w_lds[];                              // [2][kSub][cp], then s_a [Q][kObsStride]
   __shared__ double s_e[kThreads], s_d[kThreads], c_b[kMaxCols], c_g[kMaxCols], c_mean[kMaxCols];
-  __shared__ double c_shift[kObs ? kMaxCols : 1];
-  __shared__ int c_which[kObs ? kMaxCols : 1];
+  __shared__ double c_shift[kObs || kFluct ? kMaxCols : 1];
+  __shared__ int c_which[kObs || kFluct ? kMaxCols : 1];
+  __shared__ int c_kind[kFluct ? kMaxCols : 1];
   double *const s_a = w_lds + 2 * kSub * cp;
   const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const Fragment fr = fragment_of(lane);                         // the MFMA's (k, i / j) of this lane
@@ -274,12 +363,13 @@ __global__ void __launch_bounds__(kThreads) k_mbar_gram(const double *__restrict
     c_b[t] = cols[kColB + t];
     c_g[t] = cols[kColG + t];
     c_mean[t] = cols[kColMean + t];
-    if constexpr (kObs) {
+    if constexpr (kObs || kFluct) {
       c_shift[t] = cols[kColOwnShift + t];
       c_which[t] = (int)cols[kColWhich + t];
     }
+    if constexpr (kFluct) c_kind[t] = (int)cols[kColKind + t];
   }
-  const double shift = kObs ? 0.0 : cols[kColShift];
+  const double shift = kObs ? 0.0 : cols[kFluct ? kFluctEnergyShift : kColShift];
   // this wavefront's tiles: pair p = wave + 4 s = I (I + 1) / 2 + J, column offsets 16 I and 16 J
   int off_i[kSlots], off_j[kSlots];
 #pragma unroll
@@ -302,8 +392,8 @@ __global__ void __launch_bounds__(kThreads) k_mbar_gram(const double *__restrict
       // (every thread has passed the last barrier of the step before, so its fills have read s_e and s_d)
       s_e[t] = ok ? e : 0.0;
       s_d[t] = ok ? m + log(s) : INFINITY;
-      if constexpr (kObs) {
-        if (i < n) {
+      if constexpr (kObs || kFluct) {
+        if (i < n && (kObs || oc.n_columns > 0)) {               // (the fluctuation form without observables: nothing to park)
           // (the record of the step's first sample is wave-uniform: the division stays off the vector registers)
           long long record = (i - t) / oc.n_chains, chain = (i - t) - record * oc.n_chains + t;
           while (chain >= oc.n_chains) {
@@ -329,6 +419,16 @@ __global__ void __launch_bounds__(kThreads) k_mbar_gram(const double *__restrict
               if constexpr (kObs) {
                 const int which = c_which[col];
                 if (which >= 0) w = w * (s_a[which * kObsStride + q * kSub + row] - c_shift[col]) / c_mean[col];
+              } else if constexpr (kFluct) {
+                const int kind = c_kind[col];
+                if (kind != kState) {
+                  const int which = c_which[col];
+                  const double e1 = es - shift;
+                  const double a1 = which >= 0 ? s_a[which * kObsStride + q * kSub + row] - c_shift[col] : 0.0;
+                  // E1 and A1 are the energy form's and the observable form's expressions; the others w * (x * y) / norm
+                  const double factor = kind == kE1 ? e1 : kind == kE2 ? e1 * e1 : kind == kA1 ? a1 : kind == kA2 ? a1 * a1 : a1 * e1;
+                  w = w * factor / c_mean[col];
+                }
               } else {
                 const double mean = c_mean[col];
                 if (mean != 0.0) w = w * (es - shift) / mean;
@@ -472,7 +572,7 @@ hipError_t mbar_gram(Problem &p, const Source &src, const double *f, const doubl
                            n_targets > 0 ? w.inv_temps.get<const double>() + t0 : nullptr,
                            n_targets > 0 ? w.out.get<const double>() + 4 * (size_t)t0 : nullptr, nt, minima.get<const double>(),
                            n_blocks, cols.get<double>());
-        hipLaunchKernelGGL(k_mbar_gram<false>, dim3(n_blocks), dim3(kThreads), 2 * kSub * cp * sizeof(double), stream, ps.energies,
+        hipLaunchKernelGGL(k_mbar_gram<Form::kEnergy>, dim3(n_blocks), dim3(kThreads), 2 * kSub * cp * sizeof(double), stream, ps.energies,
                            ps.n_samples, n_rungs, w.table.get<const double>(), cols.get<const double>(), n_cols, cp, n_tiles, partials,
                            ObsColumns{});
         return hipSuccess;
@@ -510,7 +610,7 @@ hipError_t mbar_gram_observables(Problem &p, const Source &src, const double *f,
   const long long n_tiles = tiles_of(ps.n_samples);
   ME_MBAR_HIP(minima.resize((size_t)nq * n_blocks * sizeof(double)));
   ME_MBAR_HIP(cols.resize(kObsColDoubles * sizeof(double)));
-  ME_MBAR_HIP(raise_lds_limit<k_mbar_gram<true>>((2 * kSub * padded_row(kMaxCols) + ME_MAX_RECORDED_OBSERVABLES * kObsStride) * sizeof(double)));
+  ME_MBAR_HIP(raise_lds_limit<k_mbar_gram<Form::kObs>>((2 * kSub * padded_row(kMaxCols) + ME_MAX_RECORDED_OBSERVABLES * kObsStride) * sizeof(double)));
   hipLaunchKernelGGL(k_mbar_min_columns, dim3(n_blocks, nq), dim3(kThreads), 0, stream, used.oc, ps.n_samples, n_tiles, minima.get<double>());
   std::vector<double> out(4 * (size_t)n_targets), means(cells), own_shifts((size_t)nq);
   ME_MBAR_HIP(gram_chunks(
@@ -519,7 +619,7 @@ hipError_t mbar_gram_observables(Problem &p, const Source &src, const double *f,
         hipLaunchKernelGGL(k_mbar_gram_obs_columns, dim3(1), dim3(kMaxCols), 0, stream, w.table.get<const double>(), n_rungs,
                            w.inv_temps.get<const double>() + t0, w.out.get<const double>() + 4 * (size_t)t0,
                            obs_out.get<const double>() + (size_t)t0 * nq, nq, nt, minima.get<const double>(), n_blocks, cols.get<double>());
-        hipLaunchKernelGGL(k_mbar_gram<true>, dim3(n_blocks), dim3(kThreads), (2 * kSub * cp + nq * kObsStride) * sizeof(double), stream,
+        hipLaunchKernelGGL(k_mbar_gram<Form::kObs>, dim3(n_blocks), dim3(kThreads), (2 * kSub * cp + nq * kObsStride) * sizeof(double), stream,
                            ps.energies, ps.n_samples, n_rungs, w.table.get<const double>(), cols.get<const double>(), n_cols, cp, n_tiles,
                            partials, used.oc);
         return hipSuccess;
@@ -533,6 +633,77 @@ hipError_t mbar_gram_observables(Problem &p, const Source &src, const double *f,
   unpack_targets(out, n_targets, ln_z, nullptr, nullptr, nullptr);
   if (mean) std::copy(means.begin(), means.end(), mean);
   if (shifts) std::copy(own_shifts.begin(), own_shifts.end(), shifts);
+  return hipSuccess;
+}
+
+// The host outputs of the fluctuation form beside gram and column_counts, each may be nullptr: ln_z, mean_e, var_e [n_targets],
+// moments [n_targets][2 + 3 Q], *energy_shift, shifts [Q], mean, var, cov_energy [n_targets][Q]
+struct FluctuationOutputs {
+  double *ln_z, *moments, *energy_shift, *shifts, *mean_e, *var_e, *mean, *var, *cov_energy;
+};
+
+// The fluctuation form: gram[C][C] and column_counts[C] with C = n_rungs + n_targets (3 + 3 Q), Q = the columns of src (0: the
+// energy columns alone), and `o`.  n_targets >= 1.
+hipError_t mbar_gram_fluctuations(Problem &p, const Source &src, const double *f, const double *temps, int n_targets, double *gram,
+                                  double *column_counts, const FluctuationOutputs &o) {
+  ME_MBAR_HIP(prepare(p, src, f));
+  if (p.empty_rung >= 0) return hipSuccess;
+  Work &w = p.w;
+  const int n_rungs = p.n_rungs, nq = src.columns.n_columns, per = 3 + 3 * nq;
+  hipStream_t stream = p.stream;
+  UsedSamples used;
+  ME_MBAR_HIP(pack_used(p, src.columns, used));
+  const MbarSamples &ps = used.sm;
+  const size_t cells = (size_t)n_targets * nq;
+  std::vector<double> inv;
+  ObsScratch scratch;
+  DeviceBuffer obs_out, e_minima, a_minima, cols, moments_dev;
+  ME_MBAR_HIP(reweight_enqueue(p, ps, temps, n_targets, inv));
+  const int n_blocks = blocks_of(ps.n_samples);
+  const long long n_tiles = tiles_of(ps.n_samples);
+  ME_MBAR_HIP(e_minima.resize((size_t)n_blocks * sizeof(double)));
+  ME_MBAR_HIP(cols.resize(kFluctColDoubles * sizeof(double)));
+  ME_MBAR_HIP(moments_dev.resize((size_t)n_targets * (per - 1) * sizeof(double)));
+  hipLaunchKernelGGL(k_mbar_min, dim3(n_blocks), dim3(kThreads), 0, stream, ps.energies, ps.n_samples, n_tiles, e_minima.get<double>());
+  if (nq > 0) {
+    ME_MBAR_HIP(obs_out.resize((3 * cells + (size_t)n_targets) * sizeof(double)));
+    ME_MBAR_HIP(reweight_observables_enqueue(p, ps, used.oc, w.inv_temps.get<const double>(), n_targets, scratch, obs_out.get<double>()));
+    ME_MBAR_HIP(a_minima.resize((size_t)nq * n_blocks * sizeof(double)));
+    hipLaunchKernelGGL(k_mbar_min_columns, dim3(n_blocks, nq), dim3(kThreads), 0, stream, used.oc, ps.n_samples, n_tiles,
+                       a_minima.get<double>());
+  }
+  ME_MBAR_HIP(raise_lds_limit<k_mbar_gram<Form::kFluct>>((2 * kSub * padded_row(kMaxCols) + ME_MAX_RECORDED_OBSERVABLES * kObsStride) * sizeof(double)));
+  std::vector<double> out(4 * (size_t)n_targets), obs(3 * cells), moments((size_t)n_targets * (per - 1)), own_shifts((size_t)nq + 1);
+  ME_MBAR_HIP(gram_chunks(
+      p, ps.n_samples, per, n_targets, gram, column_counts,
+      [&](int t0, int nt, int n_cols, int cp, double *partials) {
+        hipLaunchKernelGGL(k_mbar_gram_fluct_columns, dim3(1), dim3(kMaxCols), 0, stream, w.table.get<const double>(), n_rungs,
+                           w.inv_temps.get<const double>() + t0, w.out.get<const double>() + 4 * (size_t)t0,
+                           nq > 0 ? obs_out.get<const double>() + (size_t)t0 * nq : nullptr, (long long)cells, nq, nt,
+                           e_minima.get<const double>(), nq > 0 ? a_minima.get<const double>() : nullptr, n_blocks, cols.get<double>(),
+                           moments_dev.get<double>() + (size_t)t0 * (per - 1));
+        hipLaunchKernelGGL(k_mbar_gram<Form::kFluct>, dim3(n_blocks), dim3(kThreads), (2 * kSub * cp + nq * kObsStride) * sizeof(double),
+                           stream, ps.energies, ps.n_samples, n_rungs, w.table.get<const double>(), cols.get<const double>(), n_cols, cp,
+                           n_tiles, partials, used.oc);
+        return hipSuccess;
+      },
+      [&] {
+        ME_MBAR_HIP(hipMemcpyAsync(out.data(), w.out.get(), out.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+        ME_MBAR_HIP(hipMemcpyAsync(moments.data(), moments_dev.get(), moments.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+        if (nq > 0) ME_MBAR_HIP(hipMemcpyAsync(obs.data(), obs_out.get(), obs.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+        // (S_q and E_shift lie one after the other when Q = 16; they are fetched separately so that any Q reads its own)
+        if (nq > 0)
+          ME_MBAR_HIP(hipMemcpyAsync(own_shifts.data(), cols.get<double>() + kFluctShifts, (size_t)nq * sizeof(double), hipMemcpyDeviceToHost,
+                                     stream));
+        return hipMemcpyAsync(own_shifts.data() + nq, cols.get<double>() + kFluctEnergyShift, sizeof(double), hipMemcpyDeviceToHost, stream);
+      }));
+  unpack_targets(out, n_targets, o.ln_z, o.mean_e, o.var_e, nullptr);
+  if (o.moments) std::copy(moments.begin(), moments.end(), o.moments);
+  if (o.energy_shift) *o.energy_shift = own_shifts[(size_t)nq];
+  if (o.shifts) std::copy(own_shifts.begin(), own_shifts.begin() + nq, o.shifts);
+  if (o.mean) std::copy(obs.begin(), obs.begin() + cells, o.mean);
+  if (o.var) std::copy(obs.begin() + cells, obs.begin() + 2 * cells, o.var);
+  if (o.cov_energy) std::copy(obs.begin() + 2 * cells, obs.end(), o.cov_energy);
   return hipSuccess;
 }
 
@@ -573,6 +744,19 @@ int gram_observables_common(const Source &src, const double *f, const double *te
   if (rc) return rc;
   Problem p;
   rc = mbar_check_common(src.e, p, mbar_gram_observables(p, src, f, temps, n_targets, gram, column_counts, ln_z, mean, shifts));
+  if (rc) return rc;
+  if (n_used) *n_used = p.n_used_ll;
+  return ME_OK;
+}
+
+// the two forms of me_mbar_gram_fluctuations behind their Source
+int gram_fluctuations_common(const Source &src, const double *f, const double *temps, int n_targets, double *gram, double *column_counts,
+                             const FluctuationOutputs &o, int64_t *n_used) {
+  if (!gram || !column_counts) return fail(src.e, ME_ERR_INVALID, "gram and column_counts are needed");
+  int rc = check_f_and_targets(src.e, f, std::min(src.n_rungs, kK), temps, n_targets, 1);
+  if (rc) return rc;
+  Problem p;
+  rc = mbar_check_common(src.e, p, mbar_gram_fluctuations(p, src, f, temps, n_targets, gram, column_counts, o));
   if (rc) return rc;
   if (n_used) *n_used = p.n_used_ll;
   return ME_OK;
@@ -630,6 +814,30 @@ int me_mbar_gram_observables_samples(int32_t device_id, const double *energies, 
   Source src;
   const int rc = src.from_host(device_id, energies, rungs, n_samples, ladder_temps, n_rungs, observables, n_columns);
   return rc ? rc : src.finish(gram_observables_common(src, f, temps, n_targets, gram, column_counts, ln_z, mean, shifts, n_used));
+}
+
+int me_mbar_gram_fluctuations(me_engine *e, const double *f, const double *temps, int32_t n_targets, double *gram, double *column_counts,
+                              double *ln_z, double *moments, double *energy_shift, double *shifts, double *mean_e, double *var_e,
+                              double *mean, double *var, double *cov_energy, int64_t *n_used) {
+  Source src;
+  const int rc = src.from_engine(e);      // (no observable store: src.columns.n_columns = 0, the energy columns alone)
+  if (rc) return rc;
+  return gram_fluctuations_common(src, f, temps, n_targets, gram, column_counts,
+                                  FluctuationOutputs{ln_z, moments, energy_shift, shifts, mean_e, var_e, mean, var, cov_energy}, n_used);
+}
+
+int me_mbar_gram_fluctuations_samples(int32_t device_id, const double *energies, const int32_t *rungs, int64_t n_samples,
+                                      const double *ladder_temps, int32_t n_rungs, const double *observables, int32_t n_columns,
+                                      const double *f, const double *temps, int32_t n_targets, double *gram, double *column_counts,
+                                      double *ln_z, double *moments, double *energy_shift, double *shifts, double *mean_e,
+                                      double *var_e, double *mean, double *var, double *cov_energy, int64_t *n_used) {
+  Source src;
+  const int rc = n_columns == 0 ? src.from_host(device_id, energies, rungs, n_samples, ladder_temps, n_rungs)
+                                : src.from_host(device_id, energies, rungs, n_samples, ladder_temps, n_rungs, observables, n_columns);
+  if (rc) return rc;
+  return src.finish(gram_fluctuations_common(src, f, temps, n_targets, gram, column_counts,
+                                             FluctuationOutputs{ln_z, moments, energy_shift, shifts, mean_e, var_e, mean, var, cov_energy},
+                                             n_used));
 }
 
 }  // extern "C"

@@ -968,6 +968,29 @@ class MetropolisEngine:
         k = max(f.size, 1)      # (the ladder's rungs; without a ladder the library refuses before it writes)
         return statistics._observable_uncertainties(self._lib.me_mbar_gram_observables, (self._handle,), k, f, temps, names, g)
 
+    def fluctuation_uncertainties(self, temps, f=None, inefficiency=1.0):
+        """Asymptotic standard errors of the reweighted second moments (``me_mbar_gram_fluctuations``: one further pass over the
+        recorded samples on the matrix cores): of :meth:`reweight`'s ``energy_mean``, ``energy_var`` and ``heat_capacity`` and,
+        with an observable store, of :meth:`reweight_observables`' ``mean``, ``var``, ``cov_energy`` and ``dmean_dT`` -- each
+        value with its error under ``"d_" + key``, and ``{"temps", "names", "n_samples"}``, see
+        :func:`metropolisengine_amd.statistics.mbar_fluctuation_uncertainties`.  Without an observable store the energy keys are
+        computed alone and the others are ``(T, 0)``.  ``f``: the free energies of :meth:`ladder_free_energies` (solved with the
+        defaults when ``None``).  ``inefficiency``: the statistical inefficiency of the recorded series, a finite scalar ``>= 1``
+        that multiplies every variance, or ``"recorded"``: the largest ``g`` of :meth:`recorded_inefficiency` over the rungs, the
+        energy and every recorded column; deliberately conservative.  ``ValueError`` for invalid ``temps`` or ``inefficiency``;
+        raises without a ladder or without records."""
+        from . import statistics
+        temps = statistics.validate_mbar_temps(temps)
+        names = tuple(self.recorded_observables or ())
+        if isinstance(inefficiency, str):
+            inefficiency = self._recorded_g(inefficiency, [tuple(range(len(names)))])[0]
+        g = statistics.validate_profile_inefficiency(inefficiency)
+        if f is None:
+            f = self.ladder_free_energies()["f"]
+        f = self._ladder_f(f, finite=True)
+        k = max(f.size, 1)      # (the ladder's rungs; without a ladder the library refuses before it writes)
+        return statistics._fluctuation_uncertainties(self._lib.me_mbar_gram_fluctuations, (self._handle,), k, f, temps, names, g)
+
     # ------------------------------------------------------------------ statistical inefficiency of the recorded series
     def recorded_inefficiency(self, mintime=3, max_lag=None):
         """The statistical inefficiency ``g = 1 + 2 tau`` of the recorded series, per column and rung, pooled over the chains of

@@ -654,6 +654,105 @@ def mbar_observable_uncertainties(energies, rungs, temps, f, targets, observable
                                      tuple(range(a.shape[0])), g)
 
 
+def validate_mbar_fluctuation_observables(observables, n_samples):
+    """``observables`` of :func:`mbar_fluctuation_uncertainties`: ``None`` (no column: a ``(0, n_samples)`` array) or what
+    :func:`validate_mbar_observables` accepts."""
+    if observables is None:
+        return np.zeros((0, n_samples))
+    return validate_mbar_observables(observables, n_samples)
+
+
+def _fluctuation_uncertainty_result(gram, column_counts, n_rungs, targets, names, energy, observables, moments, n_used, inefficiency):
+    """The dictionary of :func:`mbar_fluctuation_uncertainties` from what ``me_mbar_gram_fluctuations`` returns: ``energy`` =
+    ``(mean_e, var_e)``, each ``(T,)``, ``observables`` = ``(mean, var, cov_energy)``, each ``(T, Q)``, ``moments`` ``(T, 2 + 3
+    Q)`` the shifted moments ``m_i`` that normalise the columns ``E', E'^2`` and ``A'_q, A'_q^2, A'_q E'`` of each target.  With
+    Theta of :func:`mbar_theta` and ``a`` the state column of the target, the covariance of the estimated moments is ``C_ij =
+    m_i m_j (Theta_ij + Theta_aa - Theta_ia - Theta_ja)`` and a variance is ``g^T C g`` with the gradient ``g`` of the quantity
+    (delta method): ``(-2 m_E, 1)`` on ``(E', E'^2)`` for the energy variance, ``(-2 m_A, 1)`` on ``(A', A'^2)`` for an
+    observable's, ``(1, -m_E, -m_A)`` on ``(A' E', A', E')`` for its energy covariance; the shifts drop out.  Targets are taken in
+    the chunks the device used, each chunk on those of its columns whose entries of ``gram`` are finite, as in
+    :func:`_observable_uncertainty_result`: a poisoned observable drops out of the algebra and gets NaN."""
+    k, q, n_targets = n_rungs, len(names), targets.size
+    width = 3 + 3 * q
+    per = (MBAR_GRAM_MAX_COLUMNS - k) // width
+    mean_e, var_e = energy
+    mean, var, cov = observables
+    d_energy = np.full((2, n_targets), np.nan)
+    d_obs = np.full((3, n_targets, q), np.nan)
+    root_g = np.sqrt(inefficiency)
+
+    def sigma(theta, a, rows, m, gradient):
+        c = theta[np.ix_(rows, rows)] + theta[a, a] - theta[rows, a][:, None] - theta[rows, a][None, :]
+        gm = np.asarray(gradient, dtype=np.float64) * m
+        return np.sqrt(max(float(gm @ c @ gm), 0.0)) * root_g
+
+    for t0 in range(0, n_targets, per):
+        nt = min(per, n_targets - t0)
+        idx = np.concatenate([np.arange(k), k + width * t0 + np.arange(width * nt)]).astype(np.intp)
+        idx = idx[np.isfinite(np.diag(gram)[idx])]
+        at = {int(c): i for i, c in enumerate(idx)}      # column of gram -> row of theta
+        theta = mbar_theta(gram[np.ix_(idx, idx)], column_counts[idx])
+        for t in range(t0, t0 + nt):
+            base = k + width * t
+            a, e1, e2 = at[base], at[base + 1], at[base + 2]
+            m_e, m_e2 = moments[t, 0], moments[t, 1]
+            d_energy[0, t] = sigma(theta, a, [e1], [m_e], [1.0])
+            d_energy[1, t] = sigma(theta, a, [e1, e2], [m_e, m_e2], [-2.0 * m_e, 1.0])
+            for c in range(q):
+                if base + 3 + 3 * c not in at:
+                    continue
+                a1, a2, ae = (at[base + 3 + 3 * c + j] for j in range(3))
+                m_a, m_a2, m_ae = moments[t, 2 + 3 * c:5 + 3 * c]
+                d_obs[0, t, c] = sigma(theta, a, [a1], [m_a], [1.0])
+                d_obs[1, t, c] = sigma(theta, a, [a1, a2], [m_a, m_a2], [-2.0 * m_a, 1.0])
+                d_obs[2, t, c] = sigma(theta, a, [ae, a1, e1], [m_ae, m_a, m_e], [1.0, -m_e, -m_a])
+    t_sq = targets * targets
+    return {"temps": targets, "names": tuple(names), "n_samples": int(n_used),
+            "energy_mean": mean_e, "d_energy_mean": d_energy[0], "energy_var": var_e, "d_energy_var": d_energy[1],
+            "heat_capacity": var_e / t_sq, "d_heat_capacity": d_energy[1] / t_sq,
+            "mean": mean, "d_mean": d_obs[0], "var": var, "d_var": d_obs[1], "cov_energy": cov, "d_cov_energy": d_obs[2],
+            "dmean_dT": cov / t_sq[:, None], "d_dmean_dT": d_obs[2] / t_sq[:, None]}
+
+
+def _fluctuation_uncertainties(fn, lead, n_rungs, f, targets, names, inefficiency):
+    q, n = len(names), targets.size
+    c = n_rungs + n * (3 + 3 * q)
+    gram, counts = np.zeros((c, c)), np.zeros(c)
+    ln_z, moments, shift, shifts = np.zeros(n), np.zeros((n, 2 + 3 * q)), np.zeros(1), np.zeros(max(q, 1))
+    energy = [np.zeros(n) for _ in range(2)]
+    observables = [np.zeros((n, q)) for _ in range(3)]
+    n_used = ctypes.c_int64()
+    _call(fn, lead, _capi.double_ptr(f), _capi.double_ptr(targets), n, _capi.double_ptr(gram), _capi.double_ptr(counts),
+          _capi.double_ptr(ln_z), _capi.double_ptr(moments), _capi.double_ptr(shift), _capi.double_ptr(shifts),
+          *map(_capi.double_ptr, energy), *(_capi.double_ptr(a) if q else None for a in observables), ctypes.byref(n_used))
+    return _fluctuation_uncertainty_result(gram, counts, n_rungs, targets, names, energy, observables, moments, n_used.value,
+                                           inefficiency)
+
+
+def mbar_fluctuation_uncertainties(energies, rungs, temps, f, targets, observables=None, inefficiency=1.0, device=0):
+    """Asymptotic standard errors of the reweighted SECOND moments: the energy variance and the heat capacity of
+    :func:`mbar_reweight`, and the variances, energy covariances and temperature derivatives of
+    :func:`mbar_reweight_observables` (``me_mbar_gram_fluctuations_samples``: the Gram matrix of the MBAR weight matrix with the
+    columns ``E', E'^2`` and, per observable, ``A', A'^2, A' E'`` of every target, the products formed in registers on the way
+    to the matrix cores; the algebra of Shirts & Chodera 2008, eqs. 8 and D8, and the delta method run here in float64; the
+    engine form is ``MetropolisEngine.fluctuation_uncertainties``).  ``observables``: ``(Q, n_samples)``, ``Q <= 16``, or
+    ``None`` for the energy keys alone.  Returns ``{"temps", "names", "n_samples"}``, ``{"energy_mean", "energy_var",
+    "heat_capacity"}`` ``(T,)`` and ``{"mean", "var", "cov_energy", "dmean_dT"}`` ``(T, Q)`` -- the values of the two reweighting
+    functions, bit for bit when every energy is finite -- and the standard error of each under ``"d_" + key``.
+
+    The formula assumes INDEPENDENT samples: pass the statistical inefficiency of the series, a finite scalar ``>= 1``, as
+    ``inefficiency``; it multiplies every variance (``ValueError`` otherwise).  A non-finite value of column ``q`` in a used
+    sample gives NaN in that column's four values and errors, and nothing else."""
+    g = validate_profile_inefficiency(inefficiency)
+    e, r, t = validate_mbar_samples(energies, rungs, temps)
+    targets = validate_mbar_temps(targets, "targets")
+    f = validate_mbar_f(f, t.size)
+    a = validate_mbar_fluctuation_observables(observables, e.size)
+    lead = _host_samples(device, e, r, t) + (_capi.double_ptr(a) if a.shape[0] else None, a.shape[0])
+    return _fluctuation_uncertainties(_capi.load().me_mbar_gram_fluctuations_samples, lead, t.size, f, targets,
+                                      tuple(range(a.shape[0])), g)
+
+
 def _ladder_response(ladder_gram, column_counts):
     """``M = N^{1/2} (I - N^{1/2} G_KK N^{1/2})^+ N^{1/2}`` (K x K; the pseudo-inverse cut at ``rcond = 1e-10`` as in
     :func:`mbar_theta`): what is left of MBAR's asymptotic covariance for columns of the weight matrix that have no samples of

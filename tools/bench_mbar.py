@@ -6,6 +6,9 @@
     python tools/bench_mbar.py --observables        (reweighting of recorded observables: whole-call time beside the energy-only call)
     python tools/bench_mbar.py --observable-gram    (the Gram pass with observable columns beside me_mbar_gram at an equal
                                                      column count, profiles/mbar_observable_uncertainty.txt)
+    python tools/bench_mbar.py --fluctuations --rungs 8 32
+                                                    (the Gram pass with second-moment columns beside the observable form on the
+                                                     same input, profiles/mbar_fluctuation_uncertainty.txt)
     python tools/bench_mbar.py --profile            (reweighted histograms along an observable beside the one-column observable
                                                      reweighting, profiles/mbar_profile.txt)
     python tools/bench_mbar.py --profile-uncertainty --rungs 8 32
@@ -201,6 +204,60 @@ def time_observable_gram(k, log2_chains, records, n_targets=8, columns=(1, 4, 16
               "of the times %.2f, of the launched columns %.2f, of their squares %.2f"
               % (q, obs_ms, obs_max, cols_o, rw_ms, nt_e, e_ms, e_max, cols_e, obs_ms / e_ms, sum(cols_o) / sum(cols_e),
                  sum(x * x for x in cols_o) / sum(x * x for x in cols_e)), flush=True)
+
+
+def time_fluctuations(k, log2_chains, records, n_targets=8, columns=(0, 1, 4, 16)):
+    """me_mbar_gram_fluctuations (csrc/me_mbar_cov.hip, the fluctuation form) for Q recorded columns at ``n_targets``
+    temperatures beside me_mbar_gram_observables on the same samples, columns and targets in the same run (Q = 0: beside
+    me_mbar_gram, the energy form, which has no observable form to compare with).  Whole calls (counting pass, the reweighting
+    of the energies and of the observables that supplies the normalisers, the Gram launches of every chunk, the copy of G);
+    the Python method, which adds the host algebra, is timed beside them.  Columns are counted per launch: every chunk of
+    targets carries the K ladder columns."""
+    import ctypes
+    eng, _ = loaded_engine(k, log2_chains, records)
+    n = records << log2_chains
+    f = eng.ladder_free_energies(tol=1e-8)["f"]
+    dp = ctypes.POINTER(ctypes.c_double)
+    targets = np.geomspace(0.5, 3.0, n_targets)
+    energies = eng.energy_samples()
+
+    def launched(per_target):
+        per_chunk = (128 - k) // per_target
+        return [k + per_target * min(per_chunk, n_targets - t0) for t0 in range(0, n_targets, per_chunk)]
+
+    print("K = %d, %d samples, %d targets" % (k, n, n_targets), flush=True)
+    for q in columns:
+        eng.record_observables([j % 4 for j in range(q)] if q else None)
+        eng.set_energy_samples(energies)
+        if q:
+            scale = 1.0 + 0.125 * np.arange(q)
+            eng.set_observable_samples(energies[:, None, :] * scale[None, :, None])
+        c = k + n_targets * (3 + 3 * q)
+        gram, counts = np.zeros((c, c)), np.zeros(c)
+        new = times_ms(lambda: eng._check(eng._lib.me_mbar_gram_fluctuations(
+            eng._handle, f.ctypes.data_as(dp), targets.ctypes.data_as(dp), n_targets, gram.ctypes.data_as(dp), counts.ctypes.data_as(dp),
+            *([None] * 10))))
+        whole = times_ms(lambda: eng.fluctuation_uncertainties(targets, f))
+        per_old = 1 + q if q else 2
+        co = k + n_targets * per_old
+        gram_o, counts_o = np.zeros((co, co)), np.zeros(co)
+        if q:
+            old = times_ms(lambda: eng._check(eng._lib.me_mbar_gram_observables(
+                eng._handle, f.ctypes.data_as(dp), targets.ctypes.data_as(dp), n_targets, gram_o.ctypes.data_as(dp),
+                counts_o.ctypes.data_as(dp), None, None, None, None)))
+            old_whole = times_ms(lambda: eng.observable_uncertainties(targets, f))
+        else:
+            old = times_ms(lambda: eng._check(eng._lib.me_mbar_gram(
+                eng._handle, f.ctypes.data_as(dp), targets.ctypes.data_as(dp), n_targets, gram_o.ctypes.data_as(dp),
+                counts_o.ctypes.data_as(dp), None, None, None)))
+            old_whole = times_ms(lambda: eng.ladder_free_energy_uncertainties(f, targets))
+        cols_n, cols_o = launched(3 + 3 * q), launched(per_old)
+        print("    Q = %2d: me_mbar_gram_fluctuations %.3f ms (slowest of 3: %.3f), launches of %s columns, fluctuation_uncertainties "
+              "%.3f ms; %s %.3f ms (slowest of 3: %.3f), launches of %s columns, %s %.3f ms; ratio of the C calls %.2f, of the "
+              "launched columns %.2f, of their squares %.2f"
+              % (q, min(new), max(new), cols_n, min(whole), "me_mbar_gram_observables" if q else "me_mbar_gram", min(old), max(old),
+                 cols_o, "observable_uncertainties" if q else "ladder_free_energy_uncertainties", min(old_whole), min(new) / min(old),
+                 sum(cols_n) / sum(cols_o), sum(x * x for x in cols_n) / sum(x * x for x in cols_o)), flush=True)
 
 
 def time_profile(k, log2_chains, records, n_targets=8, bins=(64, 256)):
@@ -540,6 +597,7 @@ if __name__ == "__main__":
     ap.add_argument("--gram", action="store_true")
     ap.add_argument("--observables", action="store_true")
     ap.add_argument("--observable-gram", action="store_true")
+    ap.add_argument("--fluctuations", action="store_true")
     ap.add_argument("--profile", action="store_true")
     ap.add_argument("--profile-uncertainty", action="store_true")
     ap.add_argument("--surface", action="store_true")
@@ -573,6 +631,10 @@ if __name__ == "__main__":
     if cli.profile_uncertainty:
         for k in cli.rungs:
             time_profile_uncertainty(k, cli.log2_chains, cli.records, forced_rows=cli.rows_per_pass)
+        sys.exit(0)
+    if cli.fluctuations:
+        for k in cli.rungs:
+            time_fluctuations(k, cli.log2_chains, cli.records)
         sys.exit(0)
     if cli.observable_gram:
         for k in cli.rungs:
