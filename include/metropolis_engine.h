@@ -458,6 +458,23 @@ int me_mbar_energy_shift(me_engine *engine, double *shift);
  *                       me_mbar_reweight, plus ME_ERR_STATE without an observable store.
  *   me_mbar_reweight_observables_samples   the same kernels on host arrays, like me_mbar_reweight_samples; observables is
  *                       [n_observables][n_samples], 1 <= n_observables <= ME_MAX_RECORDED_OBSERVABLES.
+ *   me_mbar_reweight_perturbed   reweighting to states that differ from the sampled ones by more than their temperature (csrc/
+ *                       me_mbar_perturbed.hip has the definition).  Target p has the temperature temps[p] (finite, > 0) and the
+ *                       couplings couplings[p][0 .. Q) (finite) over the Q recorded columns; its energy is H = E + b with b =
+ *                       sum_q couplings[p][q] A_q over the columns whose coupling is not exactly 0, in ascending q, from 0.0, one
+ *                       fma per term (a column whose coupling is 0 is not read for b), and its log weight fma(-H, 1 / T, -d_n)
+ *                       with the d_n of me_mbar_reweight (a sample is used when its ENERGY is finite).  ln_z [n] = ln Z(T_p,
+ *                       lambda_p) / Z(T_0, 0), the zero of me_mbar_reweight's ln_z; mean_h, var_h [n] the mean and variance of H;
+ *                       mean, var, cov_h [n][Q] as me_mbar_reweight_observables' mean, var, cov_energy with H for E;
+ *                       neff_fraction [n].  Any output may be NULL, any number of targets is taken.  With every coupling of a
+ *                       target 0, H = E exactly and mean, var, cov_h, neff_fraction are me_mbar_reweight_observables' bit for
+ *                       bit.  A non-finite value of a column that target p couples to, in a used sample, makes every output of
+ *                       target p non-finite and changes no other target; one of a column it does not couple to makes only that
+ *                       column's mean, var, cov_h non-finite.  All sums have a fixed order: a target is bit for bit the same
+ *                       alone, among any others and at any position.  Errors as for me_mbar_reweight_observables (ME_ERR_STATE
+ *                       without an observable store), and ME_ERR_INVALID for couplings == NULL or a non-finite coupling.
+ *   me_mbar_reweight_perturbed_samples   the same kernels on host arrays; observables is [n_observables][n_samples], couplings
+ *                       [n][n_observables].
  *   me_mbar_gram_observables   me_mbar_gram for the asymptotic covariance of the reweighted means of the Q recorded columns
  *                       (csrc/me_mbar_cov.hip has the definition).  n_targets >= 1 target temperatures.  W has C = n_rungs +
  *                       n_targets (1 + Q) columns: column k < n_rungs is rung k (column_counts[k] = its finite samples), column
@@ -583,6 +600,14 @@ int me_mbar_reweight_observables_samples(int32_t device_id, const double *energi
                                          const double *observables, int32_t n_observables, const double *ladder_temps,
                                          int32_t n_rungs, const double *f, const double *temps, int32_t n, double *mean,
                                          double *var, double *cov_energy, double *neff_fraction);
+int me_mbar_reweight_perturbed(me_engine *engine, const double *f, const double *temps, const double *couplings /* [n][Q] */,
+                               int32_t n, double *ln_z, double *mean_h, double *var_h, double *mean, double *var, double *cov_h,
+                               double *neff_fraction);
+int me_mbar_reweight_perturbed_samples(int32_t device_id, const double *energies, const int32_t *rungs, int64_t n_samples,
+                                       const double *ladder_temps, int32_t n_rungs, const double *f, const double *temps,
+                                       const double *couplings, int32_t n, const double *observables, int32_t n_observables,
+                                       double *ln_z, double *mean_h, double *var_h, double *mean, double *var, double *cov_h,
+                                       double *neff_fraction);
 int me_mbar_gram_observables(me_engine *engine, const double *f, const double *temps, int32_t n_targets, double *gram,
                              double *column_counts, double *ln_z, double *mean, double *shifts, int64_t *n_used);
 int me_mbar_gram_observables_samples(int32_t device_id, const double *energies, const int32_t *rungs, int64_t n_samples,

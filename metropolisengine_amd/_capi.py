@@ -164,6 +164,10 @@ SYMBOLS = {
     "me_mbar_reweight_observables_samples": (ctypes.c_int, [ctypes.c_int32, _dp, ctypes.POINTER(ctypes.c_int32), ctypes.c_int64, _dp,
                                                             ctypes.c_int32, _dp, ctypes.c_int32, _dp, _dp, ctypes.c_int32, _dp, _dp,
                                                             _dp, _dp]),
+    "me_mbar_reweight_perturbed": (ctypes.c_int, [_H, _dp, _dp, _dp, ctypes.c_int32] + [_dp] * 7),
+    "me_mbar_reweight_perturbed_samples": (ctypes.c_int, [ctypes.c_int32, _dp, ctypes.POINTER(ctypes.c_int32), ctypes.c_int64, _dp,
+                                                          ctypes.c_int32, _dp, _dp, _dp, ctypes.c_int32, _dp, ctypes.c_int32] +
+                                           [_dp] * 7),
     "me_mbar_histogram": (ctypes.c_int, [_H, _dp, _dp, ctypes.c_int32, ctypes.c_int32, _dp, ctypes.c_int32, _dp,
                                          ctypes.POINTER(ctypes.c_int64), _dp]),
     "me_mbar_histogram_samples": (ctypes.c_int, [ctypes.c_int32, _dp, ctypes.POINTER(ctypes.c_int32), ctypes.c_int64, _dp,

@@ -37,7 +37,7 @@ KERNEL_DIMS = [
 # (tools/build_variant.sh builds its variants from this list)
 HOST_UNITS = [
     ("me_generic", []), ("me_statistics", []), ("me_runtime_dims", []), ("me_replica", []), ("me_mbar", []), ("me_mbar_newton", []), ("me_mbar_cov", []),
-    ("me_mbar_obs", []), ("me_mbar_hist", []), ("me_mbar_hist_cov", []), ("me_mbar_hist2d", []), ("me_mbar_hist2d_cov", []),
+    ("me_mbar_obs", []), ("me_mbar_perturbed", []), ("me_mbar_hist", []), ("me_mbar_hist_cov", []), ("me_mbar_hist2d", []), ("me_mbar_hist2d_cov", []),
     ("me_series", []), ("me_api", []),
     # population annealing: the weights, sums and slot boundaries must round exactly as written (no fused multiply-adds), so
     # that the scan pass reproduces the weight pass's sums bit for bit and tests/population_reference.py can restate them

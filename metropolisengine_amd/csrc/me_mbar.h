@@ -1,6 +1,7 @@
 // What the MBAR units share (me_mbar.hip: samples, solve, reweighting; me_mbar_newton.hip: the Newton solve; me_mbar_cov.hip:
 // the Gram matrix of the weight matrix for the asymptotic covariance; me_mbar_obs.hip: recorded observables and their
-// reweighting; me_mbar_hist.hip: reweighted histograms along an observable; me_mbar_hist_cov.hip: the slot Gram sums behind
+// reweighting; me_mbar_perturbed.hip: their reweighting to perturbed energies, on the pass state of me_mbar_obs_state.h;
+// me_mbar_hist.hip: reweighted histograms along an observable; me_mbar_hist_cov.hip: the slot Gram sums behind
 // their error bars; me_mbar_hist2d.hip: joint histograms along two; me_mbar_hist2d_cov.hip: the cell Gram sums behind theirs --
 // four pairings of the policies of one pass kernel, me_mbar_slots.h, behind two host drivers, histogram_slots for the masses and
 // slot_gram_passes for the Gram sums): the tile policy,

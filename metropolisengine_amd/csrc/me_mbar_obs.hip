@@ -51,16 +51,14 @@
 // Registers (hipcc -O3, gfx950, -Rpass-analysis=kernel-resource-usage): k_mbar_reweight_obs 194 VGPRs, 2 wavefronts per SIMD;
 // k_mbar_reweight_obs_finish 94, k_mbar_log_denominator 54, k_observable_record 18; no kernel uses scratch.  (Columns beyond a
 // pass's nq are carried along unchanged, never zeroed behind a runtime bound: that indexing put the state into scratch.)
-#include "me_mbar.h"
+// The state, add_sample, the merges and the butterfly live in me_mbar_obs_state.h, which me_mbar_perturbed.hip shares.
+#include "me_mbar_obs_state.h"
 
 #pragma clang fp contract(off)
 
 namespace me {
 namespace mbar {
 namespace {
-
-constexpr int kObsTargets = 4;                  // targets per pass
-constexpr int kObsCols = 4;                     // observable columns per pass
 
 struct ObsSelection {
   int q[ME_MAX_RECORDED_OBSERVABLES];
@@ -101,132 +99,6 @@ __global__ void __launch_bounds__(kThreads) k_observable_record(const R *__restr
 }
 
 // ---- reweighting --------------------------------------------------------------------------------------------------------
-// what a target's weights share, and what one observable column adds
-struct TargetState {
-  double M, W, Q2, mean_e;
-  double mean[kObsCols], M2[kObsCols], C[kObsCols];
-};
-static_assert(sizeof(TargetState) == 16 * sizeof(double), "partials are addressed as 16 doubles per state");
-
-__device__ __forceinline__ void clear(TargetState &s) {
-  s.M = -INFINITY;
-  s.W = s.Q2 = s.mean_e = 0.0;
-#pragma unroll
-  for (int q = 0; q < kObsCols; ++q) s.mean[q] = s.M2[q] = s.C[q] = 0.0;
-}
-
-// one more sample: log weight l, energy e, observable values a[0 .. nq); one exponential, no branch on the data
-__device__ __forceinline__ void add_sample(TargetState &s, double l, double e, const double (&a)[kObsCols], int nq) {
-  const bool higher = l > s.M;
-  const double x = math64::exp_nonpos(higher ? s.M - l : l - s.M);
-  const double scale = higher ? x : 1.0, w = higher ? 1.0 : x;
-  const double W = s.W * scale + w;
-  const double r = w / W;
-  const double mean_e = s.mean_e + (e - s.mean_e) * r;
-  const double we = w * (e - mean_e);           // w (E - mean_E_new)
-#pragma unroll
-  for (int q = 0; q < kObsCols; ++q)
-    if (q < nq) {
-      const double delta = a[q] - s.mean[q];
-      const double mean = s.mean[q] + delta * r;
-      s.M2[q] = s.M2[q] * scale + (w * delta) * (a[q] - mean);
-      s.C[q] = s.C[q] * scale + delta * we;
-      s.mean[q] = mean;
-    }
-  s.Q2 = s.Q2 * (scale * scale) + w * w;
-  s.mean_e = mean_e;
-  s.W = W;
-  s.M = higher ? l : s.M;
-}
-
-__device__ __forceinline__ double pick(bool first, double a, double b) { return first ? a : b; }
-
-// a (earlier in the fixed order) and b joined; an empty side (W = 0) returns the other one unchanged.  Branch-free: the
-// general formula is evaluated and then dropped by selects (what it makes of an empty side, NaN included, is never kept).
-__device__ __forceinline__ TargetState merge(const TargetState &a, const TargetState &b, int nq) {
-  const bool keep_a = !(b.W > 0.0), keep_b = !keep_a && !(a.W > 0.0);
-  TargetState r;
-  const double M = fmax(a.M, b.M);
-  const double sa = math64::exp_nonpos(a.M - M), sb = math64::exp_nonpos(b.M - M);
-  const double Wa = a.W * sa, Wb = b.W * sb;
-  const double W = Wa + Wb;
-  const double fb = Wb / W, cross = Wa * fb;
-  const double delta_e = b.mean_e - a.mean_e;
-  r.M = pick(keep_a, a.M, pick(keep_b, b.M, M));
-  r.W = pick(keep_a, a.W, pick(keep_b, b.W, W));
-  r.mean_e = pick(keep_a, a.mean_e, pick(keep_b, b.mean_e, a.mean_e + delta_e * fb));
-  r.Q2 = pick(keep_a, a.Q2, pick(keep_b, b.Q2, a.Q2 * (sa * sa) + b.Q2 * (sb * sb)));
-#pragma unroll
-  for (int q = 0; q < kObsCols; ++q) {
-    if (q < nq) {
-      const double delta = b.mean[q] - a.mean[q];
-      r.mean[q] = pick(keep_a, a.mean[q], pick(keep_b, b.mean[q], a.mean[q] + delta * fb));
-      r.M2[q] = pick(keep_a, a.M2[q], pick(keep_b, b.M2[q], (a.M2[q] * sa + b.M2[q] * sb) + (delta * delta) * cross));
-      r.C[q] = pick(keep_a, a.C[q], pick(keep_b, b.C[q], (a.C[q] * sa + b.C[q] * sb) + (delta * delta_e) * cross));
-    } else {                                    // (unused columns stay what clear() made them)
-      r.mean[q] = a.mean[q], r.M2[q] = a.M2[q], r.C[q] = a.C[q];
-    }
-  }
-  return r;
-}
-
-// s and o with the lower lane's first
-__device__ __forceinline__ TargetState merge_ordered(bool o_first, const TargetState &s, const TargetState &o, int nq) {
-  TargetState a, b;
-  a.M = pick(o_first, o.M, s.M), b.M = pick(o_first, s.M, o.M);
-  a.W = pick(o_first, o.W, s.W), b.W = pick(o_first, s.W, o.W);
-  a.Q2 = pick(o_first, o.Q2, s.Q2), b.Q2 = pick(o_first, s.Q2, o.Q2);
-  a.mean_e = pick(o_first, o.mean_e, s.mean_e), b.mean_e = pick(o_first, s.mean_e, o.mean_e);
-#pragma unroll
-  for (int q = 0; q < kObsCols; ++q) {
-    a.mean[q] = pick(o_first, o.mean[q], s.mean[q]), b.mean[q] = pick(o_first, s.mean[q], o.mean[q]);
-    a.M2[q] = pick(o_first, o.M2[q], s.M2[q]), b.M2[q] = pick(o_first, s.M2[q], o.M2[q]);
-    a.C[q] = pick(o_first, o.C[q], s.C[q]), b.C[q] = pick(o_first, s.C[q], o.C[q]);
-  }
-  return merge(a, b, nq);
-}
-
-__device__ __forceinline__ TargetState shuffle_xor(const TargetState &s, int d, int nq) {
-  TargetState o;
-  o.M = __shfl_xor(s.M, d);
-  o.W = __shfl_xor(s.W, d);
-  o.Q2 = __shfl_xor(s.Q2, d);
-  o.mean_e = __shfl_xor(s.mean_e, d);
-#pragma unroll
-  for (int q = 0; q < kObsCols; ++q) {
-    if (q < nq) {
-      o.mean[q] = __shfl_xor(s.mean[q], d);
-      o.M2[q] = __shfl_xor(s.M2[q], d);
-      o.C[q] = __shfl_xor(s.C[q], d);
-    } else {
-      o.mean[q] = s.mean[q], o.M2[q] = s.M2[q], o.C[q] = s.C[q];
-    }
-  }
-  return o;
-}
-
-// butterfly over the wavefront; the lower lane's state is always the first operand, so every lane holds the same result
-__device__ __forceinline__ TargetState wave_merge(TargetState s, int nq) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const TargetState o = shuffle_xor(s, d, nq);
-    s = merge_ordered((lane & d) != 0, s, o, nq);
-  }
-  return s;
-}
-
-// the block's wavefront results in order (thread 0 returns the block's state)
-__device__ __forceinline__ TargetState block_merge(const TargetState &w, TargetState *waves, int nq) {
-  if ((threadIdx.x & 63) == 0) waves[threadIdx.x >> 6] = w;
-  __syncthreads();
-  TargetState b = waves[0];
-  if (threadIdx.x == 0)
-    for (int k = 1; k < kWaves; ++k) b = merge(b, waves[k], nq);
-  __syncthreads();
-  return b;
-}
-
 // d_n = m_n + ln s_n of every sample of the padded range [0, n_padded); NaN when the energy is not finite or n <= i
 __global__ void __launch_bounds__(kThreads) k_mbar_log_denominator(const double *__restrict__ energies, long long n, long long n_padded,
                                                                     int n_rungs, const double *__restrict__ table, double *d) {

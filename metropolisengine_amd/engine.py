@@ -811,6 +811,31 @@ class MetropolisEngine:
         f = self._ladder_f(f, finite=False)
         return statistics._reweight_observables(self._lib.me_mbar_reweight_observables, (self._handle,), f, temps, names)
 
+    def reweight_perturbed(self, temps, couplings, f=None):
+        """The ladder's samples reweighted to states that differ by more than their temperature
+        (``me_mbar_reweight_perturbed``, on the device): target ``p`` has the temperature ``temps[p]`` (a scalar serves every
+        target) and the energy ``H = E + sum_q couplings[p, q] A_q`` over the recorded columns ``A_q`` -- a field conjugate to
+        an order parameter (``{"real_0": -h}``), a changed stiffness (``{"real_0_sq": lam}``), a changed coefficient of one
+        term of an energy dictionary (``{"energy_<term>": c_new / c - 1}``).  ``couplings``: ``(P, Q)`` in the order of
+        :attr:`recorded_observables`, or a dictionary from recorded names or column indices to scalars or ``(P,)``; columns
+        it does not name are 0.  ``f``: the free energies of :meth:`ladder_free_energies` (solved with the defaults when
+        ``None``).  Returns ``{"temps", "couplings" (P, Q), "names", "ln_z", "hamiltonian_mean", "hamiltonian_var",
+        "heat_capacity", "perturbation_mean", "mean", "var", "cov_hamiltonian", "dmean_dT", "neff_fraction"}`` (see
+        :func:`metropolisengine_amd.statistics.mbar_reweight_perturbed`).  Bitwise reproducible; a target does not depend on
+        what else is asked for, and a column whose coupling is exactly 0 never enters ``H``.  ``ValueError`` for invalid
+        ``temps`` or ``couplings`` (shape, unknown name, a column named twice, non-finite); raises without a ladder, without
+        records or without an observable store."""
+        from . import statistics
+        temps = statistics.broadcast_mbar_targets(temps, couplings)
+        names = self.recorded_observables
+        if not names:
+            raise ValueError("no observable store: call record_observables first")
+        lam = statistics.validate_mbar_couplings(couplings, temps.size, names)
+        if f is None:
+            f = self.ladder_free_energies()["f"]
+        f = self._ladder_f(f, finite=False)
+        return statistics._reweight_perturbed(self._lib.me_mbar_reweight_perturbed, (self._handle,), f, temps, lam, names)
+
     def free_energy_profile(self, which, edges, temps, f=None):
         """The reweighted histogram of one recorded quantity and the free-energy profile ``F(A; T) = -T ln p(A; T)`` along it at
         each temperature of ``temps`` (``me_mbar_histogram``, on the device: the samples stay there).  ``which``: a name of

@@ -349,6 +349,97 @@ def mbar_reweight_observables(energies, rungs, temps, f, targets, observables, d
                                  tuple(range(a.shape[0])))
 
 
+def validate_mbar_couplings(couplings, n_targets, names):
+    """``couplings`` of a perturbed reweighting as a contiguous float64 ``(P, Q)`` array, ``P = n_targets`` and ``Q =
+    len(names)`` the columns in their order.  An array: ``(P, Q)``, or ``(Q,)`` for every target alike.  A dictionary: the keys
+    are entries of ``names`` or column indices, the values scalars or ``(P,)``; columns it does not name are 0.  ``ValueError``
+    for a shape mismatch, an unknown name or index, a column named twice (by its name and by its index, say) or a non-finite
+    coupling.  Runs before the library is touched."""
+    names = tuple(names)
+    p, q = int(n_targets), len(names)
+    if isinstance(couplings, dict):
+        lam = np.zeros((p, q))
+        seen = set()
+        for key, value in couplings.items():
+            if isinstance(key, (int, np.integer)) and not isinstance(key, bool):
+                if not 0 <= int(key) < q:
+                    raise ValueError("coupling index %d outside the %d columns" % (int(key), q))
+                col = int(key)
+            elif key in names:
+                col = names.index(key)
+            else:
+                raise ValueError("unknown column %r; the columns are %s" % (key, ", ".join(map(str, names))))
+            if col in seen:
+                raise ValueError("column %r is coupled twice" % (names[col],))
+            seen.add(col)
+            v = np.asarray(value, dtype=np.float64)
+            if v.ndim > 1 or (v.ndim == 1 and v.size != p):
+                raise ValueError("the coupling of %r must be a scalar or hold one value per target (%d)" % (key, p))
+            lam[:, col] = v
+    else:
+        lam = np.asarray(couplings, dtype=np.float64)
+        if lam.ndim == 1 and lam.size == q:
+            lam = np.broadcast_to(lam, (p, q))
+        if lam.shape != (p, q):
+            raise ValueError("couplings must be (targets = %d, columns = %d), got %s" % (p, q, lam.shape))
+    if not np.all(np.isfinite(lam)):
+        raise ValueError("couplings must be finite")
+    return np.ascontiguousarray(lam, dtype=np.float64)
+
+
+def broadcast_mbar_targets(temps, couplings):
+    """``temps`` (a scalar or ``(P,)``) as ``(P,)`` for couplings that name ``P`` targets: one temperature serves them all.
+    ``P`` is the length of ``temps`` unless that is 1, then the rows of a 2-d ``couplings`` or the longest value of a
+    dictionary."""
+    t = validate_mbar_temps(temps, "targets")
+    if t.size == 1:
+        if isinstance(couplings, dict):
+            p = max([np.asarray(v).size for v in couplings.values() if np.ndim(v) == 1] + [1])
+        else:
+            p = np.shape(couplings)[0] if np.ndim(couplings) == 2 else 1
+        t = np.ascontiguousarray(np.broadcast_to(t, (max(p, 1),)))
+    return t
+
+
+def _perturbed_result(temps, couplings, names, ln_z, mean_h, var_h, mean, var, cov, neff):
+    t2 = temps * temps
+    return {"temps": temps, "couplings": couplings, "names": tuple(names), "ln_z": ln_z, "hamiltonian_mean": mean_h,
+            "hamiltonian_var": var_h, "heat_capacity": var_h / t2,
+            "perturbation_mean": np.array([sum(row[q] * m[q] for q in np.flatnonzero(row)) for row, m in zip(couplings, mean)],
+                                          dtype=np.float64),
+            "mean": mean, "var": var, "cov_hamiltonian": cov, "dmean_dT": cov / t2[:, None], "neff_fraction": neff}
+
+
+def _reweight_perturbed(fn, lead, f, targets, couplings, names, columns=()):
+    """``columns``: the trailing ``(observables, n_observables)`` of the engine-less form."""
+    out = [np.zeros(targets.size) for _ in range(3)] + [np.zeros((targets.size, len(names))) for _ in range(3)] + [np.zeros(targets.size)]
+    _call(fn, lead, _capi.double_ptr(f), _capi.double_ptr(targets), _capi.double_ptr(couplings), targets.size, *columns,
+          *map(_capi.double_ptr, out))
+    return _perturbed_result(targets, couplings, names, *out)
+
+
+def mbar_reweight_perturbed(energies, rungs, temps, f, targets, couplings, observables, device=0):
+    """Reweight the samples of a ladder (``temps``, free energies ``f`` of :func:`mbar_free_energies`) to states that differ
+    by more than their temperature (``me_mbar_reweight_perturbed_samples``; the engine form is
+    ``MetropolisEngine.reweight_perturbed``): target ``p`` has the temperature ``targets[p]`` (a scalar serves every target)
+    and the energy ``H = E + sum_q couplings[p, q] A_q`` over the columns ``A_q`` of ``observables`` ``(Q, n_samples)``.
+    ``couplings``: see :func:`validate_mbar_couplings` (the names of the columns are their numbers).  Returns ``{"temps",
+    "couplings" (P, Q), "names", "ln_z", "hamiltonian_mean", "hamiltonian_var", "heat_capacity", "perturbation_mean", "mean",
+    "var", "cov_hamiltonian", "dmean_dT", "neff_fraction"}``: ``ln_z = ln Z(T, lambda) / Z(T_0, 0)`` (the zero of
+    :func:`mbar_reweight`), the mean and variance of ``H``, ``heat_capacity = hamiltonian_var / T^2``, ``perturbation_mean =
+    sum_q lambda_q mean_q``, the mean and variance of every column and its covariance with ``H`` ``(P, Q)``, ``dmean_dT =
+    cov_hamiltonian / T^2``.  A column whose coupling is exactly 0 never enters ``H``; a non-finite value in a coupled column
+    of a used sample makes every result of that target non-finite and changes no other target."""
+    e, r, t = validate_mbar_samples(energies, rungs, temps)
+    targets = broadcast_mbar_targets(targets, couplings)
+    f = validate_mbar_f(f, t.size)
+    a = validate_mbar_observables(observables, e.size)
+    names = tuple(range(a.shape[0]))
+    lam = validate_mbar_couplings(couplings, targets.size, names)
+    return _reweight_perturbed(_capi.load().me_mbar_reweight_perturbed_samples, _host_samples(device, e, r, t), f, targets, lam, names,
+                               (_capi.double_ptr(a), a.shape[0]))
+
+
 MBAR_MAX_HISTOGRAM_BINS = 256   # bins of a reweighted histogram (ME_MAX_HISTOGRAM_BINS)
 
 

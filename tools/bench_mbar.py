@@ -4,6 +4,9 @@
     python tools/bench_mbar.py --one-solve 16       (a single solve, for a kernel trace around it)
     python tools/bench_mbar.py --gram               (the Gram pass of the asymptotic error bars, profiles/mbar_uncertainty.txt)
     python tools/bench_mbar.py --observables        (reweighting of recorded observables: whole-call time beside the energy-only call)
+    python tools/bench_mbar.py --perturbed --rungs 8 32
+                                                    (reweighting to perturbed energies, every column coupled and one column
+                                                     coupled, beside the observable reweighting, profiles/mbar_perturbed.txt)
     python tools/bench_mbar.py --observable-gram    (the Gram pass with observable columns beside me_mbar_gram at an equal
                                                      column count, profiles/mbar_observable_uncertainty.txt)
     python tools/bench_mbar.py --fluctuations --rungs 8 32
@@ -156,6 +159,36 @@ def time_observables(k, log2_chains, records, n_targets=8, columns=(1, 4, 16)):
         print("    Q = %2d: %.3f ms = %.2f x energy-only; %d passes, %.2f GB of sample traffic: whole call >= %.0f GB/s = %.0f %% "
               "of the %.1f TB/s HBM rate (a lower bound for the passes)" % (q, ms, ms / energy_ms, len(passes), 1e-9 * traffic, 1e-9 * traffic / (1e-3 * ms),
                                       100 * traffic / (1e-3 * ms) / HBM_RATE, 1e-12 * HBM_RATE), flush=True)
+
+
+def time_perturbed(k, log2_chains, records, n_targets=8, columns=(1, 4, 16)):
+    """me_mbar_reweight_perturbed (csrc/me_mbar_perturbed.hip) for Q recorded columns at ``n_targets`` targets, with every column
+    coupled and with one column coupled, beside me_mbar_reweight_observables on the same input in the same run (the yardstick:
+    a kernel the perturbed unit does not touch).  Both times are wall times of the WHOLE call.  Per chunk of 4 targets the
+    perturbed call adds one bias pass, which reads its coupled columns and writes 32 bytes per sample, and every pass of 4
+    columns reads those 32 bytes on top of what k_mbar_reweight_obs reads."""
+    eng, _ = loaded_engine(k, log2_chains, records)
+    n = records << log2_chains
+    f = eng.ladder_free_energies(tol=1e-8)["f"]
+    targets = np.geomspace(0.5, 3.0, n_targets)
+    energies = eng.energy_samples()
+    print("K = %d, %d samples, %d targets" % (k, n, n_targets), flush=True)
+    for q in columns:
+        eng.record_observables([j % 4 for j in range(q)])
+        eng.set_energy_samples(energies)
+        scale = 1.0 + 0.125 * np.arange(q)
+        eng.set_observable_samples(energies[:, None, :] * scale[None, :, None])
+        obs_ms = best(lambda: eng.reweight_observables(targets, f))
+        line = "    Q = %2d: reweight_observables %.3f ms;" % (q, obs_ms)
+        for label, coupled in (("every column coupled", q), ("one column coupled", 1)):
+            lam = np.zeros((n_targets, q))
+            lam[:, :coupled] = 0.02 / coupled
+            ms = best(lambda: eng.reweight_perturbed(targets, lam, f))
+            chunks, col_passes = -(-n_targets // 4), -(-q // 4)
+            traffic = n * (16 + chunks * ((coupled * 8 + 32) + sum((1 + min(4, q - q0)) * 8 + 8 + 32 for q0 in range(0, q, 4))))
+            line += " %s %.3f ms = %.2f x (%d bias + %d column passes, %.2f GB, whole call >= %.0f GB/s);" % (
+                label, ms, ms / obs_ms, chunks, chunks * col_passes, 1e-9 * traffic, 1e-9 * traffic / (1e-3 * ms))
+        print(line, flush=True)
 
 
 def time_observable_gram(k, log2_chains, records, n_targets=8, columns=(1, 4, 16)):
@@ -596,6 +629,7 @@ if __name__ == "__main__":
     ap.add_argument("--one-solve", type=int, default=0)
     ap.add_argument("--gram", action="store_true")
     ap.add_argument("--observables", action="store_true")
+    ap.add_argument("--perturbed", action="store_true")
     ap.add_argument("--observable-gram", action="store_true")
     ap.add_argument("--fluctuations", action="store_true")
     ap.add_argument("--profile", action="store_true")
@@ -635,6 +669,10 @@ if __name__ == "__main__":
     if cli.fluctuations:
         for k in cli.rungs:
             time_fluctuations(k, cli.log2_chains, cli.records)
+        sys.exit(0)
+    if cli.perturbed:
+        for k in cli.rungs:
+            time_perturbed(k, cli.log2_chains, cli.records)
         sys.exit(0)
     if cli.observable_gram:
         for k in cli.rungs:
